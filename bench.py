@@ -53,7 +53,48 @@ def parse():
     ap.add_argument("--no-secondary", action="store_true", help="skip the config 2 / 4 / 5 lines")
     ap.add_argument("--no-e2e", action="store_true", help="skip the PCIe-inclusive pass (e2e_gcups)")
     ap.add_argument("--gen-workers", type=int, default=0, help="processes for input generation (0 = auto; use 1 under rocprofv3)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all; "
+                         "a fixed, seeded sample of the pairs' CIGAR runs): two builds run with the same arguments compare file by file")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+DUMP_BYTES = 64 * 10**6       # --dump-outputs: the payload of all files together
+DUMP_SEED = 20240607          # --dump-outputs: which pairs' CIGAR runs (and, for very large batches, which pairs) are written
+DUMP_CIGAR_PAIRS = 1024
+
+
+def dump_outputs(np, dirname, res, runs, off):
+    """--dump-outputs: the arrays a caller of the timed path receives from its last step -- per pair: score, query_idx, reference_idx,
+    cells, status (+ cigar_len with traceback) -- and the packed (len << 4 | op) CIGAR runs of a seeded sample of DUMP_CIGAR_PAIRS pairs
+    (`cigar_pairs`: their indices, `cigar_offsets`: pair k's runs are cigar_runs[cigar_offsets[k]:cigar_offsets[k + 1]]). Everything is
+    written as float64, which holds these integers exactly. Per-pair arrays take at most half of DUMP_BYTES: a larger batch is written for a
+    seeded sample of its pairs (`pair_index`); the CIGAR sample ends before the pair whose runs would pass DUMP_BYTES. Returns the names."""
+    os.makedirs(dirname, exist_ok=True)
+    fields = [f for f in ("score", "query_idx", "reference_idx", "cells", "status", "cigar_len") if f in res and (f != "cigar_len" or runs is not None)]
+    n = len(res["score"])
+    rng = np.random.default_rng(DUMP_SEED)
+    keep = max(1, (DUMP_BYTES // 2) // (8 * (len(fields) + 1)))
+    idx = np.arange(n, dtype=np.int64) if n <= keep else np.sort(rng.choice(n, keep, replace=False))
+    out = {"pair_index": idx}
+    for f in fields:
+        out[f] = np.asarray(res[f])[idx]
+    if runs is not None:
+        budget = DUMP_BYTES - 8 * sum(len(v) for v in out.values())
+        pick = np.sort(np.random.default_rng(DUMP_SEED + 1).choice(n, min(n, DUMP_CIGAR_PAIRS), replace=False))
+        off = np.asarray(off, dtype=np.int64)
+        lens = off[pick + 1] - off[pick]
+        fit = int(np.searchsorted(np.cumsum(lens + 2) * 8, budget, side="right"))   # (+2: the pair's index and offset)
+        pick, lens = pick[:fit], lens[:fit]
+        out["cigar_pairs"] = pick
+        out["cigar_offsets"] = np.concatenate([[0], np.cumsum(lens)])
+        out["cigar_runs"] = np.concatenate([np.asarray(runs[int(off[p]): int(off[p + 1])]) for p in pick]) if fit else np.zeros(0)
+    for name, v in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+    return sorted(out)
 
 
 def usable_cpus() -> int:
@@ -300,6 +341,9 @@ def run_multibatch(a):
     if trace:
         runs, off = mb.cigars(res["cigar_len"])
         rescored = self_check(np, w, res, runs, off, range(0, n_total, max(1, n_total // 256)))
+    if a.dump_outputs:
+        dumped = dump_outputs(np, a.dump_outputs, res, runs, off)
+        print(f"bench.py: wrote {', '.join(dumped)} to {a.dump_outputs}", file=sys.stderr)
     mb.close()
     # the oracle as checker and reported CPU baseline, on a bounded sample: the first pairs of EVERY device's slice (the checker runs after
     # the timed region and is never the thing measured)
@@ -481,6 +525,9 @@ def main():
             runs, off = batch.cigars(res["cigar_len"])
         # oracle-independent self-check of the HIP output: a spread of pairs' CIGARs re-walked and re-scored
         rescored = self_check(np, w, res, runs, off, range(0, n_rank, max(1, n_rank // 256))) if trace else 0
+        if a.dump_outputs:
+            dumped = dump_outputs(np, a.dump_outputs, res, runs, off)
+            print(f"bench.py: wrote {', '.join(dumped)} to {a.dump_outputs}", file=sys.stderr)
 
         batch.close()      # the 10 kbp batch's trace arena is most of the device memory: free it before the side configurations
         e2e = None
