@@ -21,6 +21,7 @@
 
 #include "../../include/block_aligner_hip.h"
 #include "aa_matrices.inc"
+#include "ba_extend.h"
 #include "ba_params.h"
 
 using ba::BatchParams;
@@ -51,6 +52,10 @@ extern "C" hipError_t ba_launch_walk(hipStream_t, const BatchParams*, uint32_t g
 extern "C" hipError_t ba_launch_merge_retry(hipStream_t, const uint32_t*, uint32_t, const BatchParams*, const BatchParams*, const uint32_t*, uint32_t*);
 extern "C" hipError_t ba_launch_pack_sequences(hipStream_t, int, const uint8_t*, const uint64_t*, const uint64_t*, const uint64_t*, const uint32_t*,
                                                const uint64_t*, const uint32_t*, uint8_t*, uint32_t, uint32_t, unsigned long long*);
+extern "C" hipError_t ba_launch_pack_images(hipStream_t, int, const uint8_t*, const uint64_t*, const uint64_t*, const uint8_t*, const uint64_t*, const uint32_t*,
+                                            const uint64_t*, const uint32_t*, uint8_t*, uint32_t, uint32_t, unsigned long long*);
+extern "C" hipError_t ba_launch_extend_results(hipStream_t, const ba::ExtendParams*);
+extern "C" hipError_t ba_launch_extend_gather(hipStream_t, const ba::ExtendParams*);
 
 typedef hipError_t (*LaunchFn)(int, int, unsigned, unsigned, hipStream_t, const BatchParams*);
 typedef hipError_t (*OccFn)(int, int, unsigned, int*);
@@ -427,6 +432,15 @@ static void profile_image(const AAProfile* pr, uint32_t P, uint8_t* dst) {
 struct NoProfiles { const AAProfile* operator()(size_t) const { return nullptr; } };
 
 constexpr size_t POOL_SLACK = 256;
+// Seed-and-extend batches (ba_extend_batch_*): every pair's query / reference is a slice of the caller's bytes, which are on the device
+// already (uploaded once, [host_base, host_base + bytes) at dev_base); k_pack_images cuts the images out of them, reversed and / or
+// complemented as `flags` says (2 per pair, caller's order: query, reference; ba::IMG_*). seed_of names the seed a pair belongs to.
+struct ExtImages {
+    const uint8_t* host_base = nullptr; const uint8_t* dev_base = nullptr;
+    const uint8_t* flags = nullptr;
+    const uint32_t* seed_of = nullptr;
+    float* pack_ms = nullptr;   // (optional) device time of the packer
+};
 struct Packed {   // host-side packing of a set of pairs: padded images + the per-pair arrays the kernels read
     std::vector<uint64_t> qo, ro, cig_off;
     std::vector<uint32_t> ql, rl;
@@ -437,6 +451,7 @@ struct Packed {   // host-side packing of a set of pairs: padded images + the pe
     bool on_device = false;
     const uint8_t* raw = nullptr; uint64_t raw_bytes = 0; uint32_t pad = 0;
     std::vector<uint64_t> raw_qo, raw_ro;
+    const ExtImages* ext = nullptr; std::vector<uint8_t> ext_flags;   // extension images (device order, 2 per pair)
     // Device order: entry s of every array above describes the caller's pair order[s] (empty = the caller's order). The
     // waves take pairs in device order, which is longest first (greedy longest-processing-time): no wave starts a long pair
     // when the rest of the batch is done. Lognormal protein lengths (22..8881, SURVEY 8d's config 4): +16 % score only,
@@ -446,7 +461,7 @@ struct Packed {   // host-side packing of a set of pairs: padded images + the pe
 };
 template <class GetSeq, class GetProfile, class Lap>
 static int pack_pairs_in_order(int kind, Gaps gaps, size_t min_size, size_t max_size, uint32_t mode, size_t n, bool already_converted,
-                               GetSeq get, GetProfile getp, Packed& P, Lap lap) {
+                               GetSeq get, GetProfile getp, Packed& P, Lap lap, const ExtImages* ext = nullptr) {
     const bool profile = kind == BA_KIND_PROFILE_;
     // ---- PaddedBytes images: [NULL] + bytes + NULL x (max_size + 16)
     const size_t pad = max_size + 16;
@@ -493,6 +508,18 @@ static int pack_pairs_in_order(int kind, Gaps gaps, size_t min_size, size_t max_
     total += POOL_SLACK;   // behind the last image: the kernels read whole 128-byte rows of a block unpredicated (prefetch_seq)
     lap("offsets");
     P.total = total; P.maxlen2 = maxlen2; P.cig_total = cig_total; P.pad = (uint32_t)pad;
+    if (ext) {   // extension images: always cut on the device, out of the caller's bytes uploaded once
+        P.on_device = true; P.ext = ext; P.raw = ext->host_base;
+        P.raw_qo.resize(n); P.raw_ro.resize(n); P.ext_flags.resize(2 * n);
+        for (size_t p = 0; p < n; p++) {
+            const uint8_t* ptr; size_t len;
+            get(p, 0, &ptr, &len); P.raw_qo[p] = (uint64_t)(ptr - ext->host_base);
+            get(p, 1, &ptr, &len); P.raw_ro[p] = (uint64_t)(ptr - ext->host_base);
+            P.ext_flags[2 * p] = ext->flags[2 * P.who(p)]; P.ext_flags[2 * p + 1] = ext->flags[2 * P.who(p) + 1];
+        }
+        lap("extension image offsets");
+        return 0;
+    }
     // One dense host buffer (the pooled batch calls): ship it as it is, pad and convert on the device. Scattered or
     // overlapping sources (PaddedBytes handles, a reference shared by many pairs) and profile batches are packed here.
     if (!profile && !already_converted && n >= 256 && n < (1u << 30) && (uint64_t)(hi - lo) <= 2 * sum_len + 4096 && !dev_env("BA_HOST_PACK")) {
@@ -543,7 +570,7 @@ static int pack_pairs_in_order(int kind, Gaps gaps, size_t min_size, size_t max_
 
 template <class GetSeq, class GetProfile, class Lap>
 static int pack_pairs(int kind, Gaps gaps, size_t min_size, size_t max_size, uint32_t mode, size_t n, bool already_converted,
-                      GetSeq get, GetProfile getp, Packed& P, Lap lap) {
+                      GetSeq get, GetProfile getp, Packed& P, Lap lap, const ExtImages* ext = nullptr) {
     std::vector<uint64_t> cost(n);   // cells to fill ~ (|q| + |r|) x block size
     for (size_t p = 0; p < n; p++) {
         const uint8_t* ptr; size_t len;
@@ -559,10 +586,10 @@ static int pack_pairs(int kind, Gaps gaps, size_t min_size, size_t max_size, uin
     if (identity || dev_env("BA_CALLER_ORDER")) P.order.clear();
     lap("longest-first order");
     const std::vector<uint32_t>& order = P.order;
-    if (order.empty()) return pack_pairs_in_order(kind, gaps, min_size, max_size, mode, n, already_converted, get, getp, P, lap);
+    if (order.empty()) return pack_pairs_in_order(kind, gaps, min_size, max_size, mode, n, already_converted, get, getp, P, lap, ext);
     return pack_pairs_in_order(kind, gaps, min_size, max_size, mode, n, already_converted,
                                [&](size_t s, int w, const uint8_t** ptr, size_t* len) { get(order[s], w, ptr, len); },
-                               [&](size_t s) { return getp(order[s]); }, P, lap);
+                               [&](size_t s) { return getp(order[s]); }, P, lap, ext);
 }
 
 // Pair-slot batches: pair p's region of the trace arena holds its expected stack -- every step at the minimum block size, one
@@ -801,6 +828,26 @@ static int batch_alloc_scratch(BaBatch* b) {
 // Sequence images into b->pool; the per-pair offset / length arrays must already be on the device.
 static int upload_images(BaBatch* b, const Packed& P, size_t n) {
     if (!P.on_device) { HIP_TRY(hipMemcpy(b->pool.p, P.image.data(), P.total, hipMemcpyHostToDevice)); return 0; }
+    if (P.ext) {   // extension images: the caller's bytes are on the device already
+        DevBuf raw_q, raw_r, flags, err;
+        if (raw_q.alloc(n * 8) || raw_r.alloc(n * 8) || flags.alloc(2 * n) || err.alloc(8)) return 1;
+        HIP_TRY(hipMemcpy(raw_q.p, P.raw_qo.data(), n * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(raw_r.p, P.raw_ro.data(), n * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(flags.p, P.ext_flags.data(), 2 * n, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(err.p, 0xff, 8));
+        HIP_TRY(hipMemset((uint8_t*)b->pool.p + P.total - POOL_SLACK, null_byte(b->kind), POOL_SLACK));
+        HIP_TRY(hipEventRecord(b->ev0, b->stream));
+        HIP_TRY(ba_launch_pack_images(b->stream, seq_kind(b->kind), P.ext->dev_base, raw_q.as<uint64_t>(), raw_r.as<uint64_t>(), flags.as<uint8_t>(),
+                                      b->q_off.as<uint64_t>(), b->q_len.as<uint32_t>(), b->r_off.as<uint64_t>(), b->r_len.as<uint32_t>(),
+                                      b->pool.as<uint8_t>(), P.pad, (uint32_t)n, err.as<unsigned long long>()));
+        HIP_TRY(hipEventRecord(b->ev1, b->stream));
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        if (P.ext->pack_ms) HIP_TRY(hipEventElapsedTime(P.ext->pack_ms, b->ev0, b->ev1));
+        unsigned long long e = 0;
+        HIP_TRY(hipMemcpy(&e, err.p, 8, hipMemcpyDeviceToHost));
+        if (e != ~0ull) return fail("seed %u: byte 0x%02x is outside the matrix alphabet", P.ext->seed_of[P.who((size_t)(e >> 8))], (unsigned)(e & 0xff));
+        return 0;
+    }
     DevBuf raw, raw_q, raw_r, err;
     if (raw.alloc(P.raw_bytes) || raw_q.alloc(n * 8) || raw_r.alloc(n * 8) || err.alloc(8)) return 1;
     HIP_TRY(hipMemcpy(raw.p, P.raw, P.raw_bytes, hipMemcpyHostToDevice));
@@ -825,7 +872,7 @@ static void plan_exclusive(BaBatch* b, const std::vector<uint32_t>& ql, const st
 // `getp(p)` instead.
 template <class GetSeq, class GetProfile = NoProfiles>
 static BaBatch* batch_build(int kind, const void* matrix, Gaps gaps, SizeRange size, int32_t x_drop, uint32_t mode, size_t n,
-                            bool already_converted, GetSeq get, GetProfile getp = GetProfile()) {
+                            bool already_converted, GetSeq get, GetProfile getp = GetProfile(), const ExtImages* ext = nullptr) {
     if (ensure_device()) return nullptr;
     const bool verbose = dev_env("BA_SETUP_TIMING") != nullptr;   // development: where the batch set-up time goes
     auto t_last = std::chrono::steady_clock::now();
@@ -863,7 +910,7 @@ static BaBatch* batch_build(int kind, const void* matrix, Gaps gaps, SizeRange s
     b->gap_open = gaps.open; b->gap_extend = gaps.extend; b->x_drop = x_drop;
 
     Packed P;
-    if (pack_pairs(kind, gaps, min_size, max_size, mode, n, already_converted, get, getp, P, lap)) return nullptr;
+    if (pack_pairs(kind, gaps, min_size, max_size, mode, n, already_converted, get, getp, P, lap, ext)) return nullptr;
     std::vector<uint64_t>& qo = P.qo; std::vector<uint64_t>& ro = P.ro; std::vector<uint32_t>& ql = P.ql; std::vector<uint32_t>& rl = P.rl;
     std::vector<uint64_t>& cig_off = P.cig_off;
     const uint64_t total = P.total, maxlen2 = P.maxlen2, cig_total = P.cig_total;
@@ -1044,13 +1091,13 @@ static int upload_dev_of(BaBatch* b) {
 // Replace the pairs of an existing batch (same matrix, gaps, block range and modes); the device buffers -- above all the
 // trace arena, whose allocation dominates the set-up time -- are reused, so the new set must fit what they were sized for.
 template <class GetSeq, class GetProfile = NoProfiles>
-static int batch_reload(BaBatch* b, size_t n, bool already_converted, GetSeq get, GetProfile getp = GetProfile()) {
+static int batch_reload(BaBatch* b, size_t n, bool already_converted, GetSeq get, GetProfile getp = GetProfile(), const ExtImages* ext = nullptr) {
     if (!b) return fail("null batch");
     if (b->in_flight) return fail("reload: the batch has a launch in flight (ba_batch_wait first)");
     if (n == 0 || n > b->cap_n) return fail("reload: %zu pairs exceed the batch's capacity of %llu", n, (unsigned long long)b->cap_n);
     HIP_TRY(hipSetDevice(b->device));
     Packed P;
-    if (pack_pairs(b->kind, Gaps{(int8_t)b->gap_open, (int8_t)b->gap_extend}, b->min_size, b->max_size, b->mode, n, already_converted, get, getp, P, [](const char*) {})) return 1;
+    if (pack_pairs(b->kind, Gaps{(int8_t)b->gap_open, (int8_t)b->gap_extend}, b->min_size, b->max_size, b->mode, n, already_converted, get, getp, P, [](const char*) {}, ext)) return 1;
     if (P.total > b->cap_pool) return fail("reload: %llu sequence bytes exceed the batch's capacity of %llu", (unsigned long long)P.total, (unsigned long long)b->cap_pool);
     if (P.maxlen2 > b->cap_maxlen2) return fail("reload: a pair is longer (%llu) than the longest pair the batch was created with (%llu)", (unsigned long long)P.maxlen2 - 2, (unsigned long long)b->cap_maxlen2 - 2);
     if ((b->mode & BA_TRACE) && P.cig_total > b->cap_cig) return fail("reload: CIGAR capacity exceeded");
@@ -1410,6 +1457,179 @@ static void to_caller_order(const std::vector<uint32_t>& order, T* dst) {
     for (size_t s = 0; s < order.size(); s++) dst[order[s]] = tmp[s];
 }
 
+// ------------------------------------------------------------------ seed-and-extend batches (ba_extend_batch_*)
+// One seed = one result: X-drop alignment leftwards from the seed (reversed prefixes) and rightwards from its end. Every non-empty side of
+// every seed is a pair of ONE ordinary batch (batch_build: same planning, kernels and re-runs), whose images k_pack_images cuts out of the
+// caller's bytes on the device -- uploaded once, no slice copied on the host; the splice (ba_extend.hip) then scores the seeds and joins
+// both sides' results and CIGAR runs per seed on the device, in the caller's order.
+struct ExtSet {   // a seed set cut into sides (host addresses into the caller's pool; nothing is copied)
+    const uint8_t* lo = nullptr; uint64_t bytes = 0;   // extent of the seeds' sequences in the caller's pool
+    std::vector<const uint8_t*> src;                   // 2 per side (query, reference): first byte of the slice
+    std::vector<uint32_t> len;                         // 2 per side
+    std::vector<uint8_t> flags;                        // 2 per side: ba::IMG_*
+    std::vector<uint32_t> seed_of;                     // per side
+    std::vector<uint32_t> side;                        // 2 per seed (left, right): index of the side, or ba::EXT_NO_SIDE
+    std::vector<uint64_t> s_raw_q, s_raw_r, s_img_q, s_img_r;   // the seeds' own images: source offsets in the upload, offsets in the seed pool
+    std::vector<uint8_t> s_flags;                      // 2 per seed
+    uint64_t seed_bytes = 0;
+};
+static int ext_check_params(int kind, Gaps gaps, SizeRange size, int32_t x_drop, uint32_t mode) {   // ba_extend_batch_create's own arguments
+    if (kind == BA_KIND_PROFILE_) return fail("extension batches take a sequence matrix: profile batches cannot be extended");
+    if (kind < 0 || kind > 2) return fail("unknown matrix kind %d", kind);
+    if (!(mode & BA_X_DROP)) return fail("extension batches need BA_X_DROP: a side ends where its score drops");
+    if (mode & (BA_LOCAL_START | BA_FREE_QUERY_START_GAPS | BA_FREE_QUERY_END_GAPS))
+        return fail("extension batches take BA_X_DROP, BA_TRACE and BA_CIGAR_EQ only: LOCAL_START and FREE_QUERY_* are rejected");
+    const size_t min_size = size.min < 16 ? 16 : size.min, max_size = size.max < 16 ? 16 : size.max;   // (as batch_build)
+    std::string why;
+    if (check_align_params(false, gaps, min_size, max_size, x_drop, mode, &why)) return fail("%s", why.c_str());
+    if (min_size > max_size) return fail("min block size exceeds max block size");
+    return 0;
+}
+// Check a seed set (the mode and the matrix kind are checked already) and cut it into sides.
+static int ext_plan(int kind, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len,
+                    const uint32_t* q_seed, const uint32_t* r_seed, const uint32_t* seed_len, const uint8_t* strand, size_t n, ExtSet& S) {
+    if (!pool || !q_off || !q_len || !r_off || !r_len || !q_seed || !r_seed || !seed_len) return fail("null argument");
+    if (n == 0 || n > (1u << 28)) return fail("an extension batch must hold between 1 and 2^28 seeds");   // (k_pack_images: two workgroups per side)
+    S = ExtSet();
+    S.side.resize(2 * n); S.s_raw_q.resize(n); S.s_raw_r.resize(n); S.s_img_q.resize(n); S.s_img_r.resize(n); S.s_flags.resize(2 * n);
+    const uint8_t* hi = nullptr;
+    for (size_t p = 0; p < n; p++) {
+        const uint64_t Q = q_len[p], R = r_len[p], s = q_seed[p], t = r_seed[p], L = seed_len[p];
+        if (L == 0) return fail("seed %zu: seed_len must be at least 1", p);
+        if (s + L > Q || t + L > R)
+            return fail("seed %zu: the seed (query %llu + %llu, reference %llu + %llu) runs past the end of its sequences (%llu, %llu)", p,
+                        (unsigned long long)s, (unsigned long long)L, (unsigned long long)t, (unsigned long long)L, (unsigned long long)Q, (unsigned long long)R);
+        const uint8_t st = strand ? strand[p] : 0;
+        if (st > 1) return fail("seed %zu: strand must be 0 or 1", p);
+        if (st && kind != BA_KIND_NUC) return fail("seed %zu: strand needs a NucMatrix batch (reverse complement is nucleotide-only)", p);
+        const uint8_t* q = pool + q_off[p]; const uint8_t* r = pool + r_off[p];
+        for (const uint8_t* x : {q, r}) if (!S.lo || x < S.lo) S.lo = x;
+        if (!hi || q + Q > hi) hi = q + Q;
+        if (r + R > hi) hi = r + R;
+        auto add_side = [&](int w, const uint8_t* qs, uint64_t ql, uint8_t qf, const uint8_t* rs, uint64_t rl, uint8_t rf) {
+            if (!ql || !rl) { S.side[2 * p + w] = ba::EXT_NO_SIDE; return; }
+            S.side[2 * p + w] = (uint32_t)S.seed_of.size();
+            S.seed_of.push_back((uint32_t)p);
+            S.src.push_back(qs); S.len.push_back((uint32_t)ql); S.flags.push_back(qf);
+            S.src.push_back(rs); S.len.push_back((uint32_t)rl); S.flags.push_back(rf);
+        };
+        // (minus strand: q is the reverse complement of the caller's bytes; the seed's frame is that of q)
+        if (st) add_side(0, q + (Q - s), s, ba::IMG_COMPLEMENT, r, t, ba::IMG_REVERSE);
+        else add_side(0, q, s, ba::IMG_REVERSE, r, t, ba::IMG_REVERSE);
+        if (st) add_side(1, q, Q - s - L, ba::IMG_REVERSE | ba::IMG_COMPLEMENT, r + t + L, R - t - L, 0);
+        else add_side(1, q + s + L, Q - s - L, 0, r + t + L, R - t - L, 0);
+        S.s_raw_q[p] = (uint64_t)((st ? q + (Q - s - L) : q + s) - pool); S.s_raw_r[p] = (uint64_t)(r + t - pool);   // (made relative to lo below)
+        S.s_flags[2 * p] = st ? (ba::IMG_REVERSE | ba::IMG_COMPLEMENT) : 0; S.s_flags[2 * p + 1] = 0;
+        S.s_img_q[p] = S.seed_bytes; S.seed_bytes += (1 + L + 3) & ~(uint64_t)3;
+        S.s_img_r[p] = S.seed_bytes; S.seed_bytes += (1 + L + 3) & ~(uint64_t)3;
+    }
+    const uint64_t base = (uint64_t)(S.lo - pool);
+    for (size_t p = 0; p < n; p++) { S.s_raw_q[p] -= base; S.s_raw_r[p] -= base; }
+    S.bytes = (uint64_t)(hi - S.lo);
+    if (S.seed_of.size() > 0x7fffffffu) return fail("too many sides");
+    return 0;
+}
+struct BaExtendBatch {
+    int device = 0, kind = 0; uint32_t mode = 0;
+    std::unique_ptr<BaBatch> inner;   // the sides of the loaded set; null if the batch was created with none (nothing to fill)
+    uint32_t n = 0, n_sides = 0;
+    uint64_t cap_n = 0, cap_raw = 0, cap_seed = 0, runs_cap = 0, total_runs = 0;
+    hipStream_t stream = nullptr; hipEvent_t ev[4] = {};
+    DevBuf raw, seed_pool, seed_q, seed_r, seed_raw_q, seed_raw_r, seed_flags, seed_len, q_seed, r_seed, side, matrix, err;
+    DevBuf score, left_score, right_score, q_start, r_start, q_end, r_end, cells, status, cigar_len, join, out_off, runs;
+    float fill_ms = 0, pack_ms = 0, splice_ms = 0;
+    bool ran = false;
+    ba::ExtendParams params() const {
+        ba::ExtendParams ep{};
+        ep.n = n; ep.kind = seq_kind(kind); ep.flags = mode; ep.matrix = matrix.as<int8_t>();
+        ep.q_seed = q_seed.as<uint32_t>(); ep.r_seed = r_seed.as<uint32_t>(); ep.seed_len = seed_len.as<uint32_t>();
+        ep.seed_pool = seed_pool.as<uint8_t>(); ep.seed_q = seed_q.as<uint64_t>(); ep.seed_r = seed_r.as<uint64_t>(); ep.side = side.as<uint32_t>();
+        if (inner) {
+            const BaBatch* b = inner.get();
+            ep.in_score = b->score.as<int32_t>(); ep.in_qidx = b->qidx.as<uint32_t>(); ep.in_ridx = b->ridx.as<uint32_t>();
+            ep.in_cells = b->cells.as<unsigned long long>(); ep.in_status = b->status.as<uint32_t>(); ep.in_cig_len = b->cig_len.as<uint32_t>();
+            ep.in_cig_off = b->cig_off.as<uint64_t>(); ep.in_cig_ops = b->cig_ops.as<uint32_t>();
+        }
+        ep.score = score.as<int32_t>(); ep.left_score = left_score.as<int32_t>(); ep.right_score = right_score.as<int32_t>();
+        ep.q_start = q_start.as<uint32_t>(); ep.r_start = r_start.as<uint32_t>(); ep.q_end = q_end.as<uint32_t>(); ep.r_end = r_end.as<uint32_t>();
+        ep.cells = cells.as<unsigned long long>(); ep.status = status.as<uint32_t>(); ep.cigar_len = cigar_len.as<uint32_t>();
+        ep.join = join.as<uint32_t>(); ep.out_off = out_off.as<uint64_t>(); ep.runs = runs.as<uint32_t>();
+        return ep;
+    }
+    ~BaExtendBatch() {
+        inner.reset();
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+// Load a planned set into the batch: the caller's bytes once to the device, the sides into the inner batch (built on create, reloaded
+// after), the seeds' own images. `create`: size every buffer for this set; otherwise the set must fit them.
+static int ext_load(BaExtendBatch* e, const ExtSet& S, size_t n, const void* matrix, Gaps gaps, SizeRange size, int32_t x_drop,
+                    const uint32_t* q_seed, const uint32_t* r_seed, const uint32_t* seed_len, bool create) {
+    const size_t n_sides = S.seed_of.size();
+    if (create) {
+        e->cap_n = n; e->cap_raw = S.bytes; e->cap_seed = S.seed_bytes;
+        if (e->raw.alloc(S.bytes) || e->seed_pool.alloc(S.seed_bytes + 64) || e->err.alloc(8)) return 1;
+        DevBuf* per_seed4[] = {&e->seed_len, &e->q_seed, &e->r_seed, &e->score, &e->left_score, &e->right_score, &e->q_start, &e->r_start,
+                               &e->q_end, &e->r_end, &e->status, &e->cigar_len, &e->join};
+        for (DevBuf* d : per_seed4) if (d->alloc(n * 4)) return 1;
+        if (e->seed_q.alloc(n * 8) || e->seed_r.alloc(n * 8) || e->seed_raw_q.alloc(n * 8) || e->seed_raw_r.alloc(n * 8) || e->seed_flags.alloc(2 * n) ||
+            e->side.alloc(2 * n * 4) || e->cells.alloc(n * 8) || e->out_off.alloc((n + 1) * 8) || e->matrix.alloc(1024)) return 1;
+        int8_t tmp[1024] = {0};
+        if (e->kind == BA_KIND_BYTES) { const ByteMatrix* bm = (const ByteMatrix*)matrix; tmp[0] = bm->match_score; tmp[1] = bm->mismatch_score; }
+        else memcpy(tmp, matrix, e->kind == BA_KIND_AA ? 27 * 32 : 8 * 16);
+        HIP_TRY(hipMemcpy(e->matrix.p, tmp, 1024, hipMemcpyHostToDevice));
+    } else {
+        if (n > e->cap_n) return fail("reload: %zu seeds exceed the batch's capacity of %llu", n, (unsigned long long)e->cap_n);
+        if (S.bytes > e->cap_raw) return fail("reload: %llu sequence bytes exceed the batch's capacity of %llu", (unsigned long long)S.bytes, (unsigned long long)e->cap_raw);
+        if (S.seed_bytes > e->cap_seed) return fail("reload: the seeds (%llu image bytes) exceed the batch's capacity of %llu", (unsigned long long)S.seed_bytes, (unsigned long long)e->cap_seed);
+        if (n_sides && !e->inner) return fail("reload: the set has sides to align, and the batch was created with none");
+    }
+    e->n = 0; e->ran = false; e->pack_ms = 0;   // (a failure from here on leaves no seeds loaded)
+    HIP_TRY(hipMemcpy(e->raw.p, S.lo, S.bytes, hipMemcpyHostToDevice));
+    ExtImages X;
+    X.host_base = S.lo; X.dev_base = e->raw.as<uint8_t>(); X.flags = S.flags.data(); X.seed_of = S.seed_of.data(); X.pack_ms = &e->pack_ms;
+    auto get = [&](size_t p, int w, const uint8_t** ptr, size_t* len) { *ptr = S.src[2 * p + w]; *len = S.len[2 * p + w]; };
+    if (n_sides) {
+        if (create) {
+            e->inner.reset(batch_build(e->kind, matrix, gaps, size, x_drop, e->mode, n_sides, false, get, NoProfiles(), &X));
+            if (!e->inner) return 1;
+        } else if (batch_reload(e->inner.get(), n_sides, false, get, NoProfiles(), &X)) return 1;
+    }
+    // sides -> their positions in the inner batch's device order
+    std::vector<uint32_t> side(S.side);
+    if (n_sides && !e->inner->h_order.empty()) {
+        std::vector<uint32_t> pos(n_sides);
+        for (uint32_t d = 0; d < n_sides; d++) pos[e->inner->h_order[d]] = d;
+        for (uint32_t& x : side) if (x != ba::EXT_NO_SIDE) x = pos[x];
+    }
+    HIP_TRY(hipMemcpy(e->side.p, side.data(), 2 * n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->q_seed.p, q_seed, n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->r_seed.p, r_seed, n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->seed_len.p, seed_len, n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->seed_q.p, S.s_img_q.data(), n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->seed_r.p, S.s_img_r.data(), n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->seed_raw_q.p, S.s_raw_q.data(), n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->seed_raw_r.p, S.s_raw_r.data(), n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->seed_flags.p, S.s_flags.data(), 2 * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(e->cigar_len.p, 0, n * 4));
+    HIP_TRY(hipMemset(e->err.p, 0xff, 8));
+    HIP_TRY(hipEventRecord(e->ev[0], e->stream));
+    HIP_TRY(ba_launch_pack_images(e->stream, seq_kind(e->kind), e->raw.as<uint8_t>(), e->seed_raw_q.as<uint64_t>(), e->seed_raw_r.as<uint64_t>(),
+                                  e->seed_flags.as<uint8_t>(), e->seed_q.as<uint64_t>(), e->seed_len.as<uint32_t>(), e->seed_r.as<uint64_t>(),
+                                  e->seed_len.as<uint32_t>(), e->seed_pool.as<uint8_t>(), 0, (uint32_t)n, e->err.as<unsigned long long>()));
+    HIP_TRY(hipEventRecord(e->ev[1], e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, e->ev[0], e->ev[1]));
+    e->pack_ms += ms;
+    unsigned long long err = 0;
+    HIP_TRY(hipMemcpy(&err, e->err.p, 8, hipMemcpyDeviceToHost));
+    if (err != ~0ull) return fail("seed %llu: byte 0x%02x is outside the matrix alphabet", err >> 8, (unsigned)(err & 0xff));
+    e->n = (uint32_t)n; e->n_sides = (uint32_t)n_sides;
+    return 0;
+}
+
 // ------------------------------------------------------------------ C ABI, Part 2
 extern "C" {
 
@@ -1627,6 +1847,91 @@ int ba_batch_kernel(BaBatch* b) { return !b ? -1 : (b->small ? 3 : (b->quad ? 2 
 int ba_batch_geometry(BaBatch* b) { return !b ? -1 : (int)b->geom; }
 int ba_batch_retried(BaBatch* b) { return b ? (int)b->retried : -1; }
 void ba_batch_destroy(BaBatch* b) { delete b; }
+
+BaExtendBatch* ba_extend_batch_create(int kind, const void* matrix, Gaps gaps, SizeRange size, int32_t x_drop, uint32_t mode, const uint8_t* pool,
+                                      const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len,
+                                      const uint32_t* q_seed, const uint32_t* r_seed, const uint32_t* seed_len, const uint8_t* strand, uintptr_t n_seeds) {
+    ExtSet S;   // every argument is checked before the device is touched
+    if (!matrix) { fail("null argument"); return nullptr; }
+    if (ext_check_params(kind, gaps, size, x_drop, mode) || ext_plan(kind, pool, q_off, q_len, r_off, r_len, q_seed, r_seed, seed_len, strand, n_seeds, S)) return nullptr;
+    if (ensure_device()) return nullptr;
+    std::unique_ptr<BaExtendBatch> e(new BaExtendBatch);
+    e->device = g_device; e->kind = kind; e->mode = mode;
+    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { fail("hipStreamCreate failed"); return nullptr; }
+    for (hipEvent_t& ev : e->ev) if (hipEventCreate(&ev) != hipSuccess) { fail("hipEventCreate failed"); return nullptr; }
+    if (ext_load(e.get(), S, n_seeds, matrix, gaps, size, x_drop, q_seed, r_seed, seed_len, true)) return nullptr;
+    return e.release();
+}
+int ba_extend_batch_reload(BaExtendBatch* e, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len,
+                           const uint32_t* q_seed, const uint32_t* r_seed, const uint32_t* seed_len, const uint8_t* strand, uintptr_t n_seeds) {
+    if (!e) return fail("null batch");
+    ExtSet S;
+    if (ext_plan(e->kind, pool, q_off, q_len, r_off, r_len, q_seed, r_seed, seed_len, strand, n_seeds, S)) return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    return ext_load(e, S, n_seeds, nullptr, Gaps{0, 0}, SizeRange{0, 0}, 0, q_seed, r_seed, seed_len, false);   // (matrix, gaps, range: the batch's own)
+}
+int ba_extend_batch_run(BaExtendBatch* e, float* kernel_ms) {
+    if (!e) return fail("null batch");
+    if (!e->n) return fail("no seeds loaded (the last reload failed)");
+    HIP_TRY(hipSetDevice(e->device));
+    e->ran = false; e->fill_ms = 0; e->splice_ms = 0; e->total_runs = 0;
+    if (e->n_sides && batch_run(e->inner.get(), &e->fill_ms)) return 1;   // (re-runs included: the splice reads final results only)
+    ba::ExtendParams ep = e->params();
+    HIP_TRY(hipEventRecord(e->ev[0], e->stream));
+    HIP_TRY(ba_launch_extend_results(e->stream, &ep));
+    HIP_TRY(hipEventRecord(e->ev[1], e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipEventElapsedTime(&e->splice_ms, e->ev[0], e->ev[1]));
+    if (e->mode & BA_TRACE) {
+        uint64_t total = 0;
+        HIP_TRY(hipMemcpy(&total, e->out_off.as<uint64_t>() + e->n, 8, hipMemcpyDeviceToHost));
+        if (total > e->runs_cap) {
+            if (e->runs.alloc(total * 4)) return 1;
+            e->runs_cap = total;
+        }
+        ep.runs = e->runs.as<uint32_t>();
+        HIP_TRY(hipEventRecord(e->ev[2], e->stream));
+        HIP_TRY(ba_launch_extend_gather(e->stream, &ep));
+        HIP_TRY(hipEventRecord(e->ev[3], e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, e->ev[2], e->ev[3]));
+        e->splice_ms += ms;
+        e->total_runs = total;
+    }
+    e->ran = true;
+    if (kernel_ms) *kernel_ms = e->fill_ms;
+    return 0;
+}
+int ba_extend_batch_results(BaExtendBatch* e, int32_t* score, uint32_t* q_start, uint32_t* r_start, uint32_t* q_end, uint32_t* r_end,
+                            int32_t* left_score, int32_t* right_score, uint64_t* cells, uint32_t* cigar_len, uint32_t* status) {
+    if (!e) return fail("null batch");
+    if (!e->ran) return fail("ba_extend_batch_run has not been called");
+    HIP_TRY(hipSetDevice(e->device));
+    if (d2h(e->score, score, e->n) || d2h(e->q_start, q_start, e->n) || d2h(e->r_start, r_start, e->n) || d2h(e->q_end, q_end, e->n) ||
+        d2h(e->r_end, r_end, e->n) || d2h(e->left_score, left_score, e->n) || d2h(e->right_score, right_score, e->n) ||
+        d2h(e->cells, cells, e->n) || d2h(e->cigar_len, cigar_len, e->n) || d2h(e->status, status, e->n)) return 1;
+    return 0;
+}
+int ba_extend_batch_cigars(BaExtendBatch* e, uint32_t* runs, uint64_t capacity) {
+    if (!e) return fail("null batch");
+    if (!(e->mode & BA_TRACE)) return fail("batch was created without BA_TRACE");
+    if (!e->ran) return fail("ba_extend_batch_run has not been called");
+    if (e->total_runs > capacity) return fail("cigar buffer too small: need %llu entries", (unsigned long long)e->total_runs);
+    if (!e->total_runs) return 0;
+    if (!runs) return fail("null argument");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMemcpy(runs, e->runs.p, e->total_runs * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+int ba_extend_batch_times(BaExtendBatch* e, float* fill_ms, float* pack_ms, float* splice_ms) {
+    if (!e) return fail("null batch");
+    if (fill_ms) *fill_ms = e->fill_ms;
+    if (pack_ms) *pack_ms = e->pack_ms;
+    if (splice_ms) *splice_ms = e->splice_ms;
+    return 0;
+}
+void ba_extend_batch_destroy(BaExtendBatch* e) { delete e; }
 
 int block_batch_align(int kind, const void* matrix, Gaps gaps, SizeRange size, int32_t x_drop, uint32_t mode, const uint8_t* pool,
                       const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len, uintptr_t n,

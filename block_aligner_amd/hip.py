@@ -152,6 +152,14 @@ def lib() -> C.CDLL:
         L.ba_multibatch_kernel_ms.argtypes = [vp, vp, C.c_int]
         L.ba_multibatch_destroy.argtypes = [vp]
         L.ba_shard_slices.argtypes = [vp, vp, sz, C.c_int, vp]
+        L.ba_extend_batch_create.restype = vp
+        L.ba_extend_batch_create.argtypes = [C.c_int, vp, GapsC, SizeRangeC, i32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz]
+        L.ba_extend_batch_reload.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz]
+        L.ba_extend_batch_run.argtypes = [vp, C.POINTER(C.c_float)]
+        L.ba_extend_batch_results.argtypes = [vp] + [vp] * 10
+        L.ba_extend_batch_cigars.argtypes = [vp, vp, C.c_uint64]
+        L.ba_extend_batch_times.argtypes = [vp, vp, vp, vp]
+        L.ba_extend_batch_destroy.argtypes = [vp]
         _lib = L
         _loaded[LIB_PATH] = L
     return _lib
@@ -659,6 +667,87 @@ class ProfileBatchAligner(BatchAligner):
         self._h = L.ba_batch_create_profile(arr, _size(size), x_drop, mode, pool.ctypes.data, q_off.ctypes.data, q_len.ctypes.data, self.n)
         if not self._h:
             raise RuntimeError(last_error())
+
+
+class ExtendBatchAligner:
+    """Seed-and-extend batch (ba_extend_batch_*): per seed p, X-drop extension leftwards from q[q_seed[p]] / r[r_seed[p]] (reversed prefixes)
+    and rightwards from the seed's end, spliced with the seed into one result. q = pool[q_off[p]:+q_len[p]], r = pool[r_off[p]:+r_len[p]];
+    strand (NucMatrix only; None = all 0): 1 aligns the reverse complement of q, and the seed coordinates and results are in that frame.
+    mode must hold X_DROP; TRACE and CIGAR_EQ are optional. Arguments are checked before the device is touched."""
+
+    RESULTS = (("score", np.int32), ("q_start", np.uint32), ("r_start", np.uint32), ("q_end", np.uint32), ("r_end", np.uint32),
+               ("left_score", np.int32), ("right_score", np.int32), ("cells", np.uint64), ("cigar_len", np.uint32), ("status", np.uint32))
+
+    @staticmethod
+    def _arrays(pool, q_off, q_len, r_off, r_len, q_seed, r_seed, seed_len, strand):
+        a = (np.ascontiguousarray(pool, dtype=np.uint8), np.ascontiguousarray(q_off, dtype=np.uint64), np.ascontiguousarray(q_len, dtype=np.uint32),
+             np.ascontiguousarray(r_off, dtype=np.uint64), np.ascontiguousarray(r_len, dtype=np.uint32), np.ascontiguousarray(q_seed, dtype=np.uint32),
+             np.ascontiguousarray(r_seed, dtype=np.uint32), np.ascontiguousarray(seed_len, dtype=np.uint32),
+             None if strand is None else np.ascontiguousarray(strand, dtype=np.uint8))
+        n = len(a[2])
+        if any(len(x) != n for x in a[1:] if x is not None):
+            raise ValueError("q_off, q_len, r_off, r_len, q_seed, r_seed, seed_len and strand must have one entry per seed")
+        return a
+
+    @staticmethod
+    def _ptrs(a):
+        return [x.ctypes.data if x is not None else None for x in a]
+
+    def __init__(self, matrix, gaps, size, x_drop: int, mode: int, pool, q_off, q_len, r_off, r_len, q_seed, r_seed, seed_len, strand=None):
+        L = lib()
+        a = self._arrays(pool, q_off, q_len, r_off, r_len, q_seed, r_seed, seed_len, strand)
+        self.n = len(a[2])
+        self.mode = mode
+        raw = matrix.raw()
+        g = GapsC(gaps.open, gaps.extend) if isinstance(gaps, S.Gaps) else GapsC(gaps[0], gaps[1])
+        self._h = L.ba_extend_batch_create(matrix.KIND, raw.ctypes.data, g, _size(size), x_drop, mode, *self._ptrs(a), self.n)
+        if not self._h:
+            raise RuntimeError(last_error())
+
+    def reload(self, pool, q_off, q_len, r_off, r_len, q_seed, r_seed, seed_len, strand=None) -> None:
+        """Replace the seeds and keep the device buffers (ba_extend_batch_reload): the new set must fit the original one's sizes."""
+        a = self._arrays(pool, q_off, q_len, r_off, r_len, q_seed, r_seed, seed_len, strand)
+        if lib().ba_extend_batch_reload(self._h, *self._ptrs(a), len(a[2])):
+            raise RuntimeError(last_error())
+        self.n = len(a[2])
+
+    def run(self) -> float:
+        """Fill both sides of every seed, then splice; returns the fill kernel's HIP-event time in milliseconds."""
+        ms = C.c_float()
+        if lib().ba_extend_batch_run(self._h, C.byref(ms)):
+            raise RuntimeError(last_error())
+        return ms.value
+
+    def times(self):
+        """Device milliseconds: fill and splice of the last run(), image packers of the last create / reload."""
+        f, p, s = C.c_float(), C.c_float(), C.c_float()
+        if lib().ba_extend_batch_times(self._h, C.byref(f), C.byref(p), C.byref(s)):
+            raise RuntimeError(last_error())
+        return dict(fill_ms=f.value, pack_ms=p.value, splice_ms=s.value)
+
+    def results(self):
+        out = {k: np.zeros(self.n, t) for k, t in self.RESULTS}
+        if lib().ba_extend_batch_results(self._h, *(out[k].ctypes.data for k, _ in self.RESULTS)):
+            raise RuntimeError(last_error())
+        return out
+
+    def cigars(self, cigar_len=None):
+        """-> (runs, offsets): runs[offsets[p]:offsets[p+1]] are seed p's packed (len << 4 | op) runs."""
+        if cigar_len is None:
+            cigar_len = self.results()["cigar_len"]
+        off = np.zeros(self.n + 1, np.uint64)
+        np.cumsum(cigar_len, out=off[1:])
+        runs = np.empty(int(off[-1]), np.uint32)
+        if lib().ba_extend_batch_cigars(self._h, runs.ctypes.data, runs.size):
+            raise RuntimeError(last_error())
+        return runs, off
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.ba_extend_batch_destroy(self._h)
+            self._h = None
+
+    __del__ = close
 
 
 def batch_align_exp(matrix, gaps, size, x_drop: int, target_score: int, mode: int, pool, q_off, q_len, r_off, r_len):

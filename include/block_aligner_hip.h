@@ -271,6 +271,43 @@ int ba_batch_spec_cells(BaBatch* batch, uint64_t* cells);
 int ba_batch_retried(BaBatch* batch);
 void ba_batch_destroy(BaBatch* batch);
 
+/* ---- seed-and-extend batches: X-drop extension on both sides of a seed, one result per seed ("Seed extension").
+ *
+ * Seed p lies at q[q_seed[p] .. + seed_len[p]) of its query q = pool[q_off[p] .. +q_len[p]) and r[r_seed[p] .. + seed_len[p]) of its reference
+ * r = pool[r_off[p] .. +r_len[p]); seed_len >= 1, and the seed lies inside both sequences. strand (NULL = all 0; NucMatrix batches only):
+ * strand[p] = 1 replaces q by its reverse complement (uppercased bytes, A <-> T, C <-> G, every other letter as it is) before anything else;
+ * seed coordinates and results are in that oriented frame. The seed is an ungapped anchor (it need not be an exact match): its score is the
+ * sum of matrix(q[q_seed + k], r[r_seed + k]). Left side: Block::<TRACE, true>::align of rev(q[0 .. q_seed)) against rev(r[0 .. r_seed)); right
+ * side: the same alignment of q[q_seed + seed_len ..] against r[r_seed + seed_len ..]; a side where either sequence is empty is not aligned
+ * (score 0, end (0, 0), no cells, no runs). All non-empty sides of a set are ONE ordinary batch on the device -- the images are cut out of the
+ * caller's bytes there, and the seeds and both sides are spliced there.
+ *
+ * Modes: BA_X_DROP is required, BA_TRACE and BA_CIGAR_EQ are optional; LOCAL_START and FREE_QUERY_* are rejected, and so are profile batches.
+ * Every argument is checked before the device is touched (a seed out of range, seed_len 0, strand on another matrix: a message naming the seed). */
+typedef struct BaExtendBatch BaExtendBatch;
+BaExtendBatch* ba_extend_batch_create(int kind, const void* matrix, struct Gaps gaps, struct SizeRange size, int32_t x_drop, uint32_t mode,
+                                      const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len,
+                                      const uint32_t* q_seed, const uint32_t* r_seed, const uint32_t* seed_len, const uint8_t* strand, uintptr_t n_seeds);
+/* Replace the seeds and keep the device buffers, as ba_batch_reload: the new set must fit what the batch was created with -- no more seeds,
+ * no more sequence bytes, and its sides no more than the original sides (in number, bytes and longest pair). */
+int ba_extend_batch_reload(BaExtendBatch* batch, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off,
+                           const uint32_t* r_len, const uint32_t* q_seed, const uint32_t* r_seed, const uint32_t* seed_len, const uint8_t* strand,
+                           uintptr_t n_seeds);
+/* Fill both sides of every seed (one launch, re-runs included), then splice. kernel_ms (optional) = HIP-event time of the fill, as ba_batch_run. */
+int ba_extend_batch_run(BaExtendBatch* batch, float* kernel_ms);
+/* Results per seed, in the caller's order; any pointer may be NULL. score = left_score + seed score + right_score; the alignment covers
+ * q[q_start .. q_end) and r[r_start .. r_end) (q_start = q_seed - the left side's query end, q_end = q_seed + seed_len + the right side's
+ * query end; likewise r); cells = both sides' cells; status = the OR of both sides' BA_ST_* bits; cigar_len = runs per seed (BA_TRACE). */
+int ba_extend_batch_results(BaExtendBatch* batch, int32_t* score, uint32_t* q_start, uint32_t* r_start, uint32_t* q_end, uint32_t* r_end,
+                            int32_t* left_score, int32_t* right_score, uint64_t* cells, uint32_t* cigar_len, uint32_t* status);
+/* BA_TRACE: every seed's runs, concatenated in seed order (as ba_batch_cigars): the left side's runs reversed, the seed as one M run (its =/X
+ * runs with BA_CIGAR_EQ), the right side's runs; adjacent runs with the same op merged at both joins. Rescored over q[q_start .. q_end) /
+ * r[r_start .. r_end), the runs give `score` exactly. */
+int ba_extend_batch_cigars(BaExtendBatch* batch, uint32_t* runs, uint64_t capacity);
+/* Device times in ms: the last run's fill (as kernel_ms) and splice; the image packers of the last create / reload. Any pointer may be NULL. */
+int ba_extend_batch_times(BaExtendBatch* batch, float* fill_ms, float* pack_ms, float* splice_ms);
+void ba_extend_batch_destroy(BaExtendBatch* batch);
+
 /* ---- every pair with its own block range. The reference's callers choose the range per pair -- percent_len(max(|q|, |r|), 0.01) ..=
  * percent_len(max(|q|, |r|), p) in /root/reference/examples/nanopore_bench_global.rs:144-171, Block::align(..., min..=max, x) in
  * src/scan_block.rs:847 --, while ba_batch_create takes one range for the whole batch. These calls bin the pairs by (min, max), align every bin as
