@@ -22,6 +22,7 @@
 #include "../../include/block_aligner_hip.h"
 #include "aa_matrices.inc"
 #include "ba_extend.h"
+#include "ba_stats.h"
 #include "ba_params.h"
 
 using ba::BatchParams;
@@ -56,6 +57,8 @@ extern "C" hipError_t ba_launch_pack_images(hipStream_t, int, const uint8_t*, co
                                             const uint64_t*, const uint32_t*, uint8_t*, uint32_t, uint32_t, unsigned long long*);
 extern "C" hipError_t ba_launch_extend_results(hipStream_t, const ba::ExtendParams*);
 extern "C" hipError_t ba_launch_extend_gather(hipStream_t, const ba::ExtendParams*);
+extern "C" hipError_t ba_launch_stats(hipStream_t, const ba::StatsParams*);
+extern "C" hipError_t ba_launch_stats_extend(hipStream_t, const ba::ExtendParams*, const ba::AlignStats*, ba::AlignStats*);
 
 typedef hipError_t (*LaunchFn)(int, int, unsigned, unsigned, hipStream_t, const BatchParams*);
 typedef hipError_t (*OccFn)(int, int, unsigned, int*);
@@ -338,6 +341,10 @@ struct BaBatch {
     // CIGAR runs gathered on the device right behind the alignment kernels (ba_batch_compact_cigars): the later ba_batch_cigars is then one
     // device-to-host copy -- no kernel that would have to wait for room beside another batch's persistent launch
     DevBuf compact, compact_off, compact_total, dev_of;
+    // per-alignment statistics (ba_batch_stats): the records and the device -> caller position map, allocated on the first call; the kernel's time
+    DevBuf stats, stats_pos;
+    hipEvent_t ev_s0 = nullptr, ev_s1 = nullptr;
+    float stats_ms = 0;
     uint64_t compact_cap = 0, compact_used_cap = 0; bool compacted = false; uint32_t* compact_host = nullptr;
     unsigned long long* h_total = nullptr;   // page-locked mailbox the gather writes its total to (read without a copy)
     bool handle_mode = false;   // the device state of one Block handle: one pair per launch, CIGARs only on request (k_traceback)
@@ -380,6 +387,8 @@ struct BaBatch {
         if (h_total) (void)hipHostFree(h_total);
         if (ev_l0) (void)hipEventDestroy(ev_l0);
         if (ev_m1) (void)hipEventDestroy(ev_m1);
+        if (ev_s0) (void)hipEventDestroy(ev_s0);
+        if (ev_s1) (void)hipEventDestroy(ev_s1);
         if (stream2) (void)hipStreamDestroy(stream2);
         if (stream) (void)hipStreamDestroy(stream);
     }
@@ -1537,6 +1546,7 @@ struct BaExtendBatch {
     hipStream_t stream = nullptr; hipEvent_t ev[4] = {};
     DevBuf raw, seed_pool, seed_q, seed_r, seed_raw_q, seed_raw_r, seed_flags, seed_len, q_seed, r_seed, side, matrix, err;
     DevBuf score, left_score, right_score, q_start, r_start, q_end, r_end, cells, status, cigar_len, join, out_off, runs;
+    DevBuf stats;   // per-seed statistics (ba_extend_batch_stats), allocated on the first call
     float fill_ms = 0, pack_ms = 0, splice_ms = 0;
     bool ran = false;
     ba::ExtendParams params() const {
@@ -1627,6 +1637,44 @@ static int ext_load(BaExtendBatch* e, const ExtSet& S, size_t n, const void* mat
     HIP_TRY(hipMemcpy(&err, e->err.p, 8, hipMemcpyDeviceToHost));
     if (err != ~0ull) return fail("seed %llu: byte 0x%02x is outside the matrix alphabet", err >> 8, (unsigned)(err & 0xff));
     e->n = (uint32_t)n; e->n_sides = (uint32_t)n_sides;
+    return 0;
+}
+
+// ------------------------------------------------------------------ per-alignment statistics (ba_*_stats)
+// k_stats (ba_stats.hip) over a traced batch after its run: one record per pair into b->stats (allocated on the first call, freed with the
+// batch), at the pair's caller-order position or -- the sides of an extension batch -- at its device position. The runs it reads are the
+// final ones (re-runs are merged into the batch's arrays by ba_batch_wait).
+static_assert(sizeof(BaAlignStats) == sizeof(ba::AlignStats) && offsetof(BaAlignStats, matches) == offsetof(ba::AlignStats, matches) &&
+              offsetof(BaAlignStats, gap_opens) == offsetof(ba::AlignStats, gap_opens) && offsetof(BaAlignStats, path_score) == offsetof(ba::AlignStats, path_score),
+              "BaAlignStats and ba::AlignStats differ");
+static int batch_stats_device(BaBatch* b, bool caller_order) {
+    if (!(b->mode & BA_TRACE)) return fail("stats: the batch was created without BA_TRACE (the statistics are computed from the CIGAR runs)");
+    if (b->kind == BA_KIND_PROFILE_) return fail("stats: a profile batch has no reference bytes to compare with");
+    if (b->in_flight) return fail("stats: the batch has a launch in flight (ba_batch_wait first)");
+    if (!b->ran) return fail("stats: the batch has not finished a run (ba_batch_run, or ba_batch_launch and ba_batch_wait)");
+    HIP_TRY(hipSetDevice(b->device));
+    if (!b->stats.p && b->stats.alloc((size_t)b->cap_n * sizeof(ba::AlignStats))) return 1;
+    const bool map = caller_order && !b->h_order.empty();
+    if (map) {
+        if (!b->stats_pos.p && b->stats_pos.alloc((size_t)b->cap_n * 4)) return 1;
+        HIP_TRY(hipMemcpy(b->stats_pos.p, b->h_order.data(), (size_t)b->n * 4, hipMemcpyHostToDevice));
+    }
+    if (!b->ev_s0) HIP_TRY(hipEventCreate(&b->ev_s0));
+    if (!b->ev_s1) HIP_TRY(hipEventCreate(&b->ev_s1));
+    ba::StatsParams sp{};
+    sp.n = b->n; sp.kind = seq_kind(b->kind); sp.gap_open = b->gap_open; sp.gap_extend = b->gap_extend;
+    sp.matrix = b->matrix.as<int8_t>(); sp.matrix_bytes = (uint32_t)b->matrix.bytes;
+    sp.pool = b->pool.as<uint8_t>(); sp.q_off = b->q_off.as<uint64_t>(); sp.q_len = b->q_len.as<uint32_t>();
+    sp.r_off = b->r_off.as<uint64_t>(); sp.r_len = b->r_len.as<uint32_t>();
+    sp.qidx = b->qidx.as<uint32_t>(); sp.ridx = b->ridx.as<uint32_t>(); sp.status = b->status.as<uint32_t>();
+    sp.cig_len = b->cig_len.as<uint32_t>(); sp.cig_off = b->cig_off.as<uint64_t>(); sp.cig_ops = b->cig_ops.as<uint32_t>();
+    sp.out_pos = map ? b->stats_pos.as<uint32_t>() : nullptr;
+    sp.out = b->stats.as<ba::AlignStats>();
+    HIP_TRY(hipEventRecord(b->ev_s0, b->stream));
+    HIP_TRY(ba_launch_stats(b->stream, &sp));
+    HIP_TRY(hipEventRecord(b->ev_s1, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipEventElapsedTime(&b->stats_ms, b->ev_s0, b->ev_s1));
     return 0;
 }
 
@@ -1846,6 +1894,18 @@ int ba_batch_spec_cells(BaBatch* b, uint64_t* cells) {
 int ba_batch_kernel(BaBatch* b) { return !b ? -1 : (b->small ? 3 : (b->quad ? 2 : (b->multi ? 1 : 0))); }
 int ba_batch_geometry(BaBatch* b) { return !b ? -1 : (int)b->geom; }
 int ba_batch_retried(BaBatch* b) { return b ? (int)b->retried : -1; }
+int ba_batch_stats(BaBatch* b, BaAlignStats* out) {
+    if (!b) return fail("null batch");
+    if (!out) return fail("null argument");
+    if (batch_stats_device(b, true)) return 1;
+    HIP_TRY(hipMemcpy(out, b->stats.p, (size_t)b->n * sizeof(ba::AlignStats), hipMemcpyDeviceToHost));
+    return 0;
+}
+int ba_batch_stats_ms(BaBatch* b, float* ms) {
+    if (!b || !ms) return fail("null argument");
+    *ms = b->stats_ms;
+    return 0;
+}
 void ba_batch_destroy(BaBatch* b) { delete b; }
 
 BaExtendBatch* ba_extend_batch_create(int kind, const void* matrix, Gaps gaps, SizeRange size, int32_t x_drop, uint32_t mode, const uint8_t* pool,
@@ -1929,6 +1989,20 @@ int ba_extend_batch_times(BaExtendBatch* e, float* fill_ms, float* pack_ms, floa
     if (fill_ms) *fill_ms = e->fill_ms;
     if (pack_ms) *pack_ms = e->pack_ms;
     if (splice_ms) *splice_ms = e->splice_ms;
+    return 0;
+}
+int ba_extend_batch_stats(BaExtendBatch* e, BaAlignStats* out) {
+    if (!e) return fail("null batch");
+    if (!out) return fail("null argument");
+    if (!(e->mode & BA_TRACE)) return fail("stats: the batch was created without BA_TRACE (the statistics are computed from the CIGAR runs)");
+    if (!e->ran) return fail("stats: the batch has not finished a run (ba_extend_batch_run)");
+    HIP_TRY(hipSetDevice(e->device));
+    if (e->n_sides && batch_stats_device(e->inner.get(), false)) return 1;   // the sides' records, in the inner batch's device order
+    if (!e->stats.p && e->stats.alloc((size_t)e->cap_n * sizeof(ba::AlignStats))) return 1;
+    const ba::ExtendParams ep = e->params();
+    HIP_TRY(ba_launch_stats_extend(e->stream, &ep, e->n_sides ? e->inner->stats.as<ba::AlignStats>() : nullptr, e->stats.as<ba::AlignStats>()));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(out, e->stats.p, (size_t)e->n * sizeof(ba::AlignStats), hipMemcpyDeviceToHost));
     return 0;
 }
 void ba_extend_batch_destroy(BaExtendBatch* e) { delete e; }
@@ -2414,6 +2488,27 @@ int ba_sized_batch_classes(BaSizedBatch* m, SizeRange* ranges, uint64_t* counts,
     return (int)m->part.size();
 }
 void ba_sized_batch_destroy(BaSizedBatch* m) { delete m; }
+
+// per-alignment statistics of the two batch forms over ordinary batches: per bin / per slice, in the caller's order
+int ba_sized_batch_stats(BaSizedBatch* m, BaAlignStats* out) {
+    if (!m) return fail("null batch");
+    if (!out) return fail("null argument");
+    std::vector<BaAlignStats> tmp;
+    for (size_t k = 0; k < m->part.size(); k++) {
+        const auto& ix = m->idx[k];
+        tmp.resize(ix.size());
+        if (ba_batch_stats(m->part[k].get(), tmp.data())) return 1;
+        for (size_t i = 0; i < ix.size(); i++) out[ix[i]] = tmp[i];
+    }
+    return 0;
+}
+int ba_multibatch_stats(BaMultiBatch* m, BaAlignStats* out) {
+    if (!m) return fail("null batch");
+    if (!out) return fail("null argument");
+    for (size_t k = 0; k < m->part.size(); k++)
+        if (m->part[k] && ba_batch_stats(m->part[k].get(), out + m->bounds[k])) return 1;
+    return 0;
+}
 
 int ba_multibatch_kernel_ms(BaMultiBatch* m, float* ms, int capacity) {   // per slice, of the last run; returns the number of slices
     if (!m) return -1;

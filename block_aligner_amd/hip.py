@@ -42,6 +42,31 @@ class OpLenC(C.Structure):
     _fields_ = [("op", C.c_uint8), ("len", C.c_size_t)]
 
 
+class AlignStatsC(C.Structure):
+    """struct BaAlignStats (include/block_aligner_hip.h): the per-alignment statistics of the ba_*_stats calls."""
+    _fields_ = [("q_start", C.c_uint32), ("r_start", C.c_uint32), ("columns", C.c_uint32), ("matches", C.c_uint32),
+                ("mismatches", C.c_uint32), ("positives", C.c_uint32), ("ins", C.c_uint32), ("del", C.c_uint32),
+                ("gap_opens", C.c_uint32), ("longest_ins", C.c_uint32), ("longest_del", C.c_uint32), ("path_score", C.c_int32)]
+
+
+STATS_DTYPE = np.dtype(AlignStatsC)
+if C.sizeof(AlignStatsC) != 48 or STATS_DTYPE.itemsize != 48:
+    raise ImportError(f"struct BaAlignStats must be 48 bytes, the binding declares {C.sizeof(AlignStatsC)}")
+
+
+def _stats(call, h, n):
+    """One ba_*_stats call -> dict of numpy arrays, one per BaAlignStats field, plus identity = matches / columns (0 where columns == 0)
+    and edit_distance = mismatches + ins + del (SAM NM)."""
+    rec = np.zeros(n, STATS_DTYPE)
+    if call(h, rec.ctypes.data):
+        raise RuntimeError(last_error())
+    out = {k: rec[k].copy() for k in STATS_DTYPE.names}
+    cols = out["columns"]
+    out["identity"] = np.divide(out["matches"], cols, out=np.zeros(n, np.float64), where=cols > 0)
+    out["edit_distance"] = out["mismatches"] + out["ins"] + out["del"]
+    return out
+
+
 @dataclass(frozen=True)
 class AlignResult:
     score: int
@@ -160,6 +185,9 @@ def lib() -> C.CDLL:
         L.ba_extend_batch_cigars.argtypes = [vp, vp, C.c_uint64]
         L.ba_extend_batch_times.argtypes = [vp, vp, vp, vp]
         L.ba_extend_batch_destroy.argtypes = [vp]
+        for f in ("ba_batch_stats", "ba_sized_batch_stats", "ba_multibatch_stats", "ba_extend_batch_stats"):
+            getattr(L, f).argtypes = [vp, vp]
+        L.ba_batch_stats_ms.argtypes = [vp, C.POINTER(C.c_float)]
         _lib = L
         _loaded[LIB_PATH] = L
     return _lib
@@ -490,6 +518,18 @@ class BatchAligner:
         """Pairs the last run re-ran with full-size trace slots (ba_batch_retried)."""
         return lib().ba_batch_retried(self._h)
 
+    def stats(self):
+        """TRACE batches after a run: per-alignment statistics in pair order (ba_batch_stats) -> dict of arrays: q_start, r_start, columns,
+        matches, mismatches, positives, ins, del, gap_opens, longest_ins, longest_del, path_score, identity, edit_distance."""
+        return _stats(lib().ba_batch_stats, self._h, self.n)
+
+    def stats_ms(self) -> float:
+        """HIP-event time of the last stats() kernel in milliseconds."""
+        ms = C.c_float()
+        if lib().ba_batch_stats_ms(self._h, C.byref(ms)):
+            raise RuntimeError(last_error())
+        return ms.value
+
     KERNELS = ("k_align", "k_multi", "k_quad", "k_small")
 
     def spec_cells(self) -> int:
@@ -564,6 +604,10 @@ class MultiBatchAligner:
             raise RuntimeError(last_error())
         return runs, off
 
+    def stats(self):
+        """Per-alignment statistics in the caller's pair order (ba_multibatch_stats): as BatchAligner.stats."""
+        return _stats(lib().ba_multibatch_stats, self._h, self.n)
+
     def kernel_ms(self):
         """Kernel time of every slice in the last run() (ms; HIP events on the slice's own stream)."""
         t = np.zeros(64, np.float32)
@@ -631,6 +675,10 @@ class SizedBatchAligner:
         if lib().ba_sized_batch_cigars(self._h, runs.ctypes.data, runs.size):
             raise RuntimeError(last_error())
         return runs, off
+
+    def stats(self):
+        """Per-alignment statistics in the caller's pair order (ba_sized_batch_stats): as BatchAligner.stats."""
+        return _stats(lib().ba_sized_batch_stats, self._h, self.n)
 
     def classes(self):
         """[(min, max, pairs, fill kernel, kernel ms of the last run)] per bin."""
@@ -741,6 +789,11 @@ class ExtendBatchAligner:
         if lib().ba_extend_batch_cigars(self._h, runs.ctypes.data, runs.size):
             raise RuntimeError(last_error())
         return runs, off
+
+    def stats(self):
+        """TRACE batches after run(): per-seed statistics over q[q_start:q_end] / r[r_start:r_end] of the oriented query
+        (ba_extend_batch_stats): as BatchAligner.stats."""
+        return _stats(lib().ba_extend_batch_stats, self._h, self.n)
 
     def close(self):
         if getattr(self, "_h", None) and _lib is not None:

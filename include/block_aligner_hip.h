@@ -352,6 +352,42 @@ void ba_multibatch_destroy(BaMultiBatch* batch);
 /* The slicing rule on its own (no device needed): bounds[0 .. parts] for contiguous slices of near-equal summed |q| + |r|. */
 int ba_shard_slices(const uint32_t* q_len, const uint32_t* r_len, uintptr_t n_pairs, int parts, uint64_t* bounds);
 
+/* ---- per-alignment statistics, computed on the device from the CIGAR runs and the sequence images the fill left there (INTEGRATION.md,
+ * "Alignment statistics"): what SAM (NM), BLAST tabular output (.m8) and parasail's *_stats report, and the start cell of the path.
+ *
+ * The batch must have been created with BA_TRACE and have finished a run (ba_batch_run, or ba_batch_launch + ba_batch_wait). Refused with a
+ * message (ba_last_error) and a nonzero return: an untraced batch, a profile batch (its reference side has no bytes), a batch with a launch in
+ * flight, a batch that never ran (or was reloaded since), a null argument.
+ *
+ * Match-type columns are M, = and X cells. "Equal" means equal image bytes, the rule of BA_CIGAR_EQ: for NucMatrix and AAMatrix batches the
+ * converted bytes (lowercase input compares as uppercase), for ByteMatrix batches the raw bytes -- so matches / mismatches are the = / X cells
+ * of the same batch run with BA_CIGAR_EQ. A pair without runs (X-drop stopped at once, an empty sequence) gets a record of zeros with
+ * q_start = query_idx and r_start = reference_idx; a pair whose status has an overflow, lost or watchdog bit gets a record of zeros.
+ * path_score equals the reported score in every mode but BA_FREE_QUERY_END_GAPS, whose reported score is the reference's (a vector lane of the
+ * block's maximum, which need not belong to the end cell: block_aligner_amd/verify.py). The output buffer on the device is allocated on the
+ * first call and freed by destroy. */
+struct BaAlignStats {            /* 48 bytes, all 32-bit */
+    uint32_t q_start, r_start;   /* first cell of the path: the end (query_idx / reference_idx) minus what the runs consume */
+    uint32_t columns;            /* alignment columns: M/=/X + I + D cells */
+    uint32_t matches;            /* match-type columns whose two image bytes are equal (exactly the cells BA_CIGAR_EQ calls '=') */
+    uint32_t mismatches;         /* the other match-type columns */
+    uint32_t positives;          /* match-type columns with matrix score > 0 (BLAST "positives", parasail "similar") */
+    uint32_t ins, del;           /* I columns (query byte against a gap), D columns (reference byte against a gap) */
+    uint32_t gap_opens;          /* I runs + D runs */
+    uint32_t longest_ins, longest_del;
+    int32_t  path_score;         /* the runs rescored: matrix over match-type columns + open + (n - 1) extend per gap run */
+};
+/* n_pairs records, in the caller's pair order */
+int ba_batch_stats(BaBatch* batch, struct BaAlignStats* out);
+int ba_sized_batch_stats(BaSizedBatch* batch, struct BaAlignStats* out);
+int ba_multibatch_stats(BaMultiBatch* batch, struct BaAlignStats* out);
+/* One record per seed, over q[q_start .. q_end) / r[r_start .. r_end) of the oriented query: the left side's record + the seed's ungapped
+ * columns + the right side's record (counts add, the longest gaps are the larger; exact, since the joins only merge match-type runs);
+ * q_start / r_start are the extension's. A seed whose status has a failure bit gets a record of zeros. */
+int ba_extend_batch_stats(BaExtendBatch* batch, struct BaAlignStats* out);
+/* HIP-event time (ms) of the last ba_batch_stats kernel on this batch */
+int ba_batch_stats_ms(BaBatch* batch, float* ms);
+
 enum { BA_ST_TRACE_OVERFLOW = 1, BA_ST_BLOCKS_OVERFLOW = 2, BA_ST_CIGAR_OVERFLOW = 4, BA_ST_TRACEBACK_LOST = 8, BA_ST_WATCHDOG = 16,
        BA_ST_SLOT_TIMEOUT = 32 /* never reported since round 4 (a fill wave that waits for a trace slot walks pending tracebacks itself); kept for ABI stability */,
        BA_ST_MODE = 64 /* FREE_QUERY_END_GAPS reached a down step: the reference panics there */ };
