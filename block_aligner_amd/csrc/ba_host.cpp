@@ -23,6 +23,7 @@
 #include "aa_matrices.inc"
 #include "ba_extend.h"
 #include "ba_stats.h"
+#include "ba_text.h"
 #include "ba_params.h"
 
 using ba::BatchParams;
@@ -59,6 +60,8 @@ extern "C" hipError_t ba_launch_extend_results(hipStream_t, const ba::ExtendPara
 extern "C" hipError_t ba_launch_extend_gather(hipStream_t, const ba::ExtendParams*);
 extern "C" hipError_t ba_launch_stats(hipStream_t, const ba::StatsParams*);
 extern "C" hipError_t ba_launch_stats_extend(hipStream_t, const ba::ExtendParams*, const ba::AlignStats*, ba::AlignStats*);
+extern "C" hipError_t ba_launch_text_len(hipStream_t, const ba::TextParams*);
+extern "C" hipError_t ba_launch_text_write(hipStream_t, const ba::TextParams*);
 
 typedef hipError_t (*LaunchFn)(int, int, unsigned, unsigned, hipStream_t, const BatchParams*);
 typedef hipError_t (*OccFn)(int, int, unsigned, int*);
@@ -297,6 +300,19 @@ struct DevBuf {
     template <class T> T* as() const { return (T*)p; }
 };
 
+// Alignment strings (ba_*_text) of one batch: per-pair sizes in the caller's order, their offsets, the device -> caller position map and the
+// text, allocated on the first call (the text buffer grows, never shrinks) and freed with the batch. The sizes are kept for the run and the
+// format they were computed for: the second call of the two-call pattern only renders. ms: the kernels of the last call.
+struct TextState {
+    DevBuf len, off, pos, buf;
+    uint64_t buf_cap = 0, run = 0;
+    uint32_t what = ~0u;
+    bool sized = false;
+    hipEvent_t ev[2] = {};
+    float ms = 0;
+    ~TextState() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
 struct BaBatch {
     int device = 0;
     hipStream_t stream = nullptr, stream2 = nullptr;   // stream2: pair-slot small-block batches (see batch_launch)
@@ -345,6 +361,8 @@ struct BaBatch {
     DevBuf stats, stats_pos;
     hipEvent_t ev_s0 = nullptr, ev_s1 = nullptr;
     float stats_ms = 0;
+    TextState text;          // alignment strings (ba_batch_text)
+    uint64_t runs_done = 0;  // finished runs: what the text sizes are kept for
     uint64_t compact_cap = 0, compact_used_cap = 0; bool compacted = false; uint32_t* compact_host = nullptr;
     unsigned long long* h_total = nullptr;   // page-locked mailbox the gather writes its total to (read without a copy)
     bool handle_mode = false;   // the device state of one Block handle: one pair per launch, CIGARs only on request (k_traceback)
@@ -1450,6 +1468,7 @@ static int batch_wait(BaBatch* b, float* kernel_ms) {
         }
     }
     b->ran = true;
+    b->runs_done++;
     return 0;
 }
 static int batch_run(BaBatch* b, float* kernel_ms) {
@@ -1481,6 +1500,10 @@ struct ExtSet {   // a seed set cut into sides (host addresses into the caller's
     std::vector<uint64_t> s_raw_q, s_raw_r, s_img_q, s_img_r;   // the seeds' own images: source offsets in the upload, offsets in the seed pool
     std::vector<uint8_t> s_flags;                      // 2 per seed
     uint64_t seed_bytes = 0;
+    // per seed, the whole query and reference: source offsets in the upload, lengths, strand (ba_extend_batch_text renders from them)
+    std::vector<uint64_t> t_raw_q, t_raw_r;
+    std::vector<uint32_t> t_ql, t_rl;
+    std::vector<uint8_t> t_strand;
 };
 static int ext_check_params(int kind, Gaps gaps, SizeRange size, int32_t x_drop, uint32_t mode) {   // ba_extend_batch_create's own arguments
     if (kind == BA_KIND_PROFILE_) return fail("extension batches take a sequence matrix: profile batches cannot be extended");
@@ -1501,6 +1524,9 @@ static int ext_plan(int kind, const uint8_t* pool, const uint64_t* q_off, const 
     if (n == 0 || n > (1u << 28)) return fail("an extension batch must hold between 1 and 2^28 seeds");   // (k_pack_images: two workgroups per side)
     S = ExtSet();
     S.side.resize(2 * n); S.s_raw_q.resize(n); S.s_raw_r.resize(n); S.s_img_q.resize(n); S.s_img_r.resize(n); S.s_flags.resize(2 * n);
+    S.t_raw_q.resize(n); S.t_raw_r.resize(n); S.t_ql.assign(q_len, q_len + n); S.t_rl.assign(r_len, r_len + n);
+    S.t_strand.assign(n, 0);
+    if (strand) S.t_strand.assign(strand, strand + n);
     const uint8_t* hi = nullptr;
     for (size_t p = 0; p < n; p++) {
         const uint64_t Q = q_len[p], R = r_len[p], s = q_seed[p], t = r_seed[p], L = seed_len[p];
@@ -1531,9 +1557,10 @@ static int ext_plan(int kind, const uint8_t* pool, const uint64_t* q_off, const 
         S.s_flags[2 * p] = st ? (ba::IMG_REVERSE | ba::IMG_COMPLEMENT) : 0; S.s_flags[2 * p + 1] = 0;
         S.s_img_q[p] = S.seed_bytes; S.seed_bytes += (1 + L + 3) & ~(uint64_t)3;
         S.s_img_r[p] = S.seed_bytes; S.seed_bytes += (1 + L + 3) & ~(uint64_t)3;
+        S.t_raw_q[p] = q_off[p]; S.t_raw_r[p] = r_off[p];   // (made relative to lo below)
     }
     const uint64_t base = (uint64_t)(S.lo - pool);
-    for (size_t p = 0; p < n; p++) { S.s_raw_q[p] -= base; S.s_raw_r[p] -= base; }
+    for (size_t p = 0; p < n; p++) { S.s_raw_q[p] -= base; S.s_raw_r[p] -= base; S.t_raw_q[p] -= base; S.t_raw_r[p] -= base; }
     S.bytes = (uint64_t)(hi - S.lo);
     if (S.seed_of.size() > 0x7fffffffu) return fail("too many sides");
     return 0;
@@ -1547,6 +1574,15 @@ struct BaExtendBatch {
     DevBuf raw, seed_pool, seed_q, seed_r, seed_raw_q, seed_raw_r, seed_flags, seed_len, q_seed, r_seed, side, matrix, err;
     DevBuf score, left_score, right_score, q_start, r_start, q_end, r_end, cells, status, cigar_len, join, out_off, runs;
     DevBuf stats;   // per-seed statistics (ba_extend_batch_stats), allocated on the first call
+    // alignment strings (ba_extend_batch_text): the sequences' source offsets, lengths and strands of the loaded set (host copies, uploaded by
+    // the first text call after a load) and their device buffers, allocated on the first call
+    std::vector<uint64_t> h_t_raw_q, h_t_raw_r;
+    std::vector<uint32_t> h_t_ql, h_t_rl;
+    std::vector<uint8_t> h_t_strand;
+    bool t_uploaded = false;
+    DevBuf t_raw_q, t_raw_r, t_ql, t_rl, t_strand;
+    TextState text;
+    uint64_t runs_done = 0;
     float fill_ms = 0, pack_ms = 0, splice_ms = 0;
     bool ran = false;
     ba::ExtendParams params() const {
@@ -1637,6 +1673,8 @@ static int ext_load(BaExtendBatch* e, const ExtSet& S, size_t n, const void* mat
     HIP_TRY(hipMemcpy(&err, e->err.p, 8, hipMemcpyDeviceToHost));
     if (err != ~0ull) return fail("seed %llu: byte 0x%02x is outside the matrix alphabet", err >> 8, (unsigned)(err & 0xff));
     e->n = (uint32_t)n; e->n_sides = (uint32_t)n_sides;
+    e->h_t_raw_q = S.t_raw_q; e->h_t_raw_r = S.t_raw_r; e->h_t_ql = S.t_ql; e->h_t_rl = S.t_rl; e->h_t_strand = S.t_strand;
+    e->t_uploaded = false;
     return 0;
 }
 
@@ -1676,6 +1714,80 @@ static int batch_stats_device(BaBatch* b, bool caller_order) {
     HIP_TRY(hipStreamSynchronize(b->stream));
     HIP_TRY(hipEventElapsedTime(&b->stats_ms, b->ev_s0, b->ev_s1));
     return 0;
+}
+
+// ------------------------------------------------------------------ alignment strings (ba_*_text)
+// The format and flags of `what`, against the batch's kind and mode (the other refusals are the stats calls').
+static int text_check(int kind, uint32_t mode, uint32_t what) {
+    const uint32_t fmt = what & ba::TEXT_FORMAT;
+    if ((what & ~(ba::TEXT_FORMAT | ba::TEXT_SOFT_CLIP)) || fmt > ba::TEXT_CS)
+        return fail("text: unknown what 0x%x (BA_TEXT_CIGAR, BA_TEXT_MD or BA_TEXT_CS; BA_TEXT_CIGAR | BA_TEXT_SOFT_CLIP)", what);
+    if ((what & ba::TEXT_SOFT_CLIP) && fmt != ba::TEXT_CIGAR) return fail("text: BA_TEXT_SOFT_CLIP goes with BA_TEXT_CIGAR only");
+    if (!(mode & BA_TRACE)) return fail("text: the batch was created without BA_TRACE (the strings are rendered from the CIGAR runs)");
+    if (fmt != ba::TEXT_CIGAR && kind == BA_KIND_PROFILE_) return fail("text: MD and cs need reference letters, and a profile batch has none (BA_TEXT_CIGAR only)");
+    if (fmt != ba::TEXT_CIGAR && kind == BA_KIND_BYTES)
+        return fail("text: MD and cs are letter formats, and a ByteMatrix batch compares raw bytes (BA_TEXT_CIGAR only)");
+    return 0;
+}
+// Size (k_text_len + k_text_offsets, unless the sizes of this run and format are on the device already) and, with `text`, render
+// (k_text_write) the n pairs described by tp; offsets (n + 1) and the text are copied to the host.
+static int text_kernels(TextState& T, int device, hipStream_t stream, uint64_t run, ba::TextParams tp, uint64_t cap_n, const std::vector<uint32_t>* order,
+                        uint64_t* offsets, char* text, uint64_t capacity) {
+    HIP_TRY(hipSetDevice(device));
+    if ((!T.len.p || !T.off.p) && (T.len.alloc(cap_n * 4) || T.off.alloc((cap_n + 1) * 8))) return 1;
+    for (hipEvent_t& e : T.ev) if (!e) HIP_TRY(hipEventCreate(&e));
+    const uint32_t n = tp.n;
+    if (order && !order->empty()) {
+        if (!T.pos.p && T.pos.alloc(cap_n * 4)) return 1;
+        tp.out_pos = T.pos.as<uint32_t>();
+    }
+    tp.len = T.len.as<uint32_t>(); tp.offsets = T.off.as<uint64_t>();
+    T.ms = 0;
+    float ms = 0;
+    if (!(T.sized && T.run == run && T.what == tp.what)) {
+        T.sized = false;
+        if (tp.out_pos) HIP_TRY(hipMemcpy(T.pos.p, order->data(), (size_t)n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipEventRecord(T.ev[0], stream));
+        HIP_TRY(ba_launch_text_len(stream, &tp));
+        HIP_TRY(hipEventRecord(T.ev[1], stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(hipEventElapsedTime(&ms, T.ev[0], T.ev[1]));
+        T.ms += ms;
+        T.sized = true; T.run = run; T.what = tp.what;
+    }
+    HIP_TRY(hipMemcpy(offsets, T.off.p, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost));
+    if (!text) return 0;
+    const uint64_t total = offsets[n];
+    if (capacity < total)
+        return fail("text buffer too small: the text needs %llu bytes, the buffer holds %llu", (unsigned long long)total, (unsigned long long)capacity);
+    if (!total) return 0;
+    if (total > T.buf_cap) {
+        if (T.buf.alloc(total)) { T.buf_cap = 0; return 1; }
+        T.buf_cap = total;
+    }
+    tp.text = T.buf.as<char>();
+    HIP_TRY(hipEventRecord(T.ev[0], stream));
+    HIP_TRY(ba_launch_text_write(stream, &tp));
+    HIP_TRY(hipEventRecord(T.ev[1], stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipEventElapsedTime(&ms, T.ev[0], T.ev[1]));
+    T.ms += ms;
+    HIP_TRY(hipMemcpy(text, T.buf.p, total, hipMemcpyDeviceToHost));
+    return 0;
+}
+// One traced batch after its run, in the caller's pair order: the runs are the final ones (re-runs are merged by ba_batch_wait), the
+// sequences the batch's images.
+static int batch_text_device(BaBatch* b, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) {
+    if (text_check(b->kind, b->mode, what)) return 1;
+    if (b->in_flight) return fail("text: the batch has a launch in flight (ba_batch_wait first)");
+    if (!b->ran) return fail("text: the batch has not finished a run (ba_batch_run, or ba_batch_launch and ba_batch_wait)");
+    ba::TextParams tp{};
+    tp.n = b->n; tp.kind = seq_kind(b->kind); tp.what = what;
+    tp.seq = b->pool.as<uint8_t>(); tp.skip = 1; tp.strand = nullptr;
+    tp.q_off = b->q_off.as<uint64_t>(); tp.q_len = b->q_len.as<uint32_t>(); tp.r_off = b->r_off.as<uint64_t>(); tp.r_len = b->r_len.as<uint32_t>();
+    tp.q_end = b->qidx.as<uint32_t>(); tp.r_end = b->ridx.as<uint32_t>(); tp.status = b->status.as<uint32_t>();
+    tp.nrun = b->cig_len.as<uint32_t>(); tp.run_end = b->cig_off.as<uint64_t>(); tp.ops = b->cig_ops.as<uint32_t>();
+    return text_kernels(b->text, b->device, b->stream, b->runs_done, tp, b->cap_n, &b->h_order, offsets, text, capacity);
 }
 
 // ------------------------------------------------------------------ C ABI, Part 2
@@ -1901,6 +2013,16 @@ int ba_batch_stats(BaBatch* b, BaAlignStats* out) {
     HIP_TRY(hipMemcpy(out, b->stats.p, (size_t)b->n * sizeof(ba::AlignStats), hipMemcpyDeviceToHost));
     return 0;
 }
+int ba_batch_text(BaBatch* b, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) {
+    if (!b) return fail("null batch");
+    if (!offsets) return fail("null argument: offsets");
+    return batch_text_device(b, what, offsets, text, capacity);
+}
+int ba_batch_text_ms(BaBatch* b, float* ms) {
+    if (!b || !ms) return fail("null argument");
+    *ms = b->text.ms;
+    return 0;
+}
 int ba_batch_stats_ms(BaBatch* b, float* ms) {
     if (!b || !ms) return fail("null argument");
     *ms = b->stats_ms;
@@ -1960,6 +2082,7 @@ int ba_extend_batch_run(BaExtendBatch* e, float* kernel_ms) {
         e->total_runs = total;
     }
     e->ran = true;
+    e->runs_done++;
     if (kernel_ms) *kernel_ms = e->fill_ms;
     return 0;
 }
@@ -2004,6 +2127,32 @@ int ba_extend_batch_stats(BaExtendBatch* e, BaAlignStats* out) {
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipMemcpy(out, e->stats.p, (size_t)e->n * sizeof(ba::AlignStats), hipMemcpyDeviceToHost));
     return 0;
+}
+// The spliced runs (caller's order, out_off / runs) from the extension's start; the oriented query and the reference read from the caller's
+// bytes on the device (raw), by k_pack_images' rule. (The sides' texts cannot be joined: the equal stretches merge across the seed.)
+int ba_extend_batch_text(BaExtendBatch* e, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) {
+    if (!e) return fail("null batch");
+    if (!offsets) return fail("null argument: offsets");
+    if (text_check(e->kind, e->mode, what)) return 1;
+    if (!e->ran) return fail("text: the batch has not finished a run (ba_extend_batch_run)");
+    HIP_TRY(hipSetDevice(e->device));
+    if (!e->t_strand.p && (e->t_raw_q.alloc(e->cap_n * 8) || e->t_raw_r.alloc(e->cap_n * 8) || e->t_ql.alloc(e->cap_n * 4) || e->t_rl.alloc(e->cap_n * 4) ||
+                          e->t_strand.alloc(e->cap_n))) return 1;
+    if (!e->t_uploaded) {
+        HIP_TRY(hipMemcpy(e->t_raw_q.p, e->h_t_raw_q.data(), (size_t)e->n * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(e->t_raw_r.p, e->h_t_raw_r.data(), (size_t)e->n * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(e->t_ql.p, e->h_t_ql.data(), (size_t)e->n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(e->t_rl.p, e->h_t_rl.data(), (size_t)e->n * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(e->t_strand.p, e->h_t_strand.data(), (size_t)e->n, hipMemcpyHostToDevice));
+        e->t_uploaded = true;
+    }
+    ba::TextParams tp{};
+    tp.n = e->n; tp.kind = seq_kind(e->kind); tp.what = what;
+    tp.seq = e->raw.as<uint8_t>(); tp.skip = 0; tp.strand = e->t_strand.as<uint8_t>();
+    tp.q_off = e->t_raw_q.as<uint64_t>(); tp.q_len = e->t_ql.as<uint32_t>(); tp.r_off = e->t_raw_r.as<uint64_t>(); tp.r_len = e->t_rl.as<uint32_t>();
+    tp.q_end = e->q_end.as<uint32_t>(); tp.r_end = e->r_end.as<uint32_t>(); tp.status = e->status.as<uint32_t>();
+    tp.nrun = e->cigar_len.as<uint32_t>(); tp.run_end = e->out_off.as<uint64_t>(); tp.ops = e->runs.as<uint32_t>();
+    return text_kernels(e->text, e->device, e->stream, e->runs_done, tp, e->cap_n, nullptr, offsets, text, capacity);
 }
 void ba_extend_batch_destroy(BaExtendBatch* e) { delete e; }
 
@@ -2507,6 +2656,63 @@ int ba_multibatch_stats(BaMultiBatch* m, BaAlignStats* out) {
     if (!out) return fail("null argument");
     for (size_t k = 0; k < m->part.size(); k++)
         if (m->part[k] && ba_batch_stats(m->part[k].get(), out + m->bounds[k])) return 1;
+    return 0;
+}
+
+// alignment strings of the two batch forms over ordinary batches: sized per part, then rendered per part, in the caller's order
+int ba_sized_batch_text(BaSizedBatch* m, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) {
+    if (!m) return fail("null batch");
+    if (!offsets) return fail("null argument: offsets");
+    if (text_check(BA_KIND_NUC, m->mode, what)) return 1;   // (the kind's refusals come from the parts)
+    std::vector<uint64_t> len(m->n, 0), po;
+    std::vector<std::vector<uint64_t>> part_off(m->part.size());
+    for (size_t k = 0; k < m->part.size(); k++) {
+        const auto& ix = m->idx[k];
+        part_off[k].resize(ix.size() + 1);
+        if (batch_text_device(m->part[k].get(), what, part_off[k].data(), nullptr, 0)) return 1;
+        for (size_t i = 0; i < ix.size(); i++) len[ix[i]] = part_off[k][i + 1] - part_off[k][i];
+    }
+    offsets[0] = 0;
+    for (size_t p = 0; p < m->n; p++) offsets[p + 1] = offsets[p] + len[p];
+    if (!text) return 0;
+    if (capacity < offsets[m->n])
+        return fail("text buffer too small: the text needs %llu bytes, the buffer holds %llu", (unsigned long long)offsets[m->n], (unsigned long long)capacity);
+    std::vector<char> tmp;
+    for (size_t k = 0; k < m->part.size(); k++) {
+        const auto& ix = m->idx[k];
+        const uint64_t total = part_off[k].back();
+        if (!total) continue;
+        tmp.resize(total);
+        po.resize(ix.size() + 1);
+        if (batch_text_device(m->part[k].get(), what, po.data(), tmp.data(), total)) return 1;
+        for (size_t i = 0; i < ix.size(); i++)
+            if (len[ix[i]]) std::memcpy(text + offsets[ix[i]], tmp.data() + po[i], len[ix[i]]);
+    }
+    return 0;
+}
+int ba_multibatch_text(BaMultiBatch* m, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) {
+    if (!m) return fail("null batch");
+    if (!offsets) return fail("null argument: offsets");
+    if (text_check(BA_KIND_NUC, m->mode, what)) return 1;   // (the kind's refusals come from the parts)
+    std::vector<uint64_t> po;
+    offsets[0] = 0;
+    for (size_t k = 0; k < m->part.size(); k++) {
+        const uint64_t lo = m->bounds[k], hi = m->bounds[k + 1];
+        if (!m->part[k]) { for (uint64_t p = lo; p < hi; p++) offsets[p + 1] = offsets[lo]; continue; }
+        po.resize(hi - lo + 1);
+        if (batch_text_device(m->part[k].get(), what, po.data(), nullptr, 0)) return 1;
+        for (uint64_t p = lo; p < hi; p++) offsets[p + 1] = offsets[lo] + po[p - lo + 1];
+    }
+    const uint64_t n = m->bounds.back();
+    if (!text) return 0;
+    if (capacity < offsets[n])
+        return fail("text buffer too small: the text needs %llu bytes, the buffer holds %llu", (unsigned long long)offsets[n], (unsigned long long)capacity);
+    for (size_t k = 0; k < m->part.size(); k++) {
+        const uint64_t lo = m->bounds[k], hi = m->bounds[k + 1];
+        if (!m->part[k] || offsets[hi] == offsets[lo]) continue;
+        po.resize(hi - lo + 1);
+        if (batch_text_device(m->part[k].get(), what, po.data(), text + offsets[lo], offsets[hi] - offsets[lo])) return 1;
+    }
     return 0;
 }
 

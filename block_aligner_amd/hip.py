@@ -67,6 +67,27 @@ def _stats(call, h, n):
     return out
 
 
+TEXT_CIGAR, TEXT_MD, TEXT_CS, TEXT_SOFT_CLIP = 0, 1, 2, 1 << 8   # ba_*_text: the format, and the CIGAR's soft-clip flag
+
+
+def _text(call, h, n, what, soft_clip):
+    """The two-call pattern of one ba_*_text call: sizes, then text -> (uint8 buffer, uint64 offsets of n + 1)."""
+    w = int(what) | (TEXT_SOFT_CLIP if soft_clip else 0)
+    off = np.zeros(n + 1, np.uint64)
+    if call(h, w, off.ctypes.data, None, 0):
+        raise RuntimeError(last_error())
+    buf = np.zeros(int(off[-1]), np.uint8)
+    if buf.size and call(h, w, off.ctypes.data, buf.ctypes.data, buf.size):
+        raise RuntimeError(last_error())
+    return buf, off
+
+
+def _text_list(buf, off):
+    s = buf.tobytes().decode("ascii")
+    o = off.tolist()
+    return [s[o[p]:o[p + 1]] for p in range(len(o) - 1)]
+
+
 @dataclass(frozen=True)
 class AlignResult:
     score: int
@@ -188,6 +209,9 @@ def lib() -> C.CDLL:
         for f in ("ba_batch_stats", "ba_sized_batch_stats", "ba_multibatch_stats", "ba_extend_batch_stats"):
             getattr(L, f).argtypes = [vp, vp]
         L.ba_batch_stats_ms.argtypes = [vp, C.POINTER(C.c_float)]
+        for f in ("ba_batch_text", "ba_sized_batch_text", "ba_multibatch_text", "ba_extend_batch_text"):
+            getattr(L, f).argtypes = [vp, C.c_uint32, vp, vp, C.c_uint64]
+        L.ba_batch_text_ms.argtypes = [vp, C.POINTER(C.c_float)]
         _lib = L
         _loaded[LIB_PATH] = L
     return _lib
@@ -530,6 +554,23 @@ class BatchAligner:
             raise RuntimeError(last_error())
         return ms.value
 
+    def text(self, what=TEXT_CIGAR, soft_clip=False):
+        """TRACE batches after a run: every pair's CIGAR (TEXT_CIGAR, with soft_clip its S runs), SAM MD:Z value (TEXT_MD) or short cs:Z value
+        (TEXT_CS), rendered on the device (ba_batch_text) -> (buf: uint8 array, offsets: uint64 array of n + 1); pair p's text is
+        buf[offsets[p]:offsets[p + 1]], empty for a pair without runs or with a failure status."""
+        return _text(lib().ba_batch_text, self._h, self.n, what, soft_clip)
+
+    def text_list(self, what=TEXT_CIGAR, soft_clip=False):
+        """text() as one str per pair."""
+        return _text_list(*self.text(what, soft_clip))
+
+    def text_ms(self) -> float:
+        """HIP-event time of the text kernels the last text() call ran (the sizes, then the rendering), in milliseconds."""
+        ms = C.c_float()
+        if lib().ba_batch_text_ms(self._h, C.byref(ms)):
+            raise RuntimeError(last_error())
+        return ms.value
+
     KERNELS = ("k_align", "k_multi", "k_quad", "k_small")
 
     def spec_cells(self) -> int:
@@ -608,6 +649,13 @@ class MultiBatchAligner:
         """Per-alignment statistics in the caller's pair order (ba_multibatch_stats): as BatchAligner.stats."""
         return _stats(lib().ba_multibatch_stats, self._h, self.n)
 
+    def text(self, what=TEXT_CIGAR, soft_clip=False):
+        """Alignment strings in the caller's pair order (ba_multibatch_text): as BatchAligner.text."""
+        return _text(lib().ba_multibatch_text, self._h, self.n, what, soft_clip)
+
+    def text_list(self, what=TEXT_CIGAR, soft_clip=False):
+        return _text_list(*self.text(what, soft_clip))
+
     def kernel_ms(self):
         """Kernel time of every slice in the last run() (ms; HIP events on the slice's own stream)."""
         t = np.zeros(64, np.float32)
@@ -679,6 +727,13 @@ class SizedBatchAligner:
     def stats(self):
         """Per-alignment statistics in the caller's pair order (ba_sized_batch_stats): as BatchAligner.stats."""
         return _stats(lib().ba_sized_batch_stats, self._h, self.n)
+
+    def text(self, what=TEXT_CIGAR, soft_clip=False):
+        """Alignment strings in the caller's pair order (ba_sized_batch_text): as BatchAligner.text."""
+        return _text(lib().ba_sized_batch_text, self._h, self.n, what, soft_clip)
+
+    def text_list(self, what=TEXT_CIGAR, soft_clip=False):
+        return _text_list(*self.text(what, soft_clip))
 
     def classes(self):
         """[(min, max, pairs, fill kernel, kernel ms of the last run)] per bin."""
@@ -794,6 +849,14 @@ class ExtendBatchAligner:
         """TRACE batches after run(): per-seed statistics over q[q_start:q_end] / r[r_start:r_end] of the oriented query
         (ba_extend_batch_stats): as BatchAligner.stats."""
         return _stats(lib().ba_extend_batch_stats, self._h, self.n)
+
+    def text(self, what=TEXT_CIGAR, soft_clip=False):
+        """TRACE batches after run(): per-seed strings of the spliced runs from (q_start, r_start), over the oriented query (the reverse
+        complement on the minus strand); soft clips against the whole query (ba_extend_batch_text): as BatchAligner.text."""
+        return _text(lib().ba_extend_batch_text, self._h, self.n, what, soft_clip)
+
+    def text_list(self, what=TEXT_CIGAR, soft_clip=False):
+        return _text_list(*self.text(what, soft_clip))
 
     def close(self):
         if getattr(self, "_h", None) and _lib is not None:

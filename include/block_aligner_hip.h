@@ -10,6 +10,8 @@
  * Part 2 adds what the reference's FFI lacks for the hot path named in BASELINE.json: nucleotide / byte
  * matrices (ffi.rs:5 "do not have bindings yet") and a batch launcher that aligns many independent pairs in
  * one kernel launch (one wavefront per pair). A Rust `simd_hip` backend binds exactly these.
+ * Behind a traced run, per-alignment statistics (ba_*_stats) and the CIGAR / MD:Z / cs:Z strings of SAM and PAF output (ba_*_text) are
+ * computed on the device as well.
  *
  * Error behaviour: Part 1 functions keep the reference contract (no error codes; a violated precondition
  * aborts the process with the reference's assert message). Part 2 functions return 0 on success and a
@@ -387,6 +389,39 @@ int ba_multibatch_stats(BaMultiBatch* batch, struct BaAlignStats* out);
 int ba_extend_batch_stats(BaExtendBatch* batch, struct BaAlignStats* out);
 /* HIP-event time (ms) of the last ba_batch_stats kernel on this batch */
 int ba_batch_stats_ms(BaBatch* batch, float* ms);
+
+/* ---- alignment strings, rendered on the device from the CIGAR runs and the sequences the fill left there ("Alignment
+ * strings"): the CIGAR (optionally soft-clipped), the SAM MD:Z value and minimap2's short cs:Z value of every traced alignment, in one text
+ * buffer per call.
+ *
+ * An alignment is its runs in alignment order (ba_*_cigars) from its first cell (q_start, r_start of ba_*_stats). The letters are those of
+ * the image bytes: uppercase for NucMatrix, 'A' + code for AAMatrix, and for extension batches the oriented query (the reverse complement
+ * on the minus strand). "Equal" is BA_CIGAR_EQ's rule.
+ *   BA_TEXT_CIGAR  <len><op> per run (M = X I D): byte for byte the runs' string. | BA_TEXT_SOFT_CLIP: <q_start>S in front when q_start > 0,
+ *                  <q_len - q_end>S behind when that is > 0 (q_end = query_idx; for extension batches the result's q_end over the whole
+ *                  query). Every traced batch, profile and ByteMatrix batches included.
+ *   BA_TEXT_MD     SAM MD:Z without the prefix: equal match-type columns count, a mismatch emits the count and the reference letter, a D run
+ *                  the count, '^' and its reference letters; I columns emit nothing and do not break the count; the count closes it. Always
+ *                  [0-9]+(([A-Z]|\^[A-Z]+)[0-9]+)*.
+ *   BA_TEXT_CS     minimap2's short cs:Z without the prefix: :<n> per stretch of equal columns, *<ref><query> per mismatch, +<query> per I run,
+ *                  -<ref> per D run, letters lowercase; an I run ends a stretch.
+ * A pair without runs, or whose status has an overflow, lost or watchdog bit, gets empty text (SAM / PAF: '*').
+ *
+ * offsets: n_pairs + 1 entries, the caller's pair order, offsets[0] = 0; pair p's text is text[offsets[p] .. offsets[p + 1]), no terminators.
+ * text == NULL: fill offsets only. text != NULL and capacity < offsets[n_pairs]: refused with the bytes needed (the offsets are filled).
+ * The second call of that pattern (same `what`, same run) reuses the sizes on the device and only renders.
+ *
+ * Refused with a message (ba_last_error) and a nonzero return as the stats calls are (untraced, a launch in flight, never ran or reloaded
+ * since, a null batch, null offsets), and: MD or cs on a ByteMatrix batch (raw bytes need not be letters) or a profile batch (no reference
+ * letters), BA_TEXT_SOFT_CLIP with MD or cs, an unknown `what`. The device buffers are allocated on the first call, grow, and are freed by
+ * destroy. */
+enum { BA_TEXT_CIGAR = 0, BA_TEXT_MD = 1, BA_TEXT_CS = 2, BA_TEXT_SOFT_CLIP = 1u << 8 };
+int ba_batch_text(BaBatch* batch, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity);
+int ba_sized_batch_text(BaSizedBatch* batch, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity);
+int ba_multibatch_text(BaMultiBatch* batch, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity);
+int ba_extend_batch_text(BaExtendBatch* batch, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity);
+/* HIP-event time (ms) of the text kernels the last ba_batch_text call on this batch ran (the sizes, the rendering, or both) */
+int ba_batch_text_ms(BaBatch* batch, float* ms);
 
 enum { BA_ST_TRACE_OVERFLOW = 1, BA_ST_BLOCKS_OVERFLOW = 2, BA_ST_CIGAR_OVERFLOW = 4, BA_ST_TRACEBACK_LOST = 8, BA_ST_WATCHDOG = 16,
        BA_ST_SLOT_TIMEOUT = 32 /* never reported since round 4 (a fill wave that waits for a trace slot walks pending tracebacks itself); kept for ABI stability */,
