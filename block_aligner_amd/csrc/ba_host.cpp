@@ -2373,7 +2373,111 @@ int block_batch_align_profile_exp(const AAProfile* const* profiles, SizeRange si
 }
 }  // extern "C"
 
-// ------------------------------------------------------------------ one batch over several GPUs
+// ------------------------------------------------------------------ batches made of ordinary batches
+// A multi-device batch (one part per device) and a sized batch (one part per block range) are both a list of ordinary batches and, for
+// every part, the caller's positions of its pairs. They are created and run by their own policies; the getters are written once over
+// that representation (parts_*): a part whose positions are one contiguous run is written straight into the caller's buffers at its
+// offset, any other part is gathered into a buffer of its own and scattered to its positions.
+struct BaPartSet {
+    std::vector<std::unique_ptr<BaBatch>> part;   // null: a part without pairs (a multi-device batch with more devices than pairs)
+    std::vector<std::vector<uint64_t>> pos;       // part k's pairs: their positions in the caller's order, ascending
+    std::vector<float> last_ms;                   // kernel time of every part in the last run
+    size_t n = 0;
+    uint32_t mode = 0;
+};
+static bool one_run(const std::vector<uint64_t>& pos) { return !pos.empty() && pos.back() - pos.front() + 1 == pos.size(); }
+// One caller array as a part sees it: the part's slice of it when the part's positions are one run, else a buffer scatter() spreads.
+template <class T> struct PartOut {
+    T* out;
+    const std::vector<uint64_t>& pos;
+    std::vector<T> tmp;
+    PartOut(T* out_, const std::vector<uint64_t>& pos_) : out(out_), pos(pos_) { if (out && !one_run(pos)) tmp.resize(pos.size()); }
+    T* get() { return !out ? nullptr : (tmp.empty() ? out + pos[0] : tmp.data()); }
+    void scatter() const { for (size_t i = 0; i < tmp.size(); i++) out[pos[i]] = tmp[i]; }
+};
+static int parts_results(BaPartSet* m, int32_t* score, uint32_t* qi, uint32_t* ri, uint64_t* cells, uint32_t* cigar_len, uint32_t* status) {
+    if (!m) return fail("null batch");
+    for (size_t k = 0; k < m->part.size(); k++) {
+        if (!m->part[k]) continue;
+        const auto& pos = m->pos[k];
+        PartOut<int32_t> s(score, pos);
+        PartOut<uint32_t> a(qi, pos), b(ri, pos), l(cigar_len, pos), st(status, pos);
+        PartOut<uint64_t> c(cells, pos);
+        if (ba_batch_results(m->part[k].get(), s.get(), a.get(), b.get(), c.get(), l.get(), st.get())) return 1;
+        s.scatter(); a.scatter(); b.scatter(); c.scatter(); l.scatter(); st.scatter();
+    }
+    return 0;
+}
+static int parts_cigars(BaPartSet* m, uint32_t* runs, uint64_t capacity) {   // concatenated in the caller's pair order, as ba_batch_cigars
+    if (!m) return fail("null batch");
+    std::vector<uint32_t> len(m->n, 0);
+    if (parts_results(m, nullptr, nullptr, nullptr, nullptr, len.data(), nullptr)) return 1;
+    std::vector<uint64_t> off(m->n + 1, 0);
+    for (size_t p = 0; p < m->n; p++) off[p + 1] = off[p] + len[p];
+    if (off[m->n] > capacity) return fail("cigar buffer too small: need %llu entries", (unsigned long long)off[m->n]);
+    std::vector<uint32_t> tmp;
+    for (size_t k = 0; k < m->part.size(); k++) {
+        const auto& pos = m->pos[k];
+        uint64_t total = 0;
+        for (uint64_t p : pos) total += len[p];
+        if (!total) continue;
+        if (one_run(pos)) {
+            if (ba_batch_cigars(m->part[k].get(), runs + off[pos[0]], total)) return 1;
+            continue;
+        }
+        tmp.resize(total);
+        if (ba_batch_cigars(m->part[k].get(), tmp.data(), total)) return 1;
+        uint64_t at = 0;
+        for (uint64_t p : pos) { if (len[p]) std::memcpy(runs + off[p], tmp.data() + at, (size_t)len[p] * 4); at += len[p]; }
+    }
+    return 0;
+}
+static int parts_stats(BaPartSet* m, BaAlignStats* out) {
+    if (!m) return fail("null batch");
+    if (!out) return fail("null argument");
+    for (size_t k = 0; k < m->part.size(); k++) {
+        if (!m->part[k]) continue;
+        PartOut<BaAlignStats> o(out, m->pos[k]);
+        if (ba_batch_stats(m->part[k].get(), o.get())) return 1;
+        o.scatter();
+    }
+    return 0;
+}
+static int parts_text(BaPartSet* m, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) {   // sized per part, then rendered per part
+    if (!m) return fail("null batch");
+    if (!offsets) return fail("null argument: offsets");
+    if (text_check(BA_KIND_NUC, m->mode, what)) return 1;   // (the kind's refusals come from the parts)
+    std::vector<std::vector<uint64_t>> po(m->part.size());   // every part's own offsets
+    std::fill(offsets, offsets + m->n + 1, 0);
+    for (size_t k = 0; k < m->part.size(); k++) {
+        if (!m->part[k]) continue;
+        const auto& pos = m->pos[k];
+        po[k].resize(pos.size() + 1);
+        if (batch_text_device(m->part[k].get(), what, po[k].data(), nullptr, 0)) return 1;
+        for (size_t i = 0; i < pos.size(); i++) offsets[pos[i] + 1] = po[k][i + 1] - po[k][i];
+    }
+    for (size_t p = 0; p < m->n; p++) offsets[p + 1] += offsets[p];
+    if (!text) return 0;
+    if (capacity < offsets[m->n])
+        return fail("text buffer too small: the text needs %llu bytes, the buffer holds %llu", (unsigned long long)offsets[m->n], (unsigned long long)capacity);
+    std::vector<char> tmp;
+    for (size_t k = 0; k < m->part.size(); k++) {
+        const auto& pos = m->pos[k];
+        const uint64_t total = m->part[k] ? po[k].back() : 0;
+        if (!total) continue;
+        if (one_run(pos)) {
+            if (batch_text_device(m->part[k].get(), what, po[k].data(), text + offsets[pos[0]], total)) return 1;
+            continue;
+        }
+        tmp.resize(total);
+        if (batch_text_device(m->part[k].get(), what, po[k].data(), tmp.data(), total)) return 1;
+        for (size_t i = 0; i < pos.size(); i++)
+            if (po[k][i + 1] > po[k][i]) std::memcpy(text + offsets[pos[i]], tmp.data() + po[k][i], po[k][i + 1] - po[k][i]);
+    }
+    return 0;
+}
+
+// ---- one batch over several GPUs
 // Pairs are independent, so a batch shards without any exchange step: contiguous slices of the caller's pair
 // list, balanced by cost (|q| + |r|, what the number of driver steps follows), one BaBatch per device, each created by its
 // own host thread (packing and upload run in parallel), launched on its own stream; results come back in the caller's order.
@@ -2393,11 +2497,8 @@ extern "C" int ba_shard_slices(const uint32_t* q_len, const uint32_t* r_len, uin
     return 0;
 }
 
-struct BaMultiBatch {
-    std::vector<std::unique_ptr<BaBatch>> part;
+struct BaMultiBatch : BaPartSet {
     std::vector<uint64_t> bounds;     // part k holds the caller's pairs [bounds[k], bounds[k + 1])
-    std::vector<float> last_ms;       // kernel time of every part in the last ba_multibatch_run (HIP events on the part's own stream)
-    uint32_t mode = 0;
 };
 
 extern "C" {
@@ -2410,14 +2511,16 @@ BaMultiBatch* ba_multibatch_create(int kind, const void* matrix, Gaps gaps, Size
     for (int k = 0; k < n_devices; k++)
         if (devices[k] < 0 || devices[k] >= have) { fail("device %d out of range (%d devices)", devices[k], have); return nullptr; }
     std::unique_ptr<BaMultiBatch> m(new BaMultiBatch);
-    m->mode = mode;
+    m->n = n; m->mode = mode;
     m->bounds.resize(n_devices + 1);
     if (ba_shard_slices(q_len, r_len, n, n_devices, m->bounds.data())) return nullptr;
     m->part.resize(n_devices);
+    m->pos.resize(n_devices);
     std::vector<std::string> errs(n_devices);
     auto build = [&](int k) {
         const size_t lo = m->bounds[k], cnt = m->bounds[k + 1] - lo;
         if (cnt == 0) return;                                  // more devices than pairs: this one stays idle
+        for (size_t p = lo; p < lo + cnt; p++) m->pos[k].push_back(p);
         g_device = devices[k];                                 // (thread-local)
         BaBatch* b = ba_batch_create(kind, matrix, gaps, size, x_drop, mode, pool, q_off + lo, q_len + lo, r_off + lo, r_len + lo, cnt);
         if (!b) errs[k] = g_err; else m->part[k].reset(b);
@@ -2456,42 +2559,29 @@ int ba_multibatch_run(BaMultiBatch* m, float* kernel_ms) {
     return 0;
 }
 int ba_multibatch_results(BaMultiBatch* m, int32_t* score, uint32_t* qi, uint32_t* ri, uint64_t* cells, uint32_t* cigar_len, uint32_t* status) {
-    if (!m) return fail("null batch");
-    for (size_t k = 0; k < m->part.size(); k++) {
-        if (!m->part[k]) continue;
-        const size_t lo = m->bounds[k];
-        if (ba_batch_results(m->part[k].get(), score ? score + lo : nullptr, qi ? qi + lo : nullptr, ri ? ri + lo : nullptr, cells ? cells + lo : nullptr,
-                             cigar_len ? cigar_len + lo : nullptr, status ? status + lo : nullptr)) return 1;
-    }
-    return 0;
+    return parts_results(m, score, qi, ri, cells, cigar_len, status);
 }
-int ba_multibatch_cigars(BaMultiBatch* m, uint32_t* runs, uint64_t capacity) {
-    if (!m) return fail("null batch");
-    uint64_t at = 0;
-    for (auto& b : m->part) {
-        if (!b) continue;
-        std::vector<uint32_t> len(b->n);
-        HIP_TRY(hipSetDevice(b->device));
-        if (d2h(b->cig_len, len.data(), b->n)) return 1;
-        uint64_t total = 0;
-        for (uint32_t x : len) total += x;
-        if (at + total > capacity) return fail("cigar buffer too small: need more than %llu entries", (unsigned long long)capacity);
-        if (total && ba_batch_cigars(b.get(), runs + at, capacity - at)) return 1;
-        at += total;
-    }
-    return 0;
+int ba_multibatch_cigars(BaMultiBatch* m, uint32_t* runs, uint64_t capacity) { return parts_cigars(m, runs, capacity); }
+int ba_multibatch_stats(BaMultiBatch* m, BaAlignStats* out) { return parts_stats(m, out); }
+int ba_multibatch_text(BaMultiBatch* m, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) { return parts_text(m, what, offsets, text, capacity); }
+int ba_multibatch_kernel_ms(BaMultiBatch* m, float* ms, int capacity) {   // per slice, of the last run; returns the number of slices
+    if (!m) return -1;
+    for (int k = 0; k < capacity && k < (int)m->last_ms.size(); k++) ms[k] = m->last_ms[k];
+    return (int)m->part.size();
 }
+int ba_multibatch_parts(BaMultiBatch* m, uint64_t* bounds, int capacity) {   // slice boundaries (n_devices + 1 entries); returns n_devices
+    if (!m) return -1;
+    for (int k = 0; k < capacity && k < (int)m->bounds.size(); k++) bounds[k] = m->bounds[k];
+    return (int)m->part.size();
+}
+void ba_multibatch_destroy(BaMultiBatch* m) { delete m; }
+
 // ---- every pair with its own block range (lib.rs:109-111 percent_len per pair, as examples/nanopore_bench_global.rs:163,171 calls it):
 // pairs are binned by (min, max), every bin is an ordinary batch of this library -- the multi-pair kernels where the bin's minimum size has one --
-// launched one after the other on the device; results and CIGAR runs come back in the caller's order.
-struct BaSizedBatch {
-    std::vector<std::unique_ptr<BaBatch>> part;
+// launched together on the device (ba_sized_batch_run); results and CIGAR runs come back in the caller's order.
+struct BaSizedBatch : BaPartSet {
     std::vector<SizeRange> range;                 // part k's block range
-    std::vector<std::vector<uint32_t>> idx;       // part k's pairs (caller indices, ascending)
-    std::vector<float> last_ms;
     std::vector<double> work;                     // part k's share of the work (residues x maximum block size): launch order, memory share
-    size_t n = 0;
-    uint32_t mode = 0;
 };
 BaSizedBatch* ba_sized_batch_create(int kind, const void* matrix, Gaps gaps, const SizeRange* size_per_pair, int32_t x_drop, uint32_t mode, const uint8_t* pool,
                                     const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len, uintptr_t n) {
@@ -2504,28 +2594,28 @@ BaSizedBatch* ba_sized_batch_create(int kind, const void* matrix, Gaps gaps, con
     for (size_t p = 0; p < n; p++) {
         const auto key = std::make_pair(size_per_pair[p].min, size_per_pair[p].max);
         auto it = cls.find(key);
-        if (it == cls.end()) { it = cls.emplace(key, m->idx.size()).first; m->idx.emplace_back(); m->range.push_back(size_per_pair[p]); }
-        m->idx[it->second].push_back((uint32_t)p);
+        if (it == cls.end()) { it = cls.emplace(key, m->pos.size()).first; m->pos.emplace_back(); m->range.push_back(size_per_pair[p]); }
+        m->pos[it->second].push_back(p);
     }
-    m->part.resize(m->idx.size());
+    m->part.resize(m->pos.size());
     // every range's batch gets a share of the free device memory in proportion to what its trace stacks ask for (residues x maximum block size)
-    std::vector<double> weight(m->idx.size(), 0.0);
+    std::vector<double> weight(m->pos.size(), 0.0);
     double weight_left = 0;
-    for (size_t k = 0; k < m->idx.size(); k++) {
-        for (uint32_t p : m->idx[k]) weight[k] += ((double)q_len[p] + r_len[p] + 64.0) * (double)m->range[k].max;
+    for (size_t k = 0; k < m->pos.size(); k++) {
+        for (uint64_t p : m->pos[k]) weight[k] += ((double)q_len[p] + r_len[p] + 64.0) * (double)m->range[k].max;
         weight_left += weight[k];
     }
     m->work = weight;
     struct CapReset { ~CapReset() { g_mem_cap = ~0ull; } } cap_reset;
-    for (size_t k = 0; k < m->idx.size(); k++) {
+    for (size_t k = 0; k < m->pos.size(); k++) {
         {
             size_t free_b = 0, total_b = 0;
             (void)hipMemGetInfo(&free_b, &total_b);
-            g_mem_cap = m->idx.size() > 1 ? (uint64_t)((double)free_b * 0.95 * (weight[k] / std::max(weight_left, 1.0))) : ~0ull;
+            g_mem_cap = m->pos.size() > 1 ? (uint64_t)((double)free_b * 0.95 * (weight[k] / std::max(weight_left, 1.0))) : ~0ull;
             g_mem_cap = std::max<uint64_t>(g_mem_cap, 3ull << 30);   // (batch_plan keeps 1 GB aside; a range of a few pairs still needs its scratch)
             weight_left -= weight[k];
         }
-        const auto& ix = m->idx[k];
+        const auto& ix = m->pos[k];
         std::vector<uint64_t> qo(ix.size()), ro(ix.size());
         std::vector<uint32_t> ql(ix.size()), rl(ix.size());
         for (size_t i = 0; i < ix.size(); i++) { qo[i] = q_off[ix[i]]; ro[i] = r_off[ix[i]]; ql[i] = q_len[ix[i]]; rl[i] = r_len[ix[i]]; }
@@ -2549,19 +2639,8 @@ int ba_sized_batch_run(BaSizedBatch* m, float* kernel_ms) {
     if (!m) return fail("null batch");
     // Round 5: all ranges' launches at once, each on its batch's own stream, the ones with the most work first: a range of a few thousand pairs
     // does not fill the device (its grid is what its pairs need), and the long ranges' launches end with a few long pairs. kernel_ms: the host's
-    // clock from the first launch to the last completion (the device is idle before: the previous run was waited for). BA_SIZED_SERIAL (development):
-    // one after the other, kernel_ms the sum of the launches' event times.
+    // clock from the first launch to the last completion (the device is idle before: the previous run was waited for).
     m->last_ms.assign(m->part.size(), 0.f);
-    if (dev_env("BA_SIZED_SERIAL")) {
-        float total = 0;
-        for (size_t k = 0; k < m->part.size(); k++) {
-            float ms = 0;
-            if (ba_batch_run(m->part[k].get(), &ms)) return 1;
-            m->last_ms[k] = ms; total += ms;
-        }
-        if (kernel_ms) *kernel_ms = total;
-        return 0;
-    }
     std::vector<size_t> order(m->part.size());
     for (size_t k = 0; k < order.size(); k++) order[k] = k;
     std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return m->work[a] > m->work[b]; });
@@ -2593,140 +2672,22 @@ int ba_sized_batch_run(BaSizedBatch* m, float* kernel_ms) {
     return 0;
 }
 int ba_sized_batch_results(BaSizedBatch* m, int32_t* score, uint32_t* qi, uint32_t* ri, uint64_t* cells, uint32_t* cigar_len, uint32_t* status) {
-    if (!m) return fail("null batch");
-    for (size_t k = 0; k < m->part.size(); k++) {
-        const auto& ix = m->idx[k];
-        const size_t c = ix.size();
-        std::vector<int32_t> s(score ? c : 0); std::vector<uint32_t> a(qi ? c : 0), b(ri ? c : 0), l(cigar_len ? c : 0), st(status ? c : 0); std::vector<uint64_t> ce(cells ? c : 0);
-        if (ba_batch_results(m->part[k].get(), score ? s.data() : nullptr, qi ? a.data() : nullptr, ri ? b.data() : nullptr, cells ? ce.data() : nullptr,
-                             cigar_len ? l.data() : nullptr, status ? st.data() : nullptr)) return 1;
-        for (size_t i = 0; i < c; i++) {
-            const uint32_t p = ix[i];
-            if (score) score[p] = s[i]; if (qi) qi[p] = a[i]; if (ri) ri[p] = b[i]; if (cells) cells[p] = ce[i]; if (cigar_len) cigar_len[p] = l[i]; if (status) status[p] = st[i];
-        }
-    }
-    return 0;
+    return parts_results(m, score, qi, ri, cells, cigar_len, status);
 }
-int ba_sized_batch_cigars(BaSizedBatch* m, uint32_t* runs, uint64_t capacity) {   // concatenated in the caller's pair order, as ba_batch_cigars
-    if (!m) return fail("null batch");
-    std::vector<uint32_t> len(m->n, 0);
-    if (ba_sized_batch_results(m, nullptr, nullptr, nullptr, nullptr, len.data(), nullptr)) return 1;
-    std::vector<uint64_t> off(m->n + 1, 0);
-    for (size_t p = 0; p < m->n; p++) off[p + 1] = off[p] + len[p];
-    if (off[m->n] > capacity) return fail("cigar buffer too small: need %llu entries", (unsigned long long)off[m->n]);
-    for (size_t k = 0; k < m->part.size(); k++) {
-        const auto& ix = m->idx[k];
-        uint64_t total = 0;
-        for (uint32_t p : ix) total += len[p];
-        if (!total) continue;
-        std::vector<uint32_t> tmp(total);
-        if (ba_batch_cigars(m->part[k].get(), tmp.data(), total)) return 1;
-        uint64_t at = 0;
-        for (uint32_t p : ix) { if (len[p]) std::memcpy(runs + off[p], tmp.data() + at, (size_t)len[p] * 4); at += len[p]; }
-    }
-    return 0;
-}
+int ba_sized_batch_cigars(BaSizedBatch* m, uint32_t* runs, uint64_t capacity) { return parts_cigars(m, runs, capacity); }
+int ba_sized_batch_stats(BaSizedBatch* m, BaAlignStats* out) { return parts_stats(m, out); }
+int ba_sized_batch_text(BaSizedBatch* m, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) { return parts_text(m, what, offsets, text, capacity); }
 int ba_sized_batch_classes(BaSizedBatch* m, SizeRange* ranges, uint64_t* counts, int32_t* kernels, float* kernel_ms, int capacity) {   // the bins; returns their number
     if (!m) return -1;
     for (int k = 0; k < capacity && k < (int)m->part.size(); k++) {
         if (ranges) ranges[k] = m->range[k];
-        if (counts) counts[k] = m->idx[k].size();
+        if (counts) counts[k] = m->pos[k].size();
         if (kernels) kernels[k] = ba_batch_kernel(m->part[k].get());
         if (kernel_ms) kernel_ms[k] = k < (int)m->last_ms.size() ? m->last_ms[k] : 0.f;
     }
     return (int)m->part.size();
 }
 void ba_sized_batch_destroy(BaSizedBatch* m) { delete m; }
-
-// per-alignment statistics of the two batch forms over ordinary batches: per bin / per slice, in the caller's order
-int ba_sized_batch_stats(BaSizedBatch* m, BaAlignStats* out) {
-    if (!m) return fail("null batch");
-    if (!out) return fail("null argument");
-    std::vector<BaAlignStats> tmp;
-    for (size_t k = 0; k < m->part.size(); k++) {
-        const auto& ix = m->idx[k];
-        tmp.resize(ix.size());
-        if (ba_batch_stats(m->part[k].get(), tmp.data())) return 1;
-        for (size_t i = 0; i < ix.size(); i++) out[ix[i]] = tmp[i];
-    }
-    return 0;
-}
-int ba_multibatch_stats(BaMultiBatch* m, BaAlignStats* out) {
-    if (!m) return fail("null batch");
-    if (!out) return fail("null argument");
-    for (size_t k = 0; k < m->part.size(); k++)
-        if (m->part[k] && ba_batch_stats(m->part[k].get(), out + m->bounds[k])) return 1;
-    return 0;
-}
-
-// alignment strings of the two batch forms over ordinary batches: sized per part, then rendered per part, in the caller's order
-int ba_sized_batch_text(BaSizedBatch* m, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) {
-    if (!m) return fail("null batch");
-    if (!offsets) return fail("null argument: offsets");
-    if (text_check(BA_KIND_NUC, m->mode, what)) return 1;   // (the kind's refusals come from the parts)
-    std::vector<uint64_t> len(m->n, 0), po;
-    std::vector<std::vector<uint64_t>> part_off(m->part.size());
-    for (size_t k = 0; k < m->part.size(); k++) {
-        const auto& ix = m->idx[k];
-        part_off[k].resize(ix.size() + 1);
-        if (batch_text_device(m->part[k].get(), what, part_off[k].data(), nullptr, 0)) return 1;
-        for (size_t i = 0; i < ix.size(); i++) len[ix[i]] = part_off[k][i + 1] - part_off[k][i];
-    }
-    offsets[0] = 0;
-    for (size_t p = 0; p < m->n; p++) offsets[p + 1] = offsets[p] + len[p];
-    if (!text) return 0;
-    if (capacity < offsets[m->n])
-        return fail("text buffer too small: the text needs %llu bytes, the buffer holds %llu", (unsigned long long)offsets[m->n], (unsigned long long)capacity);
-    std::vector<char> tmp;
-    for (size_t k = 0; k < m->part.size(); k++) {
-        const auto& ix = m->idx[k];
-        const uint64_t total = part_off[k].back();
-        if (!total) continue;
-        tmp.resize(total);
-        po.resize(ix.size() + 1);
-        if (batch_text_device(m->part[k].get(), what, po.data(), tmp.data(), total)) return 1;
-        for (size_t i = 0; i < ix.size(); i++)
-            if (len[ix[i]]) std::memcpy(text + offsets[ix[i]], tmp.data() + po[i], len[ix[i]]);
-    }
-    return 0;
-}
-int ba_multibatch_text(BaMultiBatch* m, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) {
-    if (!m) return fail("null batch");
-    if (!offsets) return fail("null argument: offsets");
-    if (text_check(BA_KIND_NUC, m->mode, what)) return 1;   // (the kind's refusals come from the parts)
-    std::vector<uint64_t> po;
-    offsets[0] = 0;
-    for (size_t k = 0; k < m->part.size(); k++) {
-        const uint64_t lo = m->bounds[k], hi = m->bounds[k + 1];
-        if (!m->part[k]) { for (uint64_t p = lo; p < hi; p++) offsets[p + 1] = offsets[lo]; continue; }
-        po.resize(hi - lo + 1);
-        if (batch_text_device(m->part[k].get(), what, po.data(), nullptr, 0)) return 1;
-        for (uint64_t p = lo; p < hi; p++) offsets[p + 1] = offsets[lo] + po[p - lo + 1];
-    }
-    const uint64_t n = m->bounds.back();
-    if (!text) return 0;
-    if (capacity < offsets[n])
-        return fail("text buffer too small: the text needs %llu bytes, the buffer holds %llu", (unsigned long long)offsets[n], (unsigned long long)capacity);
-    for (size_t k = 0; k < m->part.size(); k++) {
-        const uint64_t lo = m->bounds[k], hi = m->bounds[k + 1];
-        if (!m->part[k] || offsets[hi] == offsets[lo]) continue;
-        po.resize(hi - lo + 1);
-        if (batch_text_device(m->part[k].get(), what, po.data(), text + offsets[lo], offsets[hi] - offsets[lo])) return 1;
-    }
-    return 0;
-}
-
-int ba_multibatch_kernel_ms(BaMultiBatch* m, float* ms, int capacity) {   // per slice, of the last run; returns the number of slices
-    if (!m) return -1;
-    for (int k = 0; k < capacity && k < (int)m->last_ms.size(); k++) ms[k] = m->last_ms[k];
-    return (int)m->part.size();
-}
-int ba_multibatch_parts(BaMultiBatch* m, uint64_t* bounds, int capacity) {   // slice boundaries (n_devices + 1 entries); returns n_devices
-    if (!m) return -1;
-    for (int k = 0; k < capacity && k < (int)m->bounds.size(); k++) bounds[k] = m->bounds[k];
-    return (int)m->part.size();
-}
-void ba_multibatch_destroy(BaMultiBatch* m) { delete m; }
 }  // extern "C"
 
 // ------------------------------------------------------------------ Block handles (Part 1 + generic)

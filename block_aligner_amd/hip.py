@@ -54,32 +54,7 @@ if C.sizeof(AlignStatsC) != 48 or STATS_DTYPE.itemsize != 48:
     raise ImportError(f"struct BaAlignStats must be 48 bytes, the binding declares {C.sizeof(AlignStatsC)}")
 
 
-def _stats(call, h, n):
-    """One ba_*_stats call -> dict of numpy arrays, one per BaAlignStats field, plus identity = matches / columns (0 where columns == 0)
-    and edit_distance = mismatches + ins + del (SAM NM)."""
-    rec = np.zeros(n, STATS_DTYPE)
-    if call(h, rec.ctypes.data):
-        raise RuntimeError(last_error())
-    out = {k: rec[k].copy() for k in STATS_DTYPE.names}
-    cols = out["columns"]
-    out["identity"] = np.divide(out["matches"], cols, out=np.zeros(n, np.float64), where=cols > 0)
-    out["edit_distance"] = out["mismatches"] + out["ins"] + out["del"]
-    return out
-
-
 TEXT_CIGAR, TEXT_MD, TEXT_CS, TEXT_SOFT_CLIP = 0, 1, 2, 1 << 8   # ba_*_text: the format, and the CIGAR's soft-clip flag
-
-
-def _text(call, h, n, what, soft_clip):
-    """The two-call pattern of one ba_*_text call: sizes, then text -> (uint8 buffer, uint64 offsets of n + 1)."""
-    w = int(what) | (TEXT_SOFT_CLIP if soft_clip else 0)
-    off = np.zeros(n + 1, np.uint64)
-    if call(h, w, off.ctypes.data, None, 0):
-        raise RuntimeError(last_error())
-    buf = np.zeros(int(off[-1]), np.uint8)
-    if buf.size and call(h, w, off.ctypes.data, buf.ctypes.data, buf.size):
-        raise RuntimeError(last_error())
-    return buf, off
 
 
 def _text_list(buf, off):
@@ -164,12 +139,9 @@ def lib() -> C.CDLL:
         L.ba_batch_create.argtypes = [C.c_int, vp, GapsC, SizeRangeC, i32, u32, vp, vp, vp, vp, vp, sz]
         L.ba_batch_reload.argtypes = [vp, vp, vp, vp, vp, vp, sz]
         L.ba_batch_reload_profile.argtypes = [vp, vp, vp, vp, vp, sz]
-        L.ba_batch_run.argtypes = [vp, C.POINTER(C.c_float)]
         L.ba_batch_launch.argtypes = [vp]
         L.ba_batch_wait.argtypes = [vp, C.POINTER(C.c_float)]
         L.ba_set_wait_limit_ms.argtypes = [C.c_uint64]; L.ba_set_wait_limit_ms.restype = None
-        L.ba_batch_results.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-        L.ba_batch_cigars.argtypes = [vp, vp, C.c_uint64]
         L.ba_batch_compact_cigars.argtypes = [vp, vp, C.c_uint64]
         L.ba_batch_surviving_cells.argtypes = [vp, vp]
         L.ba_batch_retried.argtypes = [vp]
@@ -179,38 +151,28 @@ def lib() -> C.CDLL:
         L.ba_batch_geometry.argtypes = [vp]
         L.ba_batch_spec_cells.argtypes = [vp, vp]
         L.ba_build_id.restype = C.c_char_p
-        L.ba_batch_destroy.argtypes = [vp]
         L.ba_multibatch_create.restype = vp
         L.ba_multibatch_create.argtypes = [C.c_int, vp, GapsC, SizeRangeC, i32, u32, vp, vp, vp, vp, vp, sz, vp, C.c_int]
-        L.ba_multibatch_run.argtypes = [vp, C.POINTER(C.c_float)]
-        L.ba_multibatch_results.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-        L.ba_multibatch_cigars.argtypes = [vp, vp, C.c_uint64]
         L.ba_multibatch_parts.argtypes = [vp, vp, C.c_int]
         L.ba_sized_batch_create.restype = vp
         L.ba_sized_batch_create.argtypes = [C.c_int, vp, GapsC, vp, i32, u32, vp, vp, vp, vp, vp, sz]
         L.ba_sized_batch_create_percent.restype = vp
         L.ba_sized_batch_create_percent.argtypes = [C.c_int, vp, GapsC, C.c_float, C.c_float, i32, u32, vp, vp, vp, vp, vp, sz]
-        L.ba_sized_batch_run.argtypes = [vp, C.POINTER(C.c_float)]
-        L.ba_sized_batch_results.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-        L.ba_sized_batch_cigars.argtypes = [vp, vp, C.c_uint64]
         L.ba_sized_batch_classes.argtypes = [vp, vp, vp, vp, vp, C.c_int]
-        L.ba_sized_batch_destroy.argtypes = [vp]
         L.ba_multibatch_kernel_ms.argtypes = [vp, vp, C.c_int]
-        L.ba_multibatch_destroy.argtypes = [vp]
         L.ba_shard_slices.argtypes = [vp, vp, sz, C.c_int, vp]
         L.ba_extend_batch_create.restype = vp
         L.ba_extend_batch_create.argtypes = [C.c_int, vp, GapsC, SizeRangeC, i32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz]
         L.ba_extend_batch_reload.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz]
-        L.ba_extend_batch_run.argtypes = [vp, C.POINTER(C.c_float)]
-        L.ba_extend_batch_results.argtypes = [vp] + [vp] * 10
-        L.ba_extend_batch_cigars.argtypes = [vp, vp, C.c_uint64]
         L.ba_extend_batch_times.argtypes = [vp, vp, vp, vp]
-        L.ba_extend_batch_destroy.argtypes = [vp]
-        for f in ("ba_batch_stats", "ba_sized_batch_stats", "ba_multibatch_stats", "ba_extend_batch_stats"):
-            getattr(L, f).argtypes = [vp, vp]
+        for f, fields in (("ba_batch", 6), ("ba_sized_batch", 6), ("ba_multibatch", 6), ("ba_extend_batch", 10)):   # the calls of _Batch
+            getattr(L, f"{f}_run").argtypes = [vp, C.POINTER(C.c_float)]
+            getattr(L, f"{f}_results").argtypes = [vp] * (1 + fields)
+            getattr(L, f"{f}_cigars").argtypes = [vp, vp, C.c_uint64]
+            getattr(L, f"{f}_stats").argtypes = [vp, vp]
+            getattr(L, f"{f}_text").argtypes = [vp, C.c_uint32, vp, vp, C.c_uint64]
+            getattr(L, f"{f}_destroy").argtypes = [vp]
         L.ba_batch_stats_ms.argtypes = [vp, C.POINTER(C.c_float)]
-        for f in ("ba_batch_text", "ba_sized_batch_text", "ba_multibatch_text", "ba_extend_batch_text"):
-            getattr(L, f).argtypes = [vp, C.c_uint32, vp, vp, C.c_uint64]
         L.ba_batch_text_ms.argtypes = [vp, C.POINTER(C.c_float)]
         _lib = L
         _loaded[LIB_PATH] = L
@@ -279,6 +241,20 @@ def _size(size) -> SizeRangeC:
     if isinstance(size, range):  # Rust `a..=b` written as range(a, b + 1)
         return SizeRangeC(size.start, size.stop - 1)
     return SizeRangeC(int(size[0]), int(size[1]))
+
+
+def _gaps(gaps) -> GapsC:
+    return GapsC(gaps.open, gaps.extend) if isinstance(gaps, S.Gaps) else GapsC(gaps[0], gaps[1])
+
+
+def _pair_arrays(pool, q_off, q_len, *r):
+    """pool, q_off, q_len[, r_off, r_len] as the C calls take them: contiguous uint8 bytes, uint64 offsets, uint32 lengths."""
+    return [np.ascontiguousarray(a, dtype=t) for a, t in zip((pool, q_off, q_len) + r, (np.uint8, np.uint64, np.uint32, np.uint64, np.uint32))]
+
+
+def _ptrs(arrays):
+    """The arrays' addresses (None stays None); keep the arrays referenced until the call has returned."""
+    return [a.ctypes.data if a is not None else None for a in arrays]
 
 
 class PaddedBytes:
@@ -411,8 +387,7 @@ class Block:
 
     def align(self, query: PaddedBytes, reference: PaddedBytes, matrix, gaps, size, x_drop: int = 0) -> None:
         raw = matrix.raw()
-        g = GapsC(gaps.open, gaps.extend) if isinstance(gaps, S.Gaps) else GapsC(gaps[0], gaps[1])
-        lib().block_align_generic(self._h, matrix.KIND, query._h, reference._h, raw.ctypes.data, g, _size(size), x_drop)
+        lib().block_align_generic(self._h, matrix.KIND, query._h, reference._h, raw.ctypes.data, _gaps(gaps), _size(size), x_drop)
 
     def align_exp(self, query, reference, matrix, gaps, size, x_drop: int, target_score: int):
         """scan_block.rs:884-902: double the min block size until the score reaches the target."""
@@ -455,120 +430,143 @@ class Block:
             self._h = None
 
 
-class BatchAligner:
-    """Batch launcher: many independent pairs, one persistent kernel launch, one wavefront per pair.
+class _Batch:
+    """What the four batch aligners share: run, results, cigars, stats, text and close over the C calls `<_C>_run`, `_results`, `_cigars`,
+    `_stats`, `_text` and `_destroy`. A subclass sets _C and, if its results have other fields, RESULTS; its constructor sets n, mode and _h."""
 
-    pool: uint8 array of raw sequence bytes; pair p = pool[q_off[p]:+q_len[p]] (query) vs pool[r_off[p]:+r_len[p]].
-    """
+    _C = ""
+    RESULTS = (("score", np.int32), ("query_idx", np.uint32), ("reference_idx", np.uint32), ("cells", np.uint64), ("cigar_len", np.uint32),
+               ("status", np.uint32))
 
-    def __init__(self, matrix, gaps, size, x_drop: int, mode: int, pool, q_off, q_len, r_off, r_len):
-        L = lib()
-        self.n = len(q_len)
-        self.mode = mode
-        pool = np.ascontiguousarray(pool, dtype=np.uint8)
-        q_off = np.ascontiguousarray(q_off, dtype=np.uint64); r_off = np.ascontiguousarray(r_off, dtype=np.uint64)
-        q_len = np.ascontiguousarray(q_len, dtype=np.uint32); r_len = np.ascontiguousarray(r_len, dtype=np.uint32)
-        raw = matrix.raw()
-        g = GapsC(gaps.open, gaps.extend) if isinstance(gaps, S.Gaps) else GapsC(gaps[0], gaps[1])
-        self._h = L.ba_batch_create(matrix.KIND, raw.ctypes.data, g, _size(size), x_drop, mode, pool.ctypes.data,
-                                    q_off.ctypes.data, q_len.ctypes.data, r_off.ctypes.data, r_len.ctypes.data, self.n)
-        if not self._h:
+    def _call(self, name, *args):
+        if getattr(lib(), f"{self._C}_{name}")(self._h, *args):
             raise RuntimeError(last_error())
-
-    def reload(self, pool, q_off, q_len, r_off, r_len) -> None:
-        """Replace the pairs and keep the device buffers (ba_batch_reload): the new set must fit the original one's sizes."""
-        pool = np.ascontiguousarray(pool, dtype=np.uint8)
-        q_off = np.ascontiguousarray(q_off, dtype=np.uint64); r_off = np.ascontiguousarray(r_off, dtype=np.uint64)
-        q_len = np.ascontiguousarray(q_len, dtype=np.uint32); r_len = np.ascontiguousarray(r_len, dtype=np.uint32)
-        if lib().ba_batch_reload(self._h, pool.ctypes.data, q_off.ctypes.data, q_len.ctypes.data, r_off.ctypes.data, r_len.ctypes.data, len(q_len)):
-            raise RuntimeError(last_error())
-        self.n = len(q_len)
 
     def run(self) -> float:
         """Launch and wait; returns the kernel's HIP-event time in milliseconds."""
         ms = C.c_float()
-        if lib().ba_batch_run(self._h, C.byref(ms)):
-            raise RuntimeError(last_error())
-        return ms.value
-
-    def launch(self) -> None:
-        """Enqueue one pass on the batch's stream and return (ba_batch_launch); wait() collects it."""
-        if lib().ba_batch_launch(self._h):
-            raise RuntimeError(last_error())
-
-    def compact_cigars(self, pinned_out=None) -> None:
-        """Between launch() and wait(): gather the CIGAR runs on the device behind the kernels -- straight into `pinned_out` (an array
-        from pinned_array(); pass the same array as cigars(out=...)) or into a device buffer (cigars() is then one copy)."""
-        if pinned_out is not None and not is_pinned(pinned_out):
-            raise ValueError("compact_cigars writes through this buffer from the device: it must come from pinned_array()")
-        if lib().ba_batch_compact_cigars(self._h, pinned_out.ctypes.data if pinned_out is not None else None, pinned_out.size if pinned_out is not None else 0):
-            raise RuntimeError(last_error())
-
-    def wait(self) -> float:
-        ms = C.c_float()
-        if lib().ba_batch_wait(self._h, C.byref(ms)):
-            raise RuntimeError(last_error())
+        self._call("run", C.byref(ms))
         return ms.value
 
     def results(self):
-        n = self.n
-        out = dict(score=np.zeros(n, np.int32), query_idx=np.zeros(n, np.uint32), reference_idx=np.zeros(n, np.uint32),
-                   cells=np.zeros(n, np.uint64), cigar_len=np.zeros(n, np.uint32), status=np.zeros(n, np.uint32))
-        if lib().ba_batch_results(self._h, *(out[k].ctypes.data for k in ("score", "query_idx", "reference_idx", "cells", "cigar_len", "status"))):
-            raise RuntimeError(last_error())
+        out = {k: np.zeros(self.n, t) for k, t in self.RESULTS}
+        self._call("results", *_ptrs(out.values()))
         return out
 
-    def cigars(self, cigar_len=None, out=None):
-        """-> (runs, offsets): runs[offsets[p]:offsets[p+1]] are pair p's packed (len << 4 | op) runs. out: a uint32 array to reuse
-        (a fresh 600 MB array costs more in page faults than the copy into it)."""
+    def cigars(self, cigar_len=None):
+        """-> (runs, offsets): runs[offsets[p]:offsets[p+1]] are pair p's packed (len << 4 | op) runs."""
+        return self._cigars(cigar_len)
+
+    def _cigars(self, cigar_len, out=None):
         if cigar_len is None:
             cigar_len = self.results()["cigar_len"]
         off = np.zeros(self.n + 1, np.uint64)
         np.cumsum(cigar_len, out=off[1:])
         total = int(off[-1])
         runs = out[:total] if out is not None and out.size >= total else np.empty(total, np.uint32)
-        if lib().ba_batch_cigars(self._h, runs.ctypes.data, runs.size):
-            raise RuntimeError(last_error())
+        self._call("cigars", runs.ctypes.data, runs.size)
         return runs, off
+
+    def stats(self):
+        """TRACE batches after a run: per-alignment statistics in pair order (ba_*_stats) -> dict of arrays: q_start, r_start, columns,
+        matches, mismatches, positives, ins, del, gap_opens, longest_ins, longest_del, path_score, plus identity = matches / columns (0 where
+        columns == 0) and edit_distance = mismatches + ins + del (SAM NM)."""
+        rec = np.zeros(self.n, STATS_DTYPE)
+        self._call("stats", rec.ctypes.data)
+        out = {k: rec[k].copy() for k in STATS_DTYPE.names}
+        cols = out["columns"]
+        out["identity"] = np.divide(out["matches"], cols, out=np.zeros(self.n, np.float64), where=cols > 0)
+        out["edit_distance"] = out["mismatches"] + out["ins"] + out["del"]
+        return out
+
+    def text(self, what=TEXT_CIGAR, soft_clip=False):
+        """TRACE batches after a run: every pair's CIGAR (TEXT_CIGAR, with soft_clip its S runs), SAM MD:Z value (TEXT_MD) or short cs:Z value
+        (TEXT_CS), rendered on the device (ba_*_text) -> (buf: uint8 array, offsets: uint64 array of n + 1); pair p's text is
+        buf[offsets[p]:offsets[p + 1]], empty for a pair without runs or with a failure status."""
+        w = int(what) | (TEXT_SOFT_CLIP if soft_clip else 0)
+        off = np.zeros(self.n + 1, np.uint64)   # the two-call pattern: sizes, then text
+        self._call("text", w, off.ctypes.data, None, 0)
+        buf = np.zeros(int(off[-1]), np.uint8)
+        if buf.size:
+            self._call("text", w, off.ctypes.data, buf.ctypes.data, buf.size)
+        return buf, off
+
+    def text_list(self, what=TEXT_CIGAR, soft_clip=False):
+        """text() as one str per pair."""
+        return _text_list(*self.text(what, soft_clip))
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            getattr(_lib, f"{self._C}_destroy")(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class BatchAligner(_Batch):
+    """Batch launcher: many independent pairs, one persistent kernel launch, one wavefront per pair.
+
+    pool: uint8 array of raw sequence bytes; pair p = pool[q_off[p]:+q_len[p]] (query) vs pool[r_off[p]:+r_len[p]].
+    """
+
+    _C = "ba_batch"
+
+    def __init__(self, matrix, gaps, size, x_drop: int, mode: int, pool, q_off, q_len, r_off, r_len):
+        self.n = len(q_len)
+        self.mode = mode
+        a = _pair_arrays(pool, q_off, q_len, r_off, r_len)
+        raw = matrix.raw()
+        self._h = lib().ba_batch_create(matrix.KIND, raw.ctypes.data, _gaps(gaps), _size(size), x_drop, mode, *_ptrs(a), self.n)
+        if not self._h:
+            raise RuntimeError(last_error())
+
+    def reload(self, pool, q_off, q_len, r_off, r_len) -> None:
+        """Replace the pairs and keep the device buffers (ba_batch_reload): the new set must fit the original one's sizes."""
+        a = _pair_arrays(pool, q_off, q_len, r_off, r_len)
+        self._call("reload", *_ptrs(a), len(a[2]))
+        self.n = len(a[2])
+
+    def launch(self) -> None:
+        """Enqueue one pass on the batch's stream and return (ba_batch_launch); wait() collects it."""
+        self._call("launch")
+
+    def compact_cigars(self, pinned_out=None) -> None:
+        """Between launch() and wait(): gather the CIGAR runs on the device behind the kernels -- straight into `pinned_out` (an array
+        from pinned_array(); pass the same array as cigars(out=...)) or into a device buffer (cigars() is then one copy)."""
+        if pinned_out is not None and not is_pinned(pinned_out):
+            raise ValueError("compact_cigars writes through this buffer from the device: it must come from pinned_array()")
+        self._call("compact_cigars", pinned_out.ctypes.data if pinned_out is not None else None, pinned_out.size if pinned_out is not None else 0)
+
+    def wait(self) -> float:
+        ms = C.c_float()
+        self._call("wait", C.byref(ms))
+        return ms.value
+
+    def cigars(self, cigar_len=None, out=None):
+        """-> (runs, offsets): runs[offsets[p]:offsets[p+1]] are pair p's packed (len << 4 | op) runs. out: a uint32 array to reuse
+        (a fresh 600 MB array costs more in page faults than the copy into it)."""
+        return self._cigars(cigar_len, out)
 
     def surviving_cells(self):
         """TRACE batches: per pair, sum of width x height over Trace::blocks() (scan_block.rs:1676-1691)."""
         out = np.zeros(self.n, np.uint64)
-        if lib().ba_batch_surviving_cells(self._h, out.ctypes.data):
-            raise RuntimeError(last_error())
+        self._call("surviving_cells", out.ctypes.data)
         return out
 
     def retried(self) -> int:
         """Pairs the last run re-ran with full-size trace slots (ba_batch_retried)."""
         return lib().ba_batch_retried(self._h)
 
-    def stats(self):
-        """TRACE batches after a run: per-alignment statistics in pair order (ba_batch_stats) -> dict of arrays: q_start, r_start, columns,
-        matches, mismatches, positives, ins, del, gap_opens, longest_ins, longest_del, path_score, identity, edit_distance."""
-        return _stats(lib().ba_batch_stats, self._h, self.n)
-
     def stats_ms(self) -> float:
         """HIP-event time of the last stats() kernel in milliseconds."""
         ms = C.c_float()
-        if lib().ba_batch_stats_ms(self._h, C.byref(ms)):
-            raise RuntimeError(last_error())
+        self._call("stats_ms", C.byref(ms))
         return ms.value
-
-    def text(self, what=TEXT_CIGAR, soft_clip=False):
-        """TRACE batches after a run: every pair's CIGAR (TEXT_CIGAR, with soft_clip its S runs), SAM MD:Z value (TEXT_MD) or short cs:Z value
-        (TEXT_CS), rendered on the device (ba_batch_text) -> (buf: uint8 array, offsets: uint64 array of n + 1); pair p's text is
-        buf[offsets[p]:offsets[p + 1]], empty for a pair without runs or with a failure status."""
-        return _text(lib().ba_batch_text, self._h, self.n, what, soft_clip)
-
-    def text_list(self, what=TEXT_CIGAR, soft_clip=False):
-        """text() as one str per pair."""
-        return _text_list(*self.text(what, soft_clip))
 
     def text_ms(self) -> float:
         """HIP-event time of the text kernels the last text() call ran (the sizes, then the rendering), in milliseconds."""
         ms = C.c_float()
-        if lib().ba_batch_text_ms(self._h, C.byref(ms)):
-            raise RuntimeError(last_error())
+        self._call("text_ms", C.byref(ms))
         return ms.value
 
     KERNELS = ("k_align", "k_multi", "k_quad", "k_small")
@@ -576,8 +574,7 @@ class BatchAligner:
     def spec_cells(self) -> int:
         """Cells of the last run's speculative, untraced rectangles (X-drop + TRACE): a part of results()["cells"]."""
         o = C.c_uint64()
-        if lib().ba_batch_spec_cells(self._h, C.byref(o)):
-            raise RuntimeError(last_error())
+        self._call("spec_cells", C.byref(o))
         return int(o.value)
 
     def info(self):
@@ -585,13 +582,6 @@ class BatchAligner:
         lib().ba_batch_info(self._h, o.ctypes.data)
         return dict(grid=int(o[0]), lds_bytes_per_wave=int(o[1]), trace_arena_bytes=int(o[2]), pool_bytes=int(o[3]),
                     kernel=self.KERNELS[lib().ba_batch_kernel(self._h)], geometry=lib().ba_batch_geometry(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.ba_batch_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
 
 def shard_slices(q_len, r_len, parts: int) -> np.ndarray:
@@ -603,58 +593,21 @@ def shard_slices(q_len, r_len, parts: int) -> np.ndarray:
     return bounds
 
 
-class MultiBatchAligner:
+class MultiBatchAligner(_Batch):
     """One batch over several GPUs (ba_multibatch_*): contiguous cost-balanced slices, one per entry of `devices`."""
 
+    _C = "ba_multibatch"
+
     def __init__(self, matrix, gaps, size, x_drop: int, mode: int, pool, q_off, q_len, r_off, r_len, devices):
-        L = lib()
         self.n = len(q_len)
         self.mode = mode
-        pool = np.ascontiguousarray(pool, dtype=np.uint8)
-        q_off = np.ascontiguousarray(q_off, dtype=np.uint64); r_off = np.ascontiguousarray(r_off, dtype=np.uint64)
-        q_len = np.ascontiguousarray(q_len, dtype=np.uint32); r_len = np.ascontiguousarray(r_len, dtype=np.uint32)
+        a = _pair_arrays(pool, q_off, q_len, r_off, r_len)
         raw = matrix.raw()
-        g = GapsC(gaps.open, gaps.extend) if isinstance(gaps, S.Gaps) else GapsC(gaps[0], gaps[1])
         dev = np.ascontiguousarray(devices, dtype=np.int32)
-        self._h = L.ba_multibatch_create(matrix.KIND, raw.ctypes.data, g, _size(size), x_drop, mode, pool.ctypes.data, q_off.ctypes.data,
-                                         q_len.ctypes.data, r_off.ctypes.data, r_len.ctypes.data, self.n, dev.ctypes.data, len(dev))
+        self._h = lib().ba_multibatch_create(matrix.KIND, raw.ctypes.data, _gaps(gaps), _size(size), x_drop, mode, *_ptrs(a), self.n,
+                                             dev.ctypes.data, len(dev))
         if not self._h:
             raise RuntimeError(last_error())
-
-    def run(self) -> float:
-        ms = C.c_float()
-        if lib().ba_multibatch_run(self._h, C.byref(ms)):
-            raise RuntimeError(last_error())
-        return ms.value
-
-    def results(self):
-        n = self.n
-        out = dict(score=np.zeros(n, np.int32), query_idx=np.zeros(n, np.uint32), reference_idx=np.zeros(n, np.uint32),
-                   cells=np.zeros(n, np.uint64), cigar_len=np.zeros(n, np.uint32), status=np.zeros(n, np.uint32))
-        if lib().ba_multibatch_results(self._h, *(out[k].ctypes.data for k in ("score", "query_idx", "reference_idx", "cells", "cigar_len", "status"))):
-            raise RuntimeError(last_error())
-        return out
-
-    def cigars(self, cigar_len=None):
-        if cigar_len is None:
-            cigar_len = self.results()["cigar_len"]
-        off = np.zeros(self.n + 1, np.uint64)
-        np.cumsum(cigar_len, out=off[1:])
-        runs = np.zeros(int(off[-1]), np.uint32)
-        if lib().ba_multibatch_cigars(self._h, runs.ctypes.data, runs.size):
-            raise RuntimeError(last_error())
-        return runs, off
-
-    def stats(self):
-        """Per-alignment statistics in the caller's pair order (ba_multibatch_stats): as BatchAligner.stats."""
-        return _stats(lib().ba_multibatch_stats, self._h, self.n)
-
-    def text(self, what=TEXT_CIGAR, soft_clip=False):
-        """Alignment strings in the caller's pair order (ba_multibatch_text): as BatchAligner.text."""
-        return _text(lib().ba_multibatch_text, self._h, self.n, what, soft_clip)
-
-    def text_list(self, what=TEXT_CIGAR, soft_clip=False):
-        return _text_list(*self.text(what, soft_clip))
 
     def kernel_ms(self):
         """Kernel time of every slice in the last run() (ms; HIP events on the slice's own stream)."""
@@ -667,73 +620,28 @@ class MultiBatchAligner:
         k = lib().ba_multibatch_parts(self._h, b.ctypes.data, 65)
         return b[: k + 1].copy()
 
-    def close(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.ba_multibatch_destroy(self._h)
-            self._h = None
 
-    __del__ = close
-
-
-class SizedBatchAligner:
+class SizedBatchAligner(_Batch):
     """Every pair with its own block range (ba_sized_batch_*): `sizes` = an (n, 2) array of (min, max), or percent = (min_percent, max_percent) of
     the longer sequence's length per pair, as examples/nanopore_bench_global.rs:144-171 calls percent_len."""
+
+    _C = "ba_sized_batch"
 
     def __init__(self, matrix, gaps, x_drop: int, mode: int, pool, q_off, q_len, r_off, r_len, sizes=None, percent=None):
         L = lib()
         self.n = len(q_len)
         self.mode = mode
-        pool = np.ascontiguousarray(pool, dtype=np.uint8)
-        q_off = np.ascontiguousarray(q_off, dtype=np.uint64); r_off = np.ascontiguousarray(r_off, dtype=np.uint64)
-        q_len = np.ascontiguousarray(q_len, dtype=np.uint32); r_len = np.ascontiguousarray(r_len, dtype=np.uint32)
+        a = _pair_arrays(pool, q_off, q_len, r_off, r_len)
         raw = matrix.raw()
-        g = GapsC(gaps.open, gaps.extend) if isinstance(gaps, S.Gaps) else GapsC(gaps[0], gaps[1])
         if (sizes is None) == (percent is None):
             raise ValueError("give either sizes or percent")
         if sizes is not None:
             sz = np.ascontiguousarray(sizes, dtype=np.uint64).reshape(self.n, 2)   # SizeRange {uintptr min, max}
-            self._h = L.ba_sized_batch_create(matrix.KIND, raw.ctypes.data, g, sz.ctypes.data, x_drop, mode, pool.ctypes.data, q_off.ctypes.data,
-                                              q_len.ctypes.data, r_off.ctypes.data, r_len.ctypes.data, self.n)
+            self._h = L.ba_sized_batch_create(matrix.KIND, raw.ctypes.data, _gaps(gaps), sz.ctypes.data, x_drop, mode, *_ptrs(a), self.n)
         else:
-            self._h = L.ba_sized_batch_create_percent(matrix.KIND, raw.ctypes.data, g, percent[0], percent[1], x_drop, mode, pool.ctypes.data, q_off.ctypes.data,
-                                                      q_len.ctypes.data, r_off.ctypes.data, r_len.ctypes.data, self.n)
+            self._h = L.ba_sized_batch_create_percent(matrix.KIND, raw.ctypes.data, _gaps(gaps), percent[0], percent[1], x_drop, mode, *_ptrs(a), self.n)
         if not self._h:
             raise RuntimeError(last_error())
-
-    def run(self) -> float:
-        ms = C.c_float()
-        if lib().ba_sized_batch_run(self._h, C.byref(ms)):
-            raise RuntimeError(last_error())
-        return ms.value
-
-    def results(self):
-        n = self.n
-        out = dict(score=np.zeros(n, np.int32), query_idx=np.zeros(n, np.uint32), reference_idx=np.zeros(n, np.uint32),
-                   cells=np.zeros(n, np.uint64), cigar_len=np.zeros(n, np.uint32), status=np.zeros(n, np.uint32))
-        if lib().ba_sized_batch_results(self._h, *(out[k].ctypes.data for k in ("score", "query_idx", "reference_idx", "cells", "cigar_len", "status"))):
-            raise RuntimeError(last_error())
-        return out
-
-    def cigars(self, cigar_len=None):
-        if cigar_len is None:
-            cigar_len = self.results()["cigar_len"]
-        off = np.zeros(self.n + 1, np.uint64)
-        np.cumsum(cigar_len, out=off[1:])
-        runs = np.zeros(int(off[-1]), np.uint32)
-        if lib().ba_sized_batch_cigars(self._h, runs.ctypes.data, runs.size):
-            raise RuntimeError(last_error())
-        return runs, off
-
-    def stats(self):
-        """Per-alignment statistics in the caller's pair order (ba_sized_batch_stats): as BatchAligner.stats."""
-        return _stats(lib().ba_sized_batch_stats, self._h, self.n)
-
-    def text(self, what=TEXT_CIGAR, soft_clip=False):
-        """Alignment strings in the caller's pair order (ba_sized_batch_text): as BatchAligner.text."""
-        return _text(lib().ba_sized_batch_text, self._h, self.n, what, soft_clip)
-
-    def text_list(self, what=TEXT_CIGAR, soft_clip=False):
-        return _text_list(*self.text(what, soft_clip))
 
     def classes(self):
         """[(min, max, pairs, fill kernel, kernel ms of the last run)] per bin."""
@@ -746,139 +654,77 @@ class SizedBatchAligner:
             cap = nb
         return [(int(r[i, 0]), int(r[i, 1]), int(c[i]), int(k[i]), float(t[i])) for i in range(nb)]
 
-    def close(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.ba_sized_batch_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
 
 class ProfileBatchAligner(BatchAligner):
     """Sequence-to-profile batch: pair p aligns the amino-acid query pool[q_off[p]:+q_len[p]] to profiles[p]
     (Block::align_profile over many pairs, examples/pssm_bench.rs:86-103)."""
 
     def __init__(self, profiles, size, x_drop: int, mode: int, pool, q_off, q_len):
-        L = lib()
         self.n = len(q_len)
         self.mode = mode
-        pool = np.ascontiguousarray(pool, dtype=np.uint8)
-        q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
-        q_len = np.ascontiguousarray(q_len, dtype=np.uint32)
+        a = _pair_arrays(pool, q_off, q_len)
         natives = [_NativeProfile(p) for p in profiles]
         arr = (C.c_void_p * self.n)(*[x._h for x in natives])
-        self._h = L.ba_batch_create_profile(arr, _size(size), x_drop, mode, pool.ctypes.data, q_off.ctypes.data, q_len.ctypes.data, self.n)
+        self._h = lib().ba_batch_create_profile(arr, _size(size), x_drop, mode, *_ptrs(a), self.n)
         if not self._h:
             raise RuntimeError(last_error())
 
 
-class ExtendBatchAligner:
+class ExtendBatchAligner(_Batch):
     """Seed-and-extend batch (ba_extend_batch_*): per seed p, X-drop extension leftwards from q[q_seed[p]] / r[r_seed[p]] (reversed prefixes)
     and rightwards from the seed's end, spliced with the seed into one result. q = pool[q_off[p]:+q_len[p]], r = pool[r_off[p]:+r_len[p]];
     strand (NucMatrix only; None = all 0): 1 aligns the reverse complement of q, and the seed coordinates and results are in that frame.
-    mode must hold X_DROP; TRACE and CIGAR_EQ are optional. Arguments are checked before the device is touched."""
+    mode must hold X_DROP; TRACE and CIGAR_EQ are optional. Arguments are checked before the device is touched.
 
+    run() fills both sides of every seed, then splices, and returns the fill kernel's time. cigars() gives seed p's runs; stats() and text()
+    describe the spliced path from (q_start, r_start) over the oriented query (the reverse complement on the minus strand), text()'s soft
+    clips are against the whole query."""
+
+    _C = "ba_extend_batch"
     RESULTS = (("score", np.int32), ("q_start", np.uint32), ("r_start", np.uint32), ("q_end", np.uint32), ("r_end", np.uint32),
                ("left_score", np.int32), ("right_score", np.int32), ("cells", np.uint64), ("cigar_len", np.uint32), ("status", np.uint32))
 
     @staticmethod
     def _arrays(pool, q_off, q_len, r_off, r_len, q_seed, r_seed, seed_len, strand):
-        a = (np.ascontiguousarray(pool, dtype=np.uint8), np.ascontiguousarray(q_off, dtype=np.uint64), np.ascontiguousarray(q_len, dtype=np.uint32),
-             np.ascontiguousarray(r_off, dtype=np.uint64), np.ascontiguousarray(r_len, dtype=np.uint32), np.ascontiguousarray(q_seed, dtype=np.uint32),
-             np.ascontiguousarray(r_seed, dtype=np.uint32), np.ascontiguousarray(seed_len, dtype=np.uint32),
-             None if strand is None else np.ascontiguousarray(strand, dtype=np.uint8))
+        a = _pair_arrays(pool, q_off, q_len, r_off, r_len) + [np.ascontiguousarray(x, dtype=np.uint32) for x in (q_seed, r_seed, seed_len)] + \
+            [None if strand is None else np.ascontiguousarray(strand, dtype=np.uint8)]
         n = len(a[2])
         if any(len(x) != n for x in a[1:] if x is not None):
             raise ValueError("q_off, q_len, r_off, r_len, q_seed, r_seed, seed_len and strand must have one entry per seed")
         return a
 
-    @staticmethod
-    def _ptrs(a):
-        return [x.ctypes.data if x is not None else None for x in a]
-
     def __init__(self, matrix, gaps, size, x_drop: int, mode: int, pool, q_off, q_len, r_off, r_len, q_seed, r_seed, seed_len, strand=None):
-        L = lib()
         a = self._arrays(pool, q_off, q_len, r_off, r_len, q_seed, r_seed, seed_len, strand)
         self.n = len(a[2])
         self.mode = mode
         raw = matrix.raw()
-        g = GapsC(gaps.open, gaps.extend) if isinstance(gaps, S.Gaps) else GapsC(gaps[0], gaps[1])
-        self._h = L.ba_extend_batch_create(matrix.KIND, raw.ctypes.data, g, _size(size), x_drop, mode, *self._ptrs(a), self.n)
+        self._h = lib().ba_extend_batch_create(matrix.KIND, raw.ctypes.data, _gaps(gaps), _size(size), x_drop, mode, *_ptrs(a), self.n)
         if not self._h:
             raise RuntimeError(last_error())
 
     def reload(self, pool, q_off, q_len, r_off, r_len, q_seed, r_seed, seed_len, strand=None) -> None:
         """Replace the seeds and keep the device buffers (ba_extend_batch_reload): the new set must fit the original one's sizes."""
         a = self._arrays(pool, q_off, q_len, r_off, r_len, q_seed, r_seed, seed_len, strand)
-        if lib().ba_extend_batch_reload(self._h, *self._ptrs(a), len(a[2])):
-            raise RuntimeError(last_error())
+        self._call("reload", *_ptrs(a), len(a[2]))
         self.n = len(a[2])
-
-    def run(self) -> float:
-        """Fill both sides of every seed, then splice; returns the fill kernel's HIP-event time in milliseconds."""
-        ms = C.c_float()
-        if lib().ba_extend_batch_run(self._h, C.byref(ms)):
-            raise RuntimeError(last_error())
-        return ms.value
 
     def times(self):
         """Device milliseconds: fill and splice of the last run(), image packers of the last create / reload."""
         f, p, s = C.c_float(), C.c_float(), C.c_float()
-        if lib().ba_extend_batch_times(self._h, C.byref(f), C.byref(p), C.byref(s)):
-            raise RuntimeError(last_error())
+        self._call("times", C.byref(f), C.byref(p), C.byref(s))
         return dict(fill_ms=f.value, pack_ms=p.value, splice_ms=s.value)
-
-    def results(self):
-        out = {k: np.zeros(self.n, t) for k, t in self.RESULTS}
-        if lib().ba_extend_batch_results(self._h, *(out[k].ctypes.data for k, _ in self.RESULTS)):
-            raise RuntimeError(last_error())
-        return out
-
-    def cigars(self, cigar_len=None):
-        """-> (runs, offsets): runs[offsets[p]:offsets[p+1]] are seed p's packed (len << 4 | op) runs."""
-        if cigar_len is None:
-            cigar_len = self.results()["cigar_len"]
-        off = np.zeros(self.n + 1, np.uint64)
-        np.cumsum(cigar_len, out=off[1:])
-        runs = np.empty(int(off[-1]), np.uint32)
-        if lib().ba_extend_batch_cigars(self._h, runs.ctypes.data, runs.size):
-            raise RuntimeError(last_error())
-        return runs, off
-
-    def stats(self):
-        """TRACE batches after run(): per-seed statistics over q[q_start:q_end] / r[r_start:r_end] of the oriented query
-        (ba_extend_batch_stats): as BatchAligner.stats."""
-        return _stats(lib().ba_extend_batch_stats, self._h, self.n)
-
-    def text(self, what=TEXT_CIGAR, soft_clip=False):
-        """TRACE batches after run(): per-seed strings of the spliced runs from (q_start, r_start), over the oriented query (the reverse
-        complement on the minus strand); soft clips against the whole query (ba_extend_batch_text): as BatchAligner.text."""
-        return _text(lib().ba_extend_batch_text, self._h, self.n, what, soft_clip)
-
-    def text_list(self, what=TEXT_CIGAR, soft_clip=False):
-        return _text_list(*self.text(what, soft_clip))
-
-    def close(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.ba_extend_batch_destroy(self._h)
-            self._h = None
-
-    __del__ = close
 
 
 def batch_align_exp(matrix, gaps, size, x_drop: int, target_score: int, mode: int, pool, q_off, q_len, r_off, r_len):
     """Block::align_exp over a batch (scan_block.rs:884-902) -> (score, query_idx, reference_idx, reached_min) arrays;
     reached_min[p] = 0 where the reference returns None."""
     n = len(q_len)
-    pool = np.ascontiguousarray(pool, dtype=np.uint8)
-    q_off = np.ascontiguousarray(q_off, dtype=np.uint64); r_off = np.ascontiguousarray(r_off, dtype=np.uint64)
-    q_len = np.ascontiguousarray(q_len, dtype=np.uint32); r_len = np.ascontiguousarray(r_len, dtype=np.uint32)
+    a = _pair_arrays(pool, q_off, q_len, r_off, r_len)
     raw = matrix.raw()
-    g = GapsC(gaps.open, gaps.extend) if isinstance(gaps, S.Gaps) else GapsC(gaps[0], gaps[1])
     res = (AlignResultC * n)()
     reached = np.zeros(n, np.uint64)
-    if lib().block_batch_align_exp(matrix.KIND, raw.ctypes.data, g, _size(size), x_drop, target_score, mode, pool.ctypes.data,
-                                   q_off.ctypes.data, q_len.ctypes.data, r_off.ctypes.data, r_len.ctypes.data, n, res, reached.ctypes.data):
+    if lib().block_batch_align_exp(matrix.KIND, raw.ctypes.data, _gaps(gaps), _size(size), x_drop, target_score, mode, *_ptrs(a), n, res,
+                                   reached.ctypes.data):
         raise RuntimeError(last_error())
     return _unpack_results(res, n) + (reached,)
 
@@ -886,14 +732,12 @@ def batch_align_exp(matrix, gaps, size, x_drop: int, target_score: int, mode: in
 def batch_align_profile_exp(profiles, size, x_drop: int, target_score: int, mode: int, pool, q_off, q_len):
     """Block::align_profile_exp over a batch (scan_block.rs:974-992)."""
     n = len(q_len)
-    pool = np.ascontiguousarray(pool, dtype=np.uint8)
-    q_off = np.ascontiguousarray(q_off, dtype=np.uint64); q_len = np.ascontiguousarray(q_len, dtype=np.uint32)
+    a = _pair_arrays(pool, q_off, q_len)
     natives = [_NativeProfile(p) for p in profiles]
     arr = (C.c_void_p * n)(*[x._h for x in natives])
     res = (AlignResultC * n)()
     reached = np.zeros(n, np.uint64)
-    if lib().block_batch_align_profile_exp(arr, _size(size), x_drop, target_score, mode, pool.ctypes.data, q_off.ctypes.data,
-                                           q_len.ctypes.data, n, res, reached.ctypes.data):
+    if lib().block_batch_align_profile_exp(arr, _size(size), x_drop, target_score, mode, *_ptrs(a), n, res, reached.ctypes.data):
         raise RuntimeError(last_error())
     return _unpack_results(res, n) + (reached,)
 

@@ -606,6 +606,26 @@ def test_multibatch_slices_merge_in_caller_order(hip, oracle):
         runs, off = m.cigars(got["cigar_len"])
         assert np.array_equal(runs, want_runs) and np.array_equal(off, want_off)
         m.close()
+    # fewer pairs than devices: the devices without a slice hold no batch, and every getter still equals a single batch's
+    few = synth.PairSet.from_lists([(pairs.query(p), pairs.reference(p)) for p in range(3)])
+    args = (NUC, (-5, -1), (32, 256), 70, mode, few.pool, few.q_off, few.q_len, few.r_off, few.r_len)
+    one, m = hip.BatchAligner(*args), hip.MultiBatchAligner(*args, [0, 0, 0, 0, 0])
+    bounds = [int(x) for x in m.parts()]
+    assert any(bounds[k] == bounds[k + 1] for k in range(5)), bounds
+    one.run(); m.run()
+    a, b = one.results(), m.results()
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    for x, y in zip(one.cigars(), m.cigars()):
+        assert np.array_equal(x, y)
+    a, b = one.stats(), m.stats()
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    for what in (hip.TEXT_CIGAR, hip.TEXT_MD, hip.TEXT_CS):
+        for x, y in zip(one.text(what), m.text(what)):
+            assert np.array_equal(x, y), what
+    assert one.text_list(soft_clip=True) == m.text_list(soft_clip=True)
+    one.close(); m.close()
     ref = oracle.batch_align(NUC, pairs.pool, pairs.q_off, pairs.q_len, pairs.r_off, pairs.r_len, (-5, -1), (32, 256), 70, ("trace", "x_drop"), cigar_eq=True, threads=8)
     assert np.array_equal(want["score"], ref["scores"]) and np.array_equal(want["cigar_len"], ref["cig_len"])
     with pytest.raises(RuntimeError, match="out of range"):
