@@ -10,12 +10,17 @@ data path; torch.distributed only provides the barrier and the max-over-ranks of
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0. GCUPS counts computed DP cells: the sum over every block-fill call of columns
-iterated x block height, counted on the device and checked against the oracle.
+iterated x block height, counted on the device and, with --full, checked against the oracle.
 
-Besides the headline the line carries (N = 1 only): `roofline` for the binding resource of the dominant kernel (packed-int16
-VALU issue; the HBM view sits in `roofline.hbm`), `cpu_baseline` (the AVX2 oracle on the host cores, which doubles as a
-bit-exact check of scores, end positions, cell counts and CIGAR runs), `secondary` (BASELINE.json configs 2, 4, 5 at reduced
-counts on the same kernels, each oracle-checked) and the secondary metrics SURVEY.md 8(d) asks for.
+Besides the headline the line carries `roofline` for the binding resource of the dominant kernel (packed-int16 VALU issue; the
+HBM view sits in `roofline.hbm`) and the secondary metrics SURVEY.md 8(d) asks for, all from the timed steps' own results. A plain
+run does nothing else: it sets up, warms up, times the steps, writes --dump-outputs and prints the line. `--full` adds what takes
+work of its own (N = 1 only where noted): the CIGAR self-check of a spread of pairs (`cigars_rescored`), the PCIe-inclusive pass
+(`e2e`, N = 1), `cpu_baseline` (N = 1 or --multibatch: the AVX2 oracle on the host cores, which doubles as a bit-exact check of
+scores, end positions, cell counts and CIGAR runs) and `secondary` (N = 1: BASELINE.json configs 2, 4, 5 and other sizes on the
+same kernels, each oracle-checked).
+
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
 """
 import argparse
 import json
@@ -48,10 +53,12 @@ def parse():
     ap.add_argument("--multibatch", action="store_true", help="ONE process, the library's own multi-GPU launcher (ba_multibatch_*: one list of pairs cut into "
                                                             "cost-balanced slices, one per device) instead of one process per GPU under torch.distributed.run")
     ap.add_argument("--no-trace", action="store_true", help="score-only variant (not the headline workload)")
-    ap.add_argument("--cpu-baseline-pairs", type=int, default=0, help="0 = size the sample for ~15 s of CPU work")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the config 2 / 4 / 5 lines")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the PCIe-inclusive pass (e2e_gcups)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also the CIGAR self-check, the PCIe-inclusive pass, the CPU baseline "
+                                                      "with its oracle parity check and the side configurations (--no-e2e, --no-cpu-baseline and --no-secondary leave parts out)")
+    ap.add_argument("--cpu-baseline-pairs", type=int, default=0, help="--full: 0 = size the sample for ~15 s of CPU work")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline (and the side configurations)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the config 2 / 4 / 5 lines")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the PCIe-inclusive pass (e2e_gcups)")
     ap.add_argument("--gen-workers", type=int, default=0, help="processes for input generation (0 = auto; use 1 under rocprofv3)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all; "
@@ -338,17 +345,18 @@ def run_multibatch(a):
     parts = [int(x) for x in mb.parts()]
     rescored = 0
     runs = off = None
-    if trace:
+    if trace and (a.full or a.dump_outputs):
         runs, off = mb.cigars(res["cigar_len"])
+    if trace and a.full:
         rescored = self_check(np, w, res, runs, off, range(0, n_total, max(1, n_total // 256)))
     if a.dump_outputs:
         dumped = dump_outputs(np, a.dump_outputs, res, runs, off)
         print(f"bench.py: wrote {', '.join(dumped)} to {a.dump_outputs}", file=sys.stderr)
     mb.close()
-    # the oracle as checker and reported CPU baseline, on a bounded sample: the first pairs of EVERY device's slice (the checker runs after
-    # the timed region and is never the thing measured)
+    # --full: the oracle as checker and reported CPU baseline, on a bounded sample: the first pairs of EVERY device's slice (the checker runs
+    # after the timed region and is never the thing measured)
     cpu = None
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         from oracle.oracle_py import Oracle, build
         build()
         o = Oracle("avx2")
@@ -521,26 +529,26 @@ def main():
         surviving = int(batch.surviving_cells().sum()) if trace else None
         full_equiv = w.full_matrix_cells()
         runs = off = None
-        if trace:
+        if trace and (a.full or a.dump_outputs):
             runs, off = batch.cigars(res["cigar_len"])
-        # oracle-independent self-check of the HIP output: a spread of pairs' CIGARs re-walked and re-scored
-        rescored = self_check(np, w, res, runs, off, range(0, n_rank, max(1, n_rank // 256))) if trace else 0
+        # --full: oracle-independent self-check of the HIP output: a spread of pairs' CIGARs re-walked and re-scored
+        rescored = self_check(np, w, res, runs, off, range(0, n_rank, max(1, n_rank // 256))) if trace and a.full else 0
         if a.dump_outputs:
             dumped = dump_outputs(np, a.dump_outputs, res, runs, off)
             print(f"bench.py: wrote {', '.join(dumped)} to {a.dump_outputs}", file=sys.stderr)
 
         batch.close()      # the 10 kbp batch's trace arena is most of the device memory: free it before the side configurations
         e2e = None
-        if trace and world == 1 and not a.no_e2e:
+        if a.full and trace and world == 1 and not a.no_e2e:
             try:
                 e2e = measure_e2e(np, H, W, w)
             except Exception as ex:   # (reported, never fatal for the headline: two arenas may not fit beside another process)
                 e2e = {"gcups": None, "error": str(ex)[:200]}
-        # ---- parity check + CPU baseline (the oracle is the checker and the "port" baseline, never the product)
+        # ---- --full: parity check + CPU baseline (the oracle is the checker and the "port" baseline, never the product)
         cpu = None
         secondary = None
         runs_checked = 0
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             from oracle.oracle_py import Oracle, build
             build()
             o = Oracle("avx2")

@@ -43,7 +43,7 @@ def test_bench_multibatch_line(hip):
     """The one-process bench form on every visible device (a small batch: this checks the harness, not the rate)."""
     ndev = min(hip.device_count(), 8)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--multibatch", "--gpus", str(ndev), "--pairs", "3000", "--len", "2000", "--edits", "200",
-                          "--tail", "100", "--steps", "2", "--warmup", "1", "--gen-workers", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--tail", "100", "--steps", "2", "--warmup", "1", "--gen-workers", "1", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == ndev and line["value"] > 0 and line["scaling"] == "weak" and line["config"]["pairs_total"] == 3000 * ndev
