@@ -2,8 +2,7 @@
 // The fill itself is an ordinary batch over every non-empty side; its kernels are untouched.
 #include <hip/hip_runtime.h>
 
-#include "ba_extend.h"
-#include "ba_params.h"
+#include "ba_launch.h"
 
 namespace {
 

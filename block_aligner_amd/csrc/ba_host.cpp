@@ -21,142 +21,25 @@
 
 #include "../../include/block_aligner_hip.h"
 #include "aa_matrices.inc"
-#include "ba_extend.h"
-#include "ba_stats.h"
-#include "ba_text.h"
-#include "ba_params.h"
+#include "ba_launch.h"
 
 using ba::BatchParams;
 using ba::BlockRec;
 
-// ------------------------------------------------------------------ kernel entry points (one TU per kind x class)
-#define BA_DECL(K, P)                                                                                                 \
-    extern "C" hipError_t ba_launch_k##K##_p##P(int, int, unsigned, unsigned, hipStream_t, const BatchParams*);       \
-    extern "C" hipError_t ba_occupancy_k##K##_p##P(int, int, unsigned, int*);                                         \
-    extern "C" hipError_t ba_launch_s_k##K##_p##P(int, int, unsigned, unsigned, hipStream_t, const BatchParams*);     \
-    extern "C" hipError_t ba_occupancy_s_k##K##_p##P(int, int, unsigned, int*);
-#define BA_DECL_KIND(K) BA_DECL(K, 1) BA_DECL(K, 2) BA_DECL(K, 4) BA_DECL(K, 8) BA_DECL(K, 16)
-BA_DECL_KIND(0) BA_DECL_KIND(1) BA_DECL_KIND(2) BA_DECL_KIND(3)
-#define BA_DECL_BIG(K)                                                                                                  \
-    extern "C" hipError_t ba_launch_big_k##K##_p32(int, int, unsigned, unsigned, hipStream_t, const BatchParams*);    \
-    extern "C" hipError_t ba_occupancy_big_k##K##_p32(int, int, unsigned, int*);
-BA_DECL_BIG(0) BA_DECL_BIG(1) BA_DECL_BIG(2) BA_DECL_BIG(3)
-#define BA_DECL_BIGS(K)                                                                                                 \
-    extern "C" hipError_t ba_launch_bigs_k##K##_p32(int, int, unsigned, unsigned, hipStream_t, const BatchParams*);   \
-    extern "C" hipError_t ba_occupancy_bigs_k##K##_p32(int, int, unsigned, int*);
-BA_DECL_BIGS(0) BA_DECL_BIGS(1) BA_DECL_BIGS(2) BA_DECL_BIGS(3)
-extern "C" hipError_t ba_launch_compact_cigars(hipStream_t, const uint32_t*, const uint64_t*, const uint32_t*, const uint64_t*, uint32_t*, uint32_t);
-extern "C" hipError_t ba_launch_cigar_offsets_and_compact(hipStream_t, const uint32_t*, const uint64_t*, const uint32_t*, const uint32_t*, uint64_t*, uint32_t*,
-                                                          unsigned long long*, unsigned long long, uint32_t);
-extern "C" hipError_t ba_launch_traceback(hipStream_t, const BatchParams*);
-extern "C" hipError_t ba_launch_lane_kat(hipStream_t, int, const short*, short*, int, unsigned);
-extern "C" hipError_t ba_launch_walk(hipStream_t, const BatchParams*, uint32_t grid);
-extern "C" hipError_t ba_launch_merge_retry(hipStream_t, const uint32_t*, uint32_t, const BatchParams*, const BatchParams*, const uint32_t*, uint32_t*);
-extern "C" hipError_t ba_launch_pack_sequences(hipStream_t, int, const uint8_t*, const uint64_t*, const uint64_t*, const uint64_t*, const uint32_t*,
-                                               const uint64_t*, const uint32_t*, uint8_t*, uint32_t, uint32_t, unsigned long long*);
-extern "C" hipError_t ba_launch_pack_images(hipStream_t, int, const uint8_t*, const uint64_t*, const uint64_t*, const uint8_t*, const uint64_t*, const uint32_t*,
-                                            const uint64_t*, const uint32_t*, uint8_t*, uint32_t, uint32_t, unsigned long long*);
-extern "C" hipError_t ba_launch_extend_results(hipStream_t, const ba::ExtendParams*);
-extern "C" hipError_t ba_launch_extend_gather(hipStream_t, const ba::ExtendParams*);
-extern "C" hipError_t ba_launch_stats(hipStream_t, const ba::StatsParams*);
-extern "C" hipError_t ba_launch_stats_extend(hipStream_t, const ba::ExtendParams*, const ba::AlignStats*, ba::AlignStats*);
-extern "C" hipError_t ba_launch_text_len(hipStream_t, const ba::TextParams*);
-extern "C" hipError_t ba_launch_text_write(hipStream_t, const ba::TextParams*);
-
-typedef hipError_t (*LaunchFn)(int, int, unsigned, unsigned, hipStream_t, const BatchParams*);
-typedef hipError_t (*OccFn)(int, int, unsigned, int*);
-#define BA_ROW(K) {ba_launch_k##K##_p1, ba_launch_k##K##_p2, ba_launch_k##K##_p4, ba_launch_k##K##_p8, ba_launch_k##K##_p16}
-#define BA_OROW(K) {ba_occupancy_k##K##_p1, ba_occupancy_k##K##_p2, ba_occupancy_k##K##_p4, ba_occupancy_k##K##_p8, ba_occupancy_k##K##_p16}
-#define BA_SROW(K) {ba_launch_s_k##K##_p1, ba_launch_s_k##K##_p2, ba_launch_s_k##K##_p4, ba_launch_s_k##K##_p8, ba_launch_s_k##K##_p16}
-#define BA_SOROW(K) {ba_occupancy_s_k##K##_p1, ba_occupancy_s_k##K##_p2, ba_occupancy_s_k##K##_p4, ba_occupancy_s_k##K##_p8, ba_occupancy_s_k##K##_p16}
-// [special modes?][kind][block class]
-static const LaunchFn g_launch[2][4][5] = {{BA_ROW(0), BA_ROW(1), BA_ROW(2), BA_ROW(3)}, {BA_SROW(0), BA_SROW(1), BA_SROW(2), BA_SROW(3)}};
-static const OccFn g_occ[2][4][5] = {{BA_OROW(0), BA_OROW(1), BA_OROW(2), BA_OROW(3)}, {BA_SOROW(0), BA_SOROW(1), BA_SOROW(2), BA_SOROW(3)}};
-// k_multi (ba_multi.hpp): four pairs per wave at 128 cells; sequence kinds only
-#define BA_DECL_M(K, P)                                                                                               \
-    extern "C" hipError_t ba_launch_m_k##K##_p##P(int, int, unsigned, unsigned, hipStream_t, const BatchParams*);     \
-    extern "C" hipError_t ba_occupancy_m_k##K##_p##P(int, int, unsigned, int*);
-#define BA_DECL_M_KIND(K) BA_DECL_M(K, 1) BA_DECL_M(K, 2) BA_DECL_M(K, 4) BA_DECL_M(K, 8) BA_DECL_M(K, 16)
-BA_DECL_M_KIND(0) BA_DECL_M_KIND(1) BA_DECL_M_KIND(2)
-#define BA_MROW(K) {ba_launch_m_k##K##_p1, ba_launch_m_k##K##_p2, ba_launch_m_k##K##_p4, ba_launch_m_k##K##_p8, ba_launch_m_k##K##_p16}
-#define BA_MOROW(K) {ba_occupancy_m_k##K##_p1, ba_occupancy_m_k##K##_p2, ba_occupancy_m_k##K##_p4, ba_occupancy_m_k##K##_p8, ba_occupancy_m_k##K##_p16}
-static const LaunchFn g_launch_m[3][5] = {BA_MROW(0), BA_MROW(1), BA_MROW(2)};
-static const OccFn g_occ_m[3][5] = {BA_MOROW(0), BA_MOROW(1), BA_MOROW(2)};
-// ... with slots of 256 cells, two pairs per wave (round 6: DNA batches that start at 256 cells -- percent_len of reads above 12.8 kbp --, block classes 512 .. 2048)
-extern "C" hipError_t ba_launch_m256_k1_p4(int, int, unsigned, unsigned, hipStream_t, const BatchParams*);
-extern "C" hipError_t ba_launch_m256_k1_p8(int, int, unsigned, unsigned, hipStream_t, const BatchParams*);
-extern "C" hipError_t ba_launch_m256_k1_p16(int, int, unsigned, unsigned, hipStream_t, const BatchParams*);
-extern "C" hipError_t ba_occupancy_m256_k1_p4(int, int, unsigned, int*);
-extern "C" hipError_t ba_occupancy_m256_k1_p8(int, int, unsigned, int*);
-extern "C" hipError_t ba_occupancy_m256_k1_p16(int, int, unsigned, int*);
-extern "C" hipError_t ba_launch_mg3_k1_p4(int, int, unsigned, unsigned, hipStream_t, const BatchParams*);
-extern "C" hipError_t ba_launch_mg3_k1_p8(int, int, unsigned, unsigned, hipStream_t, const BatchParams*);
-extern "C" hipError_t ba_launch_mg2_k1_p4(int, int, unsigned, unsigned, hipStream_t, const BatchParams*);
-extern "C" hipError_t ba_launch_mg2_k1_p8(int, int, unsigned, unsigned, hipStream_t, const BatchParams*);
-extern "C" hipError_t ba_occupancy_mg3_k1_p4(int, int, unsigned, int*);
-extern "C" hipError_t ba_occupancy_mg3_k1_p8(int, int, unsigned, int*);
-extern "C" hipError_t ba_occupancy_mg2_k1_p4(int, int, unsigned, int*);
-extern "C" hipError_t ba_occupancy_mg2_k1_p8(int, int, unsigned, int*);
-// k_multi in four-wave workgroups at three / two waves per SIMD (DNA, block classes 512 and 1024): [waves per SIMD - 2][block class]
-static const LaunchFn g_launch_mg[2][5] = {{nullptr, nullptr, ba_launch_mg2_k1_p4, ba_launch_mg2_k1_p8, nullptr}, {nullptr, nullptr, ba_launch_mg3_k1_p4, ba_launch_mg3_k1_p8, nullptr}};
-static const OccFn g_occ_mg[2][5] = {{nullptr, nullptr, ba_occupancy_mg2_k1_p4, ba_occupancy_mg2_k1_p8, nullptr}, {nullptr, nullptr, ba_occupancy_mg3_k1_p4, ba_occupancy_mg3_k1_p8, nullptr}};
-extern "C" hipError_t ba_launch_m512_k1_p8(int, int, unsigned, unsigned, hipStream_t, const BatchParams*);
-extern "C" hipError_t ba_launch_m512_k1_p16(int, int, unsigned, unsigned, hipStream_t, const BatchParams*);
-extern "C" hipError_t ba_occupancy_m512_k1_p8(int, int, unsigned, int*);
-extern "C" hipError_t ba_occupancy_m512_k1_p16(int, int, unsigned, int*);
-static const LaunchFn g_launch_m512[5] = {nullptr, nullptr, nullptr, ba_launch_m512_k1_p8, ba_launch_m512_k1_p16};   // k_multi with one slot of 512 cells per wave: [block class]
-static const OccFn g_occ_m512[5] = {nullptr, nullptr, nullptr, ba_occupancy_m512_k1_p8, ba_occupancy_m512_k1_p16};
-static const LaunchFn g_launch_m256[5] = {nullptr, nullptr, ba_launch_m256_k1_p4, ba_launch_m256_k1_p8, ba_launch_m256_k1_p16};   // [block class]
-static const OccFn g_occ_m256[5] = {nullptr, nullptr, ba_occupancy_m256_k1_p4, ba_occupancy_m256_k1_p8, ba_occupancy_m256_k1_p16};
-// ... and its LOCAL_START / FREE_QUERY_START_GAPS instantiations (the batch's flags choose)
-#define BA_DECL_MS(K, P)                                                                                              \
-    extern "C" hipError_t ba_launch_ms_k##K##_p##P(int, int, unsigned, unsigned, hipStream_t, const BatchParams*);    \
-    extern "C" hipError_t ba_occupancy_ms_k##K##_p##P(int, int, unsigned, int*);
-#define BA_DECL_MS_KIND(K) BA_DECL_MS(K, 1) BA_DECL_MS(K, 2) BA_DECL_MS(K, 4) BA_DECL_MS(K, 8) BA_DECL_MS(K, 16)
-BA_DECL_MS_KIND(0) BA_DECL_MS_KIND(1) BA_DECL_MS_KIND(2)
-#define BA_MSROW(K) {ba_launch_ms_k##K##_p1, ba_launch_ms_k##K##_p2, ba_launch_ms_k##K##_p4, ba_launch_ms_k##K##_p8, ba_launch_ms_k##K##_p16}
-#define BA_MSOROW(K) {ba_occupancy_ms_k##K##_p1, ba_occupancy_ms_k##K##_p2, ba_occupancy_ms_k##K##_p4, ba_occupancy_ms_k##K##_p8, ba_occupancy_ms_k##K##_p16}
-static const LaunchFn g_launch_ms[3][5] = {BA_MSROW(0), BA_MSROW(1), BA_MSROW(2)};
-static const OccFn g_occ_ms[3][5] = {BA_MSOROW(0), BA_MSOROW(1), BA_MSOROW(2)};
-// k_small (ba_small.hpp): sixteen pairs per wave at 32 cells; all four kinds (round 5: sequence-to-profile slots), block classes up to 1024 cells
-#define BA_DECL_SM(K, P)                                                                                              \
-    extern "C" hipError_t ba_launch_sm_k##K##_p##P(int, int, unsigned, unsigned, hipStream_t, const BatchParams*);    \
-    extern "C" hipError_t ba_occupancy_sm_k##K##_p##P(int, int, unsigned, int*);
-#define BA_DECL_SM_KIND(K) BA_DECL_SM(K, 1) BA_DECL_SM(K, 2) BA_DECL_SM(K, 4) BA_DECL_SM(K, 8)
-BA_DECL_SM_KIND(0) BA_DECL_SM_KIND(1) BA_DECL_SM_KIND(2) BA_DECL_SM_KIND(3)
-#define BA_SMROW(K) {ba_launch_sm_k##K##_p1, ba_launch_sm_k##K##_p2, ba_launch_sm_k##K##_p4, ba_launch_sm_k##K##_p8}
-#define BA_SMOROW(K) {ba_occupancy_sm_k##K##_p1, ba_occupancy_sm_k##K##_p2, ba_occupancy_sm_k##K##_p4, ba_occupancy_sm_k##K##_p8}
-static const LaunchFn g_launch_sm[4][4] = {BA_SMROW(0), BA_SMROW(1), BA_SMROW(2), BA_SMROW(3)};
-static const OccFn g_occ_sm[4][4] = {BA_SMOROW(0), BA_SMOROW(1), BA_SMOROW(2), BA_SMOROW(3)};
-// ... and its LOCAL_START / FREE_QUERY_START_GAPS instantiations (sequence kinds; the batch's flags choose)
-#define BA_DECL_SMS(K, P)                                                                                             \
-    extern "C" hipError_t ba_launch_sms_k##K##_p##P(int, int, unsigned, unsigned, hipStream_t, const BatchParams*);   \
-    extern "C" hipError_t ba_occupancy_sms_k##K##_p##P(int, int, unsigned, int*);
-#define BA_DECL_SMS_KIND(K) BA_DECL_SMS(K, 1) BA_DECL_SMS(K, 2) BA_DECL_SMS(K, 4) BA_DECL_SMS(K, 8)
-BA_DECL_SMS_KIND(0) BA_DECL_SMS_KIND(1) BA_DECL_SMS_KIND(2)
-#define BA_SMSROW(K) {ba_launch_sms_k##K##_p1, ba_launch_sms_k##K##_p2, ba_launch_sms_k##K##_p4, ba_launch_sms_k##K##_p8}
-#define BA_SMSOROW(K) {ba_occupancy_sms_k##K##_p1, ba_occupancy_sms_k##K##_p2, ba_occupancy_sms_k##K##_p4, ba_occupancy_sms_k##K##_p8}
-static const LaunchFn g_launch_sms[3][4] = {BA_SMSROW(0), BA_SMSROW(1), BA_SMSROW(2)};
-static const OccFn g_occ_sms[3][4] = {BA_SMSOROW(0), BA_SMSOROW(1), BA_SMSOROW(2)};
-extern "C" hipError_t ba_launch_walk_l2(hipStream_t, const BatchParams*, uint32_t grid);
-extern "C" hipError_t ba_launch_walk_loc(hipStream_t, const BatchParams*, uint32_t grid);
-typedef hipError_t (*QuadFn)(int, int, unsigned, hipStream_t, const BatchParams*);
-extern "C" hipError_t ba_launch_quad_k0(int, int, unsigned, hipStream_t, const BatchParams*);
-extern "C" hipError_t ba_launch_quad_k1(int, int, unsigned, hipStream_t, const BatchParams*);
-extern "C" hipError_t ba_launch_quad_k2(int, int, unsigned, hipStream_t, const BatchParams*);
-extern "C" hipError_t ba_launch_quad_k3(int, int, unsigned, hipStream_t, const BatchParams*);
-extern "C" hipError_t ba_quad_grid_k0(int, int, unsigned*);
-extern "C" hipError_t ba_quad_grid_k1(int, int, unsigned*);
-extern "C" hipError_t ba_quad_grid_k2(int, int, unsigned*);
-extern "C" hipError_t ba_quad_grid_k3(int, int, unsigned*);
-typedef hipError_t (*QuadGridFn)(int, int, unsigned*);
-static const QuadGridFn g_quad_grid[4] = {ba_quad_grid_k0, ba_quad_grid_k1, ba_quad_grid_k2, ba_quad_grid_k3};
-static const QuadFn g_launch_quad[4] = {ba_launch_quad_k0, ba_launch_quad_k1, ba_launch_quad_k2, ba_launch_quad_k3};
-// [special modes?][kind]
-static const LaunchFn g_launch_big[2][4] = {{ba_launch_big_k0_p32, ba_launch_big_k1_p32, ba_launch_big_k2_p32, ba_launch_big_k3_p32},
-                                            {ba_launch_bigs_k0_p32, ba_launch_bigs_k1_p32, ba_launch_bigs_k2_p32, ba_launch_bigs_k3_p32}};
-static const OccFn g_occ_big[2][4] = {{ba_occupancy_big_k0_p32, ba_occupancy_big_k1_p32, ba_occupancy_big_k2_p32, ba_occupancy_big_k3_p32},
-                                      {ba_occupancy_bigs_k0_p32, ba_occupancy_bigs_k1_p32, ba_occupancy_bigs_k2_p32, ba_occupancy_bigs_k3_p32}};
+// ------------------------------------------------------------------ the kernel catalogue (ba_launch.h)
+// [special modes?][kind][block class][family]: filled by the kernel translation units while the library loads.
+typedef const ba::KernelEntry* KernelTable[2][ba::N_KINDS][ba::N_CLASSES][ba::FAM_COUNT];
+static KernelTable& kernel_table() { static KernelTable t = {}; return t; }
+int ba::register_kernels(int kind, int pmax, bool special, const ba::KernelEntry* entries, int n) {
+    int pc = 0;
+    while ((1 << pc) < pmax) pc++;   // packed registers per lane 1 .. 16 -> block class 0 .. 4, 32 -> the row-tiled class
+    for (int k = 0; k < n; k++) kernel_table()[special][kind][pc][entries[k].family] = &entries[k];
+    return n;
+}
+static const ba::KernelEntry* find_kernel(int family, int kind, int pc, int special) {
+    if (family < 0 || family >= ba::FAM_COUNT || kind < 0 || kind >= ba::N_KINDS || pc < 0 || pc >= ba::N_CLASSES || special < 0 || special > 1) return nullptr;
+    return kernel_table()[special][kind][pc][family];
+}
 constexpr int BA_PCLASS_BIG = 5;
 static inline int special_of(uint32_t mode) { return (mode & (BA_LOCAL_START | BA_FREE_QUERY_START_GAPS | BA_FREE_QUERY_END_GAPS)) ? 1 : 0; }
 constexpr int BA_KIND_PROFILE_ = ba::KIND_PROFILE;   // batches whose "reference" is an AAProfile (sequence bytes: AA alphabet)
@@ -668,6 +551,73 @@ static int pipe_cut(BaBatch* b, const uint32_t* ql, const uint32_t* rl, size_t n
     return 1;
 }
 
+// ------------------------------------------------------------------ the kernel of a batch
+// The one place that maps what batch_build chose to a kernel family. (A quad batch's own kernel is the per-pair one, which finishes the pairs k_quad
+// hands over: b->grid and b->lds are that kernel's. k_quad itself is kernel_of(b, true).)
+static ba::KernelFamily family_of(const BaBatch* b) {
+    if (b->pclass == BA_PCLASS_BIG) return ba::FAM_TILED;
+    if (b->multi) return b->geom == 2 ? ba::FAM_MULTI_G2 : (b->geom ? ba::FAM_MULTI_G3 : (b->multi_b == 512 ? ba::FAM_MULTI_512 : (b->multi_b == 256 ? ba::FAM_MULTI_256 : ba::FAM_MULTI)));
+    return b->small ? ba::FAM_SMALL : ba::FAM_PAIR;
+}
+static const ba::KernelEntry* kernel_of(const BaBatch* b, bool quad = false) {
+    const int family = quad ? ba::FAM_QUAD : family_of(b), pc = quad ? 0 : (int)b->pclass, special = quad ? 0 : special_of(b->mode);   // (k_quad: one per kind)
+    const ba::KernelEntry* k = find_kernel(family, b->kind, pc, special);
+    if (!k) fail("no kernel of family %d for kind %d, block class %d, %s modes", family, b->kind, pc, special ? "special" : "plain");
+    return k;
+}
+// ... and what else depends on the family: LDS bytes per workgroup, bytes per wave in the `big` arena
+static uint32_t kernel_lds_bytes(const BaBatch* b) {
+    const uint32_t cells = lds_class_cells((int)b->pclass);   // (sized by the block class 128 << pc, as the kernels lay it out)
+    switch (family_of(b)) {
+    case ba::FAM_PAIR: case ba::FAM_TILED:   // + the traceback wave's windows (the special modes' walk records also hold zero-mask bits)
+        return ba::lds_wg_bytes_h(b->kind, cells) + ((b->mode & BA_TRACE) ? (special_of(b->mode) ? ba::TB_LDS_BYTES_LOC : ba::TB_LDS_BYTES) : 0u);
+    case ba::FAM_SMALL: return ba::sm_wg_bytes_h(b->kind, cells);
+    default: return ba::mq_wg_bytes_h(b->kind, cells, b->wpw);   // (k_multi's traceback waves keep their records in their own wave's region: no extra space)
+    }
+}
+static size_t kernel_wave_arena_bytes(const BaBatch* b) {
+    switch (family_of(b)) {
+    case ba::FAM_PAIR: return 0;
+    case ba::FAM_TILED: return ba::big_wave_shorts(b->max_size) * sizeof(short);
+    case ba::FAM_SMALL: return ba::SM_WAVE_BYTES;
+    default: return ba::MQ_WAVE_BYTES;
+    }
+}
+// The kernel of the entry for the batch's X_DROP bit, with / without traceback; bp's flags choose the form where the family has two.
+static const void* kernel_fn(const BaBatch* b, const ba::KernelEntry* k, bool trace, int form) { return k->fn[form][trace][(b->mode & BA_X_DROP) != 0]; }
+static hipError_t kernel_lds_opt_in(const void* fn, unsigned lds) {   // more than the default dynamic-LDS limit: opt in (160 KB per CU on gfx950)
+    return lds > 64 * 1024 ? hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
+}
+static hipError_t kernel_launch(const BaBatch* b, const ba::KernelEntry* k, bool trace, unsigned grid, unsigned lds, hipStream_t s, const BatchParams* bp) {
+    const void* fn = kernel_fn(b, k, trace, (k->fn[1][0][0] && !(bp->flags & ba::F_LOCAL)) ? 1 : 0);
+    if (hipError_t e = kernel_lds_opt_in(fn, lds)) return e;
+    void* args[] = {(void*)bp};
+    return hipLaunchKernel(fn, dim3(grid), dim3(k->wpw * 64), args, lds, s);
+}
+static hipError_t kernel_occupancy(const BaBatch* b, const ba::KernelEntry* k, bool trace, unsigned lds, int* blocks_per_cu) {
+    *blocks_per_cu = 0;
+    for (int form = 0; form < 2 && k->fn[form][0][0]; form++) {   // (two forms, one launch geometry for both: the smaller)
+        const void* fn = kernel_fn(b, k, trace, form);
+        int v = 0;
+        if (hipError_t e = kernel_lds_opt_in(fn, lds)) return e;
+        if (hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, fn, (int)k->wpw * 64, lds)) return e;
+        *blocks_per_cu = form ? std::min(*blocks_per_cu, v) : v;
+    }
+    return hipSuccess;
+}
+// Workgroups of k_quad: what fits, at least 1 and at most 32 waves per CU, on every CU of the current device.
+static int quad_grid(const BaBatch* b, uint32_t* grid) {
+    const ba::KernelEntry* k = kernel_of(b, true);
+    if (!k) return 1;
+    int per_cu = 0, dev = 0;
+    hipDeviceProp_t prop;
+    if (kernel_occupancy(b, k, (b->mode & BA_TRACE) != 0, k->lds, &per_cu) != hipSuccess || hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess)
+        return fail("occupancy query failed for the small-block kernel");
+    per_cu = std::max(1, std::min(per_cu, 32 / (int)k->wpw));
+    *grid = (uint32_t)(prop.multiProcessorCount * per_cu);
+    return *grid ? 0 : fail("occupancy query failed for the small-block kernel");
+}
+
 // Launch geometry and scratch sizes of a batch whose inputs are known: workgroups, LDS, trace slot size, traceback waves,
 // slots per wave, hand-off ring. fixed_bytes = device memory the batch needs besides its per-wave scratch.
 static int batch_plan(BaBatch* b, size_t n, uint64_t fixed_bytes, uint64_t maxlen2, bool full_trace, uint64_t avg_len2 = ~0ull) {
@@ -675,16 +625,12 @@ static int batch_plan(BaBatch* b, size_t n, uint64_t fixed_bytes, uint64_t maxle
     const bool trace = mode & BA_TRACE;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, b->device) != hipSuccess) { fail("hipGetDeviceProperties failed"); return 1; }
-    // (sized by the block class 128 << pc, as the kernels lay it out, + the traceback wave's windows)
-    // (k_multi's traceback waves keep their records in their own wave's region: no extra space)
-    b->lds = b->multi ? ba::mq_wg_bytes_h(kind, lds_class_cells(pc), b->wpw) : (b->small ? ba::sm_wg_bytes_h(kind, lds_class_cells(pc)) : ba::lds_wg_bytes_h(kind, lds_class_cells(pc)) + (trace ? (special_of(mode) ? ba::TB_LDS_BYTES_LOC : ba::TB_LDS_BYTES) : 0u));   // (the special modes' walk records also hold zero-mask bits)
+    const ba::KernelEntry* k = kernel_of(b);
+    if (!k) return 1;
+    b->lds = kernel_lds_bytes(b);
     if (b->lds > 160 * 1024) { fail("block size %zu needs %u bytes of LDS per workgroup", max_size, b->lds); return 1; }
-    if (b->lds > 64 * 1024) {
-        // handled per kernel in the launcher TU (hipFuncSetAttribute) -- see ba_kernels.hip
-    }
-    int per_cu = 0;
-    const OccFn occ = pc == BA_PCLASS_BIG ? g_occ_big[special_of(mode)][kind] : (b->multi ? (b->geom ? g_occ_mg[b->geom - 2][pc] : b->multi_b == 512 ? g_occ_m512[pc] : b->multi_b == 256 ? g_occ_m256[pc] : special_of(mode) ? g_occ_ms[kind][pc] : g_occ_m[kind][pc]) : (b->small ? (special_of(mode) ? g_occ_sms[kind][pc] : g_occ_sm[kind][pc]) : g_occ[special_of(mode)][kind][pc]));
-    if (occ(trace, (mode & BA_X_DROP) != 0, b->lds, &per_cu) != hipSuccess || per_cu <= 0) {
+    int per_cu = 0;   // (more than 64 KB: opted in per kernel, kernel_lds_opt_in)
+    if (kernel_occupancy(b, k, trace, b->lds, &per_cu) != hipSuccess || per_cu <= 0) {
         fail("occupancy query failed for kind %d class %d (lds %u)", kind, pc, b->lds); return 1;
     }
     if (per_cu * b->wpw > 32) per_cu = 32 / b->wpw;
@@ -843,8 +789,7 @@ static int batch_alloc_scratch(BaBatch* b) {
     BA_ALLOC(trace, b->pipe ? b->pipe_words * 4 : b->trace_stride * 4 * b->slots);
     BA_ALLOC(blocks, b->pipe ? b->pipe_recs * sizeof(BlockRec) : b->blocks_stride * sizeof(BlockRec) * b->slots);
     BA_ALLOC(ckpt, (size_t)(b->grid + b->cq_grid) * b->wpw * 8 * b->max_size * sizeof(short));
-    BA_ALLOC(big, b->pclass == BA_PCLASS_BIG ? (size_t)b->grid * b->wpw * ba::big_wave_shorts(b->max_size) * sizeof(short)
-                                              : (b->multi ? (size_t)b->grid * b->wpw * ba::MQ_WAVE_BYTES : (b->small ? (size_t)b->grid * b->wpw * ba::SM_WAVE_BYTES : 0)));
+    BA_ALLOC(big, (size_t)b->grid * b->wpw * kernel_wave_arena_bytes(b));
     BA_ALLOC(tb_queue, (size_t)b->tb_qsize * 4); BA_ALLOC(tb_ctrl, 256); BA_ALLOC(prof, 2048); BA_ALLOC(params_dev, sizeof(BatchParams));
     BA_ALLOC(slot_free, (size_t)b->slots * 4); BA_ALLOC(slot_info, (size_t)b->slots * sizeof(ba::SlotInfo)); BA_ALLOC(counter, 128);
     if (b->multi) BA_ALLOC(donate, ((size_t)b->grid * b->wpw + 64) * 4);   // (+ two counters in their own cache lines)
@@ -1079,7 +1024,7 @@ static BaBatch* batch_build(int kind, const void* matrix, Gaps gaps, SizeRange s
     if (b->pipe && (b->trace_off.alloc((n + 1) * 8) || b->blocks_off.alloc((n + 1) * 8))) return nullptr;
     if (b->quad) {
         if (b->cq_queue.alloc(n * 4) || b->cq_ctrl.alloc(256)) return nullptr;
-        if (g_quad_grid[kind](trace ? 1 : 0, (mode & BA_X_DROP) ? 1 : 0, &b->quad_grid) != hipSuccess || !b->quad_grid) { fail("occupancy query failed for the small-block kernel"); return nullptr; }
+        if (quad_grid(b.get(), &b->quad_grid)) return nullptr;
     }
     if ((b->quad || b->small) && (hipStreamCreateWithFlags(&b->stream2, hipStreamNonBlocking) != hipSuccess ||
                                hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&b->ev_join, hipEventDisableTiming) != hipSuccess)) {
@@ -1260,7 +1205,9 @@ static int batch_launch(BaBatch* b) {
     const BatchParams bp = b->params();
     HIP_TRY(hipEventRecord(b->ev0, b->stream));
     if (b->ev_l0) HIP_TRY(hipEventRecord(b->ev_l0, b->stream));   // (a re-run sub-batch: batch_retry re-uses ev0 for the merge)
-    const LaunchFn launch = b->pclass == BA_PCLASS_BIG ? g_launch_big[special_of(b->mode)][b->kind] : (b->multi ? (b->geom ? g_launch_mg[b->geom - 2][b->pclass] : b->multi_b == 512 ? g_launch_m512[b->pclass] : b->multi_b == 256 ? g_launch_m256[b->pclass] : special_of(b->mode) ? g_launch_ms[b->kind][b->pclass] : g_launch_m[b->kind][b->pclass]) : g_launch[special_of(b->mode)][b->kind][b->pclass]);
+    const ba::KernelEntry* k = kernel_of(b);
+    const bool tr = b->mode & BA_TRACE, xd = b->mode & BA_X_DROP;
+    if (!k) return 1;
     if (b->quad && b->n <= b->cap_n) {
         // k_quad starts every pair -- its first block and plain shift steps, four pairs per wave -- and finishes the global
         // alignments that never need more. A pair that does (a grow, X-drop termination, fewer than 32 residues) goes through a
@@ -1268,7 +1215,8 @@ static int batch_launch(BaBatch* b) {
         // first and leave early: their remaining steps are a long serial chain best started at once), a full-size one after it.
         // TRACE (a pair-slot batch): k_quad only stacks trace words; the paths of the pairs it finished are walked by k_walk, one
         // pair per lane, the per-pair kernel walks its own pairs' paths at once.
-        const int tr = (b->mode & BA_TRACE) ? 1 : 0, xd = (b->mode & BA_X_DROP) ? 1 : 0;
+        const ba::KernelEntry* kq = kernel_of(b, true);
+        if (!kq) return 1;
         uint32_t* flagA = b->cont_n.as<uint32_t>();
         HIP_TRY(hipMemsetAsync(flagA, 0, (size_t)b->n * 4, b->stream));
         HIP_TRY(hipMemsetAsync(b->cq_queue.p, 0, (size_t)b->n * 4, b->stream));
@@ -1277,7 +1225,7 @@ static int batch_launch(BaBatch* b) {
         BatchParams pq = bp; pq.cont_out = b->contA.as<ba::PairCont>(); pq.cont_out_flag = flagA;
         pq.cq_queue = b->cq_queue.as<uint32_t>(); pq.cq_ctrl = b->cq_ctrl.as<uint32_t>(); pq.cq_producers = b->quad_grid * ba::WAVES_PER_WG;
         pq.work_chunk = 4;   // (one position per slot: pairs come longest first, and a long chunk would queue the longest pairs on one wave)
-        HIP_TRY(g_launch_quad[b->kind](tr, xd, b->quad_grid, b->stream, &pq));
+        HIP_TRY(kernel_launch(b, kq, tr, b->quad_grid, kq->lds, b->stream, &pq));
         // (the pairs that reach the per-pair kernel -- with X-drop all of them, since termination is not a plain shift step: their
         // paths go to a second k_walk; without, only the pairs that grow: lane 0 walks each at once, nothing is left for the end)
         const bool walk2 = tr && bp.cig_ops && xd;
@@ -1291,14 +1239,14 @@ static int batch_launch(BaBatch* b) {
         if (beside) {
             BatchParams pa = pc; pa.ckpt_wave0 = b->grid * ba::WAVES_PER_WG; pa.cq_side = 1;
             HIP_TRY(hipStreamWaitEvent(b->stream2, b->ev_fork, 0));
-            HIP_TRY(launch(tr, xd, b->cq_grid, b->lds, b->stream2, &pa));
+            HIP_TRY(kernel_launch(b, k, tr, b->cq_grid, b->lds, b->stream2, &pa));
             HIP_TRY(hipEventRecord(b->ev_join, b->stream2));
         }
         if (tr && bp.cig_ops) {
             BatchParams w1 = bp; w1.cont_mode = 1; w1.cont_in_flag = flagA; w1.work_counter = b->counter.as<uint32_t>() + 8;   // (its own counter, zeroed above)
             HIP_TRY(ba_launch_walk(b->stream, &w1, walk_grid(b)));
         }
-        HIP_TRY(launch(tr, xd, b->grid, b->lds, b->stream, &pc));
+        HIP_TRY(kernel_launch(b, k, tr, b->grid, b->lds, b->stream, &pc));
         if (beside) HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_join, 0));
         if (walk2) {
             BatchParams w2 = bp; w2.cont_mode = 2; w2.cont_in_flag = flagA; w2.work_counter = b->counter.as<uint32_t>() + 12;
@@ -1310,7 +1258,6 @@ static int batch_launch(BaBatch* b) {
         // (the pairs run one to a wave at the start of the launch -- the batch's longest -- walk their paths at once, with the whole wave:
         // the longest walk of the batch overlaps with the fill instead of ending the launch)
         BatchParams p1 = bp; p1.inline_len2 = ~0u;
-        const LaunchFn launch_sm = special_of(b->mode) ? g_launch_sms[b->kind][b->pclass] : g_launch_sm[b->kind][b->pclass];
         const uint32_t side_n = (b->stream2 && !special_of(b->mode) && (bp.cig_ops || !(b->mode & BA_TRACE)) && b->sm_side_n && b->sm_side_n <= b->sm_excl_n) ? b->sm_side_n : 0u;
         uint32_t grid_main = b->grid;
         if (side_n) {
@@ -1327,11 +1274,11 @@ static int batch_launch(BaBatch* b) {
             ps.big = (short*)((char*)b->big.p + (size_t)grid_main * ba::WAVES_PER_WG * ba::SM_WAVE_BYTES);
             ps.ckpt_wave0 = grid_main * ba::WAVES_PER_WG; ps.cq_side = 1;
             HIP_TRY(hipStreamWaitEvent(b->stream2, b->ev_fork, 0));
-            HIP_TRY(launch_sm((b->mode & BA_TRACE) != 0, (b->mode & BA_X_DROP) != 0, grid_side, b->lds, b->stream2, &ps));
+            HIP_TRY(kernel_launch(b, k, tr, grid_side, b->lds, b->stream2, &ps));
             HIP_TRY(hipEventRecord(b->ev_join, b->stream2));
             p1.sm_excl_first = side_n;
         }
-        HIP_TRY(launch_sm((b->mode & BA_TRACE) != 0, (b->mode & BA_X_DROP) != 0, grid_main, b->lds, b->stream, &p1));
+        HIP_TRY(kernel_launch(b, k, tr, grid_main, b->lds, b->stream, &p1));
         if ((b->mode & BA_TRACE) && bp.cig_ops) {
             BatchParams pw = bp; pw.work_counter = b->counter.as<uint32_t>() + 16;   // (its own counters, zeroed with the others: the side launch may still be counting)
             if (special_of(b->mode)) HIP_TRY(ba_launch_walk_loc(b->stream, &pw, walk_grid(b)));   // (records with the zero-mask bits, the early stops)
@@ -1340,13 +1287,13 @@ static int batch_launch(BaBatch* b) {
         if (side_n) HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_join, 0));
     } else if (b->pipe) {   // pair-slot batch: the fill stacks, k_walk walks
         BatchParams p1 = bp; p1.cig_ops = nullptr; p1.inline_len2 = ~0u;
-        HIP_TRY(launch(1, (b->mode & BA_X_DROP) != 0, b->grid, b->lds, b->stream, &p1));
+        HIP_TRY(kernel_launch(b, k, true, b->grid, b->lds, b->stream, &p1));
         if (bp.cig_ops) {
             HIP_TRY(hipMemsetAsync(b->counter.p, 0, 64, b->stream));
             HIP_TRY(ba_launch_walk(b->stream, &bp, walk_grid(b)));
         }
     } else
-    HIP_TRY(launch((b->mode & BA_TRACE) != 0, (b->mode & BA_X_DROP) != 0, b->grid, b->lds, b->stream, &bp));
+    HIP_TRY(kernel_launch(b, k, tr, b->grid, b->lds, b->stream, &bp));
     HIP_TRY(hipEventRecord(b->ev1, b->stream));
     b->in_flight = true;
     return 0;
@@ -1982,6 +1929,12 @@ int ba_dev_lane_scan(int form, const int16_t* x, uint32_t n_cells, int gap_exten
     HIP_TRY(hipMemcpy(out, dout.p, (size_t)n_cells * 2, hipMemcpyDeviceToHost));
     return 0;
 }
+// ... and the kernel catalogue (tests/test_kernel_catalogue.py): the forms -- 0: there is no such kernel -- that the library holds of a family
+// (ba::KernelFamily) for a matrix kind, a block class (0 .. 4: 128 << class cells, 5: row-tiled) and the plain / special modes. Launches nothing.
+int ba_dev_kernel_forms(int family, int kind, int pclass, int special) {
+    const ba::KernelEntry* k = find_kernel(family, kind, pclass, special);
+    return !k ? 0 : (k->fn[1][0][0] ? 2 : 1);
+}
 #endif
 int ba_batch_prof(BaBatch* b, uint64_t out[128]) {   // development: phase timers of a -DBA_TIMING build (all per-pair launches of a batch add up)
     if (!b) return fail("null batch");
@@ -2003,7 +1956,12 @@ int ba_batch_spec_cells(BaBatch* b, uint64_t* cells) {
     HIP_TRY(hipMemcpy(cells, (const char*)b->prof.p + 60 * 8, 8, hipMemcpyDeviceToHost));
     return 0;
 }
-int ba_batch_kernel(BaBatch* b) { return !b ? -1 : (b->small ? 3 : (b->quad ? 2 : (b->multi ? 1 : 0))); }
+int ba_batch_kernel(BaBatch* b) {   // 0 the per-pair kernel (row-tiled class included), 1 k_multi, 2 k_quad beside it, 3 k_small
+    if (!b) return -1;
+    if (b->quad) return 2;
+    const ba::KernelFamily f = family_of(b);
+    return f == ba::FAM_SMALL ? 3 : ((f == ba::FAM_PAIR || f == ba::FAM_TILED) ? 0 : 1);
+}
 int ba_batch_geometry(BaBatch* b) { return !b ? -1 : (int)b->geom; }
 int ba_batch_retried(BaBatch* b) { return b ? (int)b->retried : -1; }
 int ba_batch_stats(BaBatch* b, BaAlignStats* out) {

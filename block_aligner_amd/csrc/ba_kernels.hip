@@ -2,6 +2,7 @@
 // BA_PMAX = max block size / 128 (packed VGPRs per border array per lane); a smaller class keeps the kernel's VGPR
 // budget (and so its occupancy) matched to the batch's max block size.
 #include "ba_driver.hpp"
+#include "ba_launch.h"
 
 #ifndef BA_KIND
 #error "define BA_KIND"
@@ -14,323 +15,74 @@
 #define BA_SPECIAL 0   // 1: the kernels of this TU handle LOCAL_START / FREE_QUERY_START_GAPS / FREE_QUERY_END_GAPS batches
 #endif
 
-#define BA_CAT_(a, b, c, d) a##b##c##d
-#define BA_CAT(a, b, c, d) BA_CAT_(a, b, c, d)
-#if BA_BIG && BA_SPECIAL   // blocks of 4096 .. 32768 cells with LOCAL_START / FREE_QUERY_*_GAPS
-#define BA_LAUNCH BA_CAT(ba_launch_bigs_k, BA_KIND, _p, BA_PMAX)
-#define BA_OCC BA_CAT(ba_occupancy_bigs_k, BA_KIND, _p, BA_PMAX)
-#elif BA_BIG   // blocks of 4096 .. 32768 cells (one class per kind)
-#define BA_LAUNCH BA_CAT(ba_launch_big_k, BA_KIND, _p, BA_PMAX)
-#define BA_OCC BA_CAT(ba_occupancy_big_k, BA_KIND, _p, BA_PMAX)
-#elif BA_SPECIAL
-#define BA_LAUNCH BA_CAT(ba_launch_s_k, BA_KIND, _p, BA_PMAX)
-#define BA_OCC BA_CAT(ba_occupancy_s_k, BA_KIND, _p, BA_PMAX)
-#else
-#define BA_LAUNCH BA_CAT(ba_launch_k, BA_KIND, _p, BA_PMAX)
-#define BA_OCC BA_CAT(ba_occupancy_k, BA_KIND, _p, BA_PMAX)
+#if !BA_BIG && (BA_KIND != 3 || (!BA_SPECIAL && BA_PMAX <= 8))
+#include "ba_multi.hpp"   // (kind 3: k_small's column code builds on multi_rect's helpers; k_multi itself has no profile form)
+#endif
+#if !BA_BIG && BA_PMAX <= 8 && (BA_KIND != 3 || !BA_SPECIAL)
+#include "ba_small.hpp"
+#endif
+#if !BA_BIG && BA_PMAX == 1 && !BA_SPECIAL
+#include "ba_quad.hpp"
 #endif
 
-template <bool TRACE, bool XDROP>
-static hipError_t launch1(unsigned grid, unsigned lds, hipStream_t s, const ba::BatchParams& bp) {
-    if (lds > 64 * 1024) {   // more than the default dynamic-LDS limit: opt in (160 KB per CU on gfx950)
-        hipError_t e = hipFuncSetAttribute((const void*)ba::k_align<BA_PMAX, BA_KIND, TRACE, XDROP, (BA_SPECIAL != 0)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    ba::k_align<BA_PMAX, BA_KIND, TRACE, XDROP, (BA_SPECIAL != 0)><<<dim3(grid), dim3(ba::WAVES_PER_WG * 64), lds, s>>>(bp);
-    return hipGetLastError();
-}
-template <bool TRACE, bool XDROP>
-static hipError_t occ1(int* blocks_per_cu, unsigned lds) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)ba::k_align<BA_PMAX, BA_KIND, TRACE, XDROP, (BA_SPECIAL != 0)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, ba::k_align<BA_PMAX, BA_KIND, TRACE, XDROP, (BA_SPECIAL != 0)>, ba::WAVES_PER_WG * 64, lds);
-}
+// The catalogue entries of this unit (ba_launch.h): the only place that names a kernel's template arguments and its workgroup size.
+// K(T, X) is a family's instantiation with / without traceback and X-drop.
+#define K_ALIGN(T, X) ba::k_align<BA_PMAX, BA_KIND, T, X, (BA_SPECIAL != 0)>
+#define K_MULTI(T, X) ba::k_multi<BA_PMAX, BA_KIND, T, X>
+#define K_MULTI_256(T, X) ba::k_multi<BA_PMAX, BA_KIND, T, X, 0, 256>
+#define K_MULTI_512(T, X) ba::k_multi<BA_PMAX, BA_KIND, T, X, 0, 512>
+#define K_MULTI_G2(T, X) ba::k_multi<BA_PMAX, BA_KIND, T, X, 0, 128, ba::MQ_GEOM_WPW, 2>
+#define K_MULTI_G3(T, X) ba::k_multi<BA_PMAX, BA_KIND, T, X, 0, 128, ba::MQ_GEOM_WPW, 3>
+#define K_MULTI_S1(T, X) ba::k_multi<BA_PMAX, BA_KIND, T, X, 1>
+#define K_MULTI_S2(T, X) ba::k_multi<BA_PMAX, BA_KIND, T, X, 2>
+#define K_SMALL(T, X) ba::k_small<BA_PMAX, BA_KIND, T, X>
+#define K_SMALL_S1(T, X) ba::k_small<BA_PMAX, BA_KIND, T, X, 1>
+#define K_SMALL_S2(T, X) ba::k_small<BA_PMAX, BA_KIND, T, X, 2>
+#define K_QUAD(T, X) ba::k_quad<BA_KIND, T, X>
+#define BA_TX(K) {{(const void*)K(false, false), (const void*)K(false, true)}, {(const void*)K(true, false), (const void*)K(true, true)}}
+#define BA_ENTRY(FAM, WPW, K) {FAM, WPW, 0u, {BA_TX(K), {}}}
+#define BA_ENTRY_SPM(FAM, WPW, K1, K2) {FAM, WPW, 0u, {BA_TX(K1), BA_TX(K2)}}   // (the batch's flags choose: spm 1 LOCAL_START, spm 2 FREE_QUERY_START_GAPS)
 
-extern "C" hipError_t BA_LAUNCH(int trace, int xdrop, unsigned grid, unsigned lds, hipStream_t s, const ba::BatchParams* bp) {
-    if (trace) return xdrop ? launch1<true, true>(grid, lds, s, *bp) : launch1<true, false>(grid, lds, s, *bp);
-    return xdrop ? launch1<false, true>(grid, lds, s, *bp) : launch1<false, false>(grid, lds, s, *bp);
-}
-extern "C" hipError_t BA_OCC(int trace, int xdrop, unsigned lds, int* blocks_per_cu) {
-    if (trace) return xdrop ? occ1<true, true>(blocks_per_cu, lds) : occ1<true, false>(blocks_per_cu, lds);
-    return xdrop ? occ1<false, true>(blocks_per_cu, lds) : occ1<false, false>(blocks_per_cu, lds);
-}
-
+static const ba::KernelEntry g_entries[] = {
+    BA_ENTRY(BA_BIG ? ba::FAM_TILED : ba::FAM_PAIR, ba::WAVES_PER_WG, K_ALIGN),
 #if BA_KIND != 3 && !BA_SPECIAL && !BA_BIG
-// four pairs per wave while the block is 128 cells, everything else by the same wave on all its lanes (ba_multi.hpp): one kernel per
-// kind and block class
-#include "ba_multi.hpp"
-template <bool TRACE, bool XDROP>
-static hipError_t launch_multi(unsigned grid, unsigned lds, hipStream_t s, const ba::BatchParams& bp) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)ba::k_multi<BA_PMAX, BA_KIND, TRACE, XDROP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    ba::k_multi<BA_PMAX, BA_KIND, TRACE, XDROP><<<dim3(grid), dim3(ba::WAVES_PER_WG * 64), lds, s>>>(bp);
-    return hipGetLastError();
-}
-template <bool TRACE, bool XDROP>
-static hipError_t occ_multi(int* blocks_per_cu, unsigned lds) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)ba::k_multi<BA_PMAX, BA_KIND, TRACE, XDROP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, ba::k_multi<BA_PMAX, BA_KIND, TRACE, XDROP>, ba::WAVES_PER_WG * 64, lds);
-}
-extern "C" hipError_t BA_CAT(ba_launch_m_k, BA_KIND, _p, BA_PMAX)(int trace, int xdrop, unsigned grid, unsigned lds, hipStream_t s, const ba::BatchParams* bp) {
-    if (trace) return xdrop ? launch_multi<true, true>(grid, lds, s, *bp) : launch_multi<true, false>(grid, lds, s, *bp);
-    return xdrop ? launch_multi<false, true>(grid, lds, s, *bp) : launch_multi<false, false>(grid, lds, s, *bp);
-}
-extern "C" hipError_t BA_CAT(ba_occupancy_m_k, BA_KIND, _p, BA_PMAX)(int trace, int xdrop, unsigned lds, int* blocks_per_cu) {
-    if (trace) return xdrop ? occ_multi<true, true>(blocks_per_cu, lds) : occ_multi<true, false>(blocks_per_cu, lds);
-    return xdrop ? occ_multi<false, true>(blocks_per_cu, lds) : occ_multi<false, false>(blocks_per_cu, lds);
-}
+    // four pairs per wave while the block is 128 cells, everything else by the same wave on all its lanes (ba_multi.hpp): one kernel per
+    // kind and block class
+    BA_ENTRY(ba::FAM_MULTI, ba::WAVES_PER_WG, K_MULTI),
 #if BA_KIND == 1 && BA_PMAX >= 4
-// ... with two slots of 256 cells per wave (round 6: DNA batches that start at 256 cells, block classes 512 .. 2048)
-template <bool TRACE, bool XDROP>
-static hipError_t launch_multi256(unsigned grid, unsigned lds, hipStream_t s, const ba::BatchParams& bp) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)ba::k_multi<BA_PMAX, BA_KIND, TRACE, XDROP, 0, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    ba::k_multi<BA_PMAX, BA_KIND, TRACE, XDROP, 0, 256><<<dim3(grid), dim3(ba::WAVES_PER_WG * 64), lds, s>>>(bp);
-    return hipGetLastError();
-}
-template <bool TRACE, bool XDROP>
-static hipError_t occ_multi256(int* blocks_per_cu, unsigned lds) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)ba::k_multi<BA_PMAX, BA_KIND, TRACE, XDROP, 0, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, ba::k_multi<BA_PMAX, BA_KIND, TRACE, XDROP, 0, 256>, ba::WAVES_PER_WG * 64, lds);
-}
-extern "C" hipError_t BA_CAT(ba_launch_m256_k, BA_KIND, _p, BA_PMAX)(int trace, int xdrop, unsigned grid, unsigned lds, hipStream_t s, const ba::BatchParams* bp) {
-    if (trace) return xdrop ? launch_multi256<true, true>(grid, lds, s, *bp) : launch_multi256<true, false>(grid, lds, s, *bp);
-    return xdrop ? launch_multi256<false, true>(grid, lds, s, *bp) : launch_multi256<false, false>(grid, lds, s, *bp);
-}
-extern "C" hipError_t BA_CAT(ba_occupancy_m256_k, BA_KIND, _p, BA_PMAX)(int trace, int xdrop, unsigned lds, int* blocks_per_cu) {
-    if (trace) return xdrop ? occ_multi256<true, true>(blocks_per_cu, lds) : occ_multi256<true, false>(blocks_per_cu, lds);
-    return xdrop ? occ_multi256<false, true>(blocks_per_cu, lds) : occ_multi256<false, false>(blocks_per_cu, lds);
-}
+    // ... with two slots of 256 cells per wave (round 6: DNA batches that start at 256 cells, block classes 512 .. 2048)
+    BA_ENTRY(ba::FAM_MULTI_256, ba::WAVES_PER_WG, K_MULTI_256),
 #endif
 #if BA_KIND == 1 && BA_PMAX >= 8
-// ... with one slot of 512 cells per wave (round 6: DNA batches that start at 512 cells -- percent_len 1 % of reads above 25.6 kbp --, block classes 1024 and 2048)
-template <bool TRACE, bool XDROP>
-static hipError_t launch_multi512(unsigned grid, unsigned lds, hipStream_t s, const ba::BatchParams& bp) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)ba::k_multi<BA_PMAX, BA_KIND, TRACE, XDROP, 0, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    ba::k_multi<BA_PMAX, BA_KIND, TRACE, XDROP, 0, 512><<<dim3(grid), dim3(ba::WAVES_PER_WG * 64), lds, s>>>(bp);
-    return hipGetLastError();
-}
-template <bool TRACE, bool XDROP>
-static hipError_t occ_multi512(int* blocks_per_cu, unsigned lds) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)ba::k_multi<BA_PMAX, BA_KIND, TRACE, XDROP, 0, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, ba::k_multi<BA_PMAX, BA_KIND, TRACE, XDROP, 0, 512>, ba::WAVES_PER_WG * 64, lds);
-}
-extern "C" hipError_t BA_CAT(ba_launch_m512_k, BA_KIND, _p, BA_PMAX)(int trace, int xdrop, unsigned grid, unsigned lds, hipStream_t s, const ba::BatchParams* bp) {
-    if (trace) return xdrop ? launch_multi512<true, true>(grid, lds, s, *bp) : launch_multi512<true, false>(grid, lds, s, *bp);
-    return xdrop ? launch_multi512<false, true>(grid, lds, s, *bp) : launch_multi512<false, false>(grid, lds, s, *bp);
-}
-extern "C" hipError_t BA_CAT(ba_occupancy_m512_k, BA_KIND, _p, BA_PMAX)(int trace, int xdrop, unsigned lds, int* blocks_per_cu) {
-    if (trace) return xdrop ? occ_multi512<true, true>(blocks_per_cu, lds) : occ_multi512<true, false>(blocks_per_cu, lds);
-    return xdrop ? occ_multi512<false, true>(blocks_per_cu, lds) : occ_multi512<false, false>(blocks_per_cu, lds);
-}
+    // ... with one slot of 512 cells per wave (round 6: DNA batches that start at 512 cells -- percent_len 1 % of reads above 25.6 kbp --, block classes 1024 and 2048)
+    BA_ENTRY(ba::FAM_MULTI_512, ba::WAVES_PER_WG, K_MULTI_512),
 #endif
 #if BA_KIND == 1 && (BA_PMAX == 4 || BA_PMAX == 8)
-// ... in workgroups of four waves at three / two waves per SIMD (round 6: DNA batches whose pairs fill that many waves' slots about once -- ba_host.cpp batch_build)
-template <bool TRACE, bool XDROP, int EU>
-static hipError_t launch_multi_g(unsigned grid, unsigned lds, hipStream_t s, const ba::BatchParams& bp) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)ba::k_multi<BA_PMAX, BA_KIND, TRACE, XDROP, 0, 128, ba::MQ_GEOM_WPW, EU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    ba::k_multi<BA_PMAX, BA_KIND, TRACE, XDROP, 0, 128, ba::MQ_GEOM_WPW, EU><<<dim3(grid), dim3(ba::MQ_GEOM_WPW * 64), lds, s>>>(bp);
-    return hipGetLastError();
-}
-template <bool TRACE, bool XDROP, int EU>
-static hipError_t occ_multi_g(int* blocks_per_cu, unsigned lds) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)ba::k_multi<BA_PMAX, BA_KIND, TRACE, XDROP, 0, 128, ba::MQ_GEOM_WPW, EU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, ba::k_multi<BA_PMAX, BA_KIND, TRACE, XDROP, 0, 128, ba::MQ_GEOM_WPW, EU>, ba::MQ_GEOM_WPW * 64, lds);
-}
-#define BA_MULTI_GEOM(EU)                                                                                                                                              \
-    extern "C" hipError_t BA_CAT(ba_launch_mg##EU##_k, BA_KIND, _p, BA_PMAX)(int trace, int xdrop, unsigned grid, unsigned lds, hipStream_t s, const ba::BatchParams* bp) { \
-        if (trace) return xdrop ? launch_multi_g<true, true, EU>(grid, lds, s, *bp) : launch_multi_g<true, false, EU>(grid, lds, s, *bp);                              \
-        return xdrop ? launch_multi_g<false, true, EU>(grid, lds, s, *bp) : launch_multi_g<false, false, EU>(grid, lds, s, *bp);                                       \
-    }                                                                                                                                                                  \
-    extern "C" hipError_t BA_CAT(ba_occupancy_mg##EU##_k, BA_KIND, _p, BA_PMAX)(int trace, int xdrop, unsigned lds, int* blocks_per_cu) {                               \
-        if (trace) return xdrop ? occ_multi_g<true, true, EU>(blocks_per_cu, lds) : occ_multi_g<true, false, EU>(blocks_per_cu, lds);                                  \
-        return xdrop ? occ_multi_g<false, true, EU>(blocks_per_cu, lds) : occ_multi_g<false, false, EU>(blocks_per_cu, lds);                                           \
-    }
-BA_MULTI_GEOM(3)
-BA_MULTI_GEOM(2)
-#undef BA_MULTI_GEOM
+    // ... in workgroups of four waves at three / two waves per SIMD (round 6: DNA batches whose pairs fill that many waves' slots about once -- ba_host.cpp batch_build)
+    BA_ENTRY(ba::FAM_MULTI_G3, ba::MQ_GEOM_WPW, K_MULTI_G3),
+    BA_ENTRY(ba::FAM_MULTI_G2, ba::MQ_GEOM_WPW, K_MULTI_G2),
 #endif
 #endif
-
 #if !BA_SPECIAL && !BA_BIG && BA_PMAX <= 8
-#if BA_KIND == 3
-#include "ba_multi.hpp"   // (k_small's column code builds on multi_rect's helpers; k_multi itself has no profile form)
+    // sixteen pairs per wave while the block is 32 cells, everything else by the same wave on all its lanes (ba_small.hpp): one kernel per
+    // kind and block class (up to 1024 cells: the solo driver's LDS borders fit in the slots' region)
+    BA_ENTRY(ba::FAM_SMALL, ba::WAVES_PER_WG, K_SMALL),
 #endif
-// sixteen pairs per wave while the block is 32 cells, everything else by the same wave on all its lanes (ba_small.hpp): one kernel per
-// kind and block class (up to 1024 cells: the solo driver's LDS borders fit in the slots' region)
-#include "ba_small.hpp"
-template <bool TRACE, bool XDROP>
-static hipError_t launch_small(unsigned grid, unsigned lds, hipStream_t s, const ba::BatchParams& bp) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)ba::k_small<BA_PMAX, BA_KIND, TRACE, XDROP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    ba::k_small<BA_PMAX, BA_KIND, TRACE, XDROP><<<dim3(grid), dim3(ba::WAVES_PER_WG * 64), lds, s>>>(bp);
-    return hipGetLastError();
-}
-template <bool TRACE, bool XDROP>
-static hipError_t occ_small(int* blocks_per_cu, unsigned lds) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)ba::k_small<BA_PMAX, BA_KIND, TRACE, XDROP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, ba::k_small<BA_PMAX, BA_KIND, TRACE, XDROP>, ba::WAVES_PER_WG * 64, lds);
-}
-extern "C" hipError_t BA_CAT(ba_launch_sm_k, BA_KIND, _p, BA_PMAX)(int trace, int xdrop, unsigned grid, unsigned lds, hipStream_t s, const ba::BatchParams* bp) {
-    if (trace) return xdrop ? launch_small<true, true>(grid, lds, s, *bp) : launch_small<true, false>(grid, lds, s, *bp);
-    return xdrop ? launch_small<false, true>(grid, lds, s, *bp) : launch_small<false, false>(grid, lds, s, *bp);
-}
-extern "C" hipError_t BA_CAT(ba_occupancy_sm_k, BA_KIND, _p, BA_PMAX)(int trace, int xdrop, unsigned lds, int* blocks_per_cu) {
-    if (trace) return xdrop ? occ_small<true, true>(blocks_per_cu, lds) : occ_small<true, false>(blocks_per_cu, lds);
-    return xdrop ? occ_small<false, true>(blocks_per_cu, lds) : occ_small<false, false>(blocks_per_cu, lds);
-}
-#endif
-
 #if BA_SPECIAL && !BA_BIG && BA_KIND != 3
-// k_multi for LOCAL_START (spm 1) / FREE_QUERY_START_GAPS (spm 2) batches of the sequence kinds: the slots take these modes' plain steps too
-// (FREE_QUERY_END_GAPS batches stay with the per-pair kernel: the mode's running column maxima are not a slot's)
-#include "ba_multi.hpp"
-template <bool TRACE, bool XDROP, int SPM>
-static hipError_t launch_multi_s(unsigned grid, unsigned lds, hipStream_t s, const ba::BatchParams& bp) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)ba::k_multi<BA_PMAX, BA_KIND, TRACE, XDROP, SPM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    ba::k_multi<BA_PMAX, BA_KIND, TRACE, XDROP, SPM><<<dim3(grid), dim3(ba::WAVES_PER_WG * 64), lds, s>>>(bp);
-    return hipGetLastError();
-}
-template <bool TRACE, bool XDROP, int SPM>
-static hipError_t occ_multi_s(int* blocks_per_cu, unsigned lds) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)ba::k_multi<BA_PMAX, BA_KIND, TRACE, XDROP, SPM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, ba::k_multi<BA_PMAX, BA_KIND, TRACE, XDROP, SPM>, ba::WAVES_PER_WG * 64, lds);
-}
-template <int SPM>
-static hipError_t launch_multi_m(int trace, int xdrop, unsigned grid, unsigned lds, hipStream_t s, const ba::BatchParams& bp) {
-    if (trace) return xdrop ? launch_multi_s<true, true, SPM>(grid, lds, s, bp) : launch_multi_s<true, false, SPM>(grid, lds, s, bp);
-    return xdrop ? launch_multi_s<false, true, SPM>(grid, lds, s, bp) : launch_multi_s<false, false, SPM>(grid, lds, s, bp);
-}
-template <int SPM>
-static hipError_t occ_multi_m(int trace, int xdrop, unsigned lds, int* blocks_per_cu) {
-    if (trace) return xdrop ? occ_multi_s<true, true, SPM>(blocks_per_cu, lds) : occ_multi_s<true, false, SPM>(blocks_per_cu, lds);
-    return xdrop ? occ_multi_s<false, true, SPM>(blocks_per_cu, lds) : occ_multi_s<false, false, SPM>(blocks_per_cu, lds);
-}
-// (the batch's flags choose the instantiation)
-extern "C" hipError_t BA_CAT(ba_launch_ms_k, BA_KIND, _p, BA_PMAX)(int trace, int xdrop, unsigned grid, unsigned lds, hipStream_t s, const ba::BatchParams* bp) {
-    return (bp->flags & ba::F_LOCAL) ? launch_multi_m<1>(trace, xdrop, grid, lds, s, *bp) : launch_multi_m<2>(trace, xdrop, grid, lds, s, *bp);
-}
-extern "C" hipError_t BA_CAT(ba_occupancy_ms_k, BA_KIND, _p, BA_PMAX)(int trace, int xdrop, unsigned lds, int* blocks_per_cu) {
-    int a = 0, b = 0;   // (one launch geometry for both)
-    hipError_t e = occ_multi_m<1>(trace, xdrop, lds, &a);
-    if (e != hipSuccess) return e;
-    e = occ_multi_m<2>(trace, xdrop, lds, &b);
-    *blocks_per_cu = a < b ? a : b;
-    return e;
-}
+    // k_multi for LOCAL_START / FREE_QUERY_START_GAPS batches of the sequence kinds: the slots take these modes' plain steps too
+    // (FREE_QUERY_END_GAPS batches stay with the per-pair kernel: the mode's running column maxima are not a slot's)
+    BA_ENTRY_SPM(ba::FAM_MULTI, ba::WAVES_PER_WG, K_MULTI_S1, K_MULTI_S2),
 #endif
-
 #if BA_SPECIAL && !BA_BIG && BA_PMAX <= 8 && BA_KIND != 3
-// ... and k_small for the same two modes
-#include "ba_small.hpp"
-template <bool TRACE, bool XDROP, int SPM>
-static hipError_t launch_small_s(unsigned grid, unsigned lds, hipStream_t s, const ba::BatchParams& bp) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)ba::k_small<BA_PMAX, BA_KIND, TRACE, XDROP, SPM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    ba::k_small<BA_PMAX, BA_KIND, TRACE, XDROP, SPM><<<dim3(grid), dim3(ba::WAVES_PER_WG * 64), lds, s>>>(bp);
-    return hipGetLastError();
-}
-template <bool TRACE, bool XDROP, int SPM>
-static hipError_t occ_small_s(int* blocks_per_cu, unsigned lds) {
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)ba::k_small<BA_PMAX, BA_KIND, TRACE, XDROP, SPM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, ba::k_small<BA_PMAX, BA_KIND, TRACE, XDROP, SPM>, ba::WAVES_PER_WG * 64, lds);
-}
-template <int SPM>
-static hipError_t launch_small_m(int trace, int xdrop, unsigned grid, unsigned lds, hipStream_t s, const ba::BatchParams& bp) {
-    if (trace) return xdrop ? launch_small_s<true, true, SPM>(grid, lds, s, bp) : launch_small_s<true, false, SPM>(grid, lds, s, bp);
-    return xdrop ? launch_small_s<false, true, SPM>(grid, lds, s, bp) : launch_small_s<false, false, SPM>(grid, lds, s, bp);
-}
-template <int SPM>
-static hipError_t occ_small_m(int trace, int xdrop, unsigned lds, int* blocks_per_cu) {
-    if (trace) return xdrop ? occ_small_s<true, true, SPM>(blocks_per_cu, lds) : occ_small_s<true, false, SPM>(blocks_per_cu, lds);
-    return xdrop ? occ_small_s<false, true, SPM>(blocks_per_cu, lds) : occ_small_s<false, false, SPM>(blocks_per_cu, lds);
-}
-// (the batch's flags choose the instantiation)
-extern "C" hipError_t BA_CAT(ba_launch_sms_k, BA_KIND, _p, BA_PMAX)(int trace, int xdrop, unsigned grid, unsigned lds, hipStream_t s, const ba::BatchParams* bp) {
-    return (bp->flags & ba::F_LOCAL) ? launch_small_m<1>(trace, xdrop, grid, lds, s, *bp) : launch_small_m<2>(trace, xdrop, grid, lds, s, *bp);
-}
-extern "C" hipError_t BA_CAT(ba_occupancy_sms_k, BA_KIND, _p, BA_PMAX)(int trace, int xdrop, unsigned lds, int* blocks_per_cu) {
-    int a = 0, b = 0;   // (one launch geometry for both)
-    hipError_t e = occ_small_m<1>(trace, xdrop, lds, &a);
-    if (e != hipSuccess) return e;
-    e = occ_small_m<2>(trace, xdrop, lds, &b);
-    *blocks_per_cu = a < b ? a : b;
-    return e;
-}
+    // ... and k_small for the same two modes
+    BA_ENTRY_SPM(ba::FAM_SMALL, ba::WAVES_PER_WG, K_SMALL_S1, K_SMALL_S2),
 #endif
-
 #if BA_PMAX == 1 && !BA_SPECIAL && !BA_BIG
-// four pairs per wave while the block is 32 cells (ba_quad.hpp): one kernel per kind
-#include "ba_quad.hpp"
-template <bool TRACE, bool XDROP>
-static hipError_t quad_grid(unsigned* grid) {
-    const unsigned lds = ba::lds_table_bytes_h(BA_KIND) + ba::WAVES_PER_WG * 4 * ba::QUAD_SLOT_BYTES;
-    int per_cu = 0, dev = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ba::k_quad<BA_KIND, TRACE, XDROP>, ba::WAVES_PER_WG * 64, lds);
-    if (e != hipSuccess) return e;
-    hipDeviceProp_t prop;
-    if ((e = hipGetDevice(&dev)) != hipSuccess || (e = hipGetDeviceProperties(&prop, dev)) != hipSuccess) return e;
-    if (per_cu < 1) per_cu = 1;
-    if (per_cu * ba::WAVES_PER_WG > 32) per_cu = 32 / ba::WAVES_PER_WG;
-    *grid = (unsigned)(prop.multiProcessorCount * per_cu);
-    return hipSuccess;
-}
-template <bool TRACE, bool XDROP>
-static hipError_t launch_quad(unsigned grid, hipStream_t s, const ba::BatchParams& bp) {
-    const unsigned lds = ba::lds_table_bytes_h(BA_KIND) + ba::WAVES_PER_WG * 4 * ba::QUAD_SLOT_BYTES;
-    ba::k_quad<BA_KIND, TRACE, XDROP><<<dim3(grid), dim3(ba::WAVES_PER_WG * 64), lds, s>>>(bp);
-    return hipGetLastError();
-}
-// grid: workgroups, from ba_quad_grid_k* (bp->cq_producers must be grid * WAVES_PER_WG)
-extern "C" hipError_t BA_CAT(ba_launch_quad_k, BA_KIND, , )(int trace, int xdrop, unsigned grid, hipStream_t s, const ba::BatchParams* bp) {
-    if (trace) return xdrop ? launch_quad<true, true>(grid, s, *bp) : launch_quad<true, false>(grid, s, *bp);
-    return xdrop ? launch_quad<false, true>(grid, s, *bp) : launch_quad<false, false>(grid, s, *bp);
-}
-extern "C" hipError_t BA_CAT(ba_quad_grid_k, BA_KIND, , )(int trace, int xdrop, unsigned* grid) {
-    if (trace) return xdrop ? quad_grid<true, true>(grid) : quad_grid<true, false>(grid);
-    return xdrop ? quad_grid<false, true>(grid) : quad_grid<false, false>(grid);
-}
+    // four pairs per wave while the block is 32 cells (ba_quad.hpp): one kernel per kind, its LDS fixed
+    {ba::FAM_QUAD, ba::WAVES_PER_WG, ba::lds_table_bytes_h(BA_KIND) + ba::WAVES_PER_WG * 4 * ba::QUAD_SLOT_BYTES, {BA_TX(K_QUAD), {}}},
 #endif
+};
+[[maybe_unused]] static const int g_registered = ba::register_kernels(BA_KIND, BA_PMAX, BA_SPECIAL != 0, g_entries, (int)(sizeof g_entries / sizeof g_entries[0]));
 
 #if BA_KIND == 0 && BA_PMAX == 1 && !BA_SPECIAL && !BA_BIG
 // kernels that exist once

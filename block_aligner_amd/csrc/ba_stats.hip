@@ -2,8 +2,7 @@
 // batch's CIGAR runs and sequence images where the fill left them. No fill kernel is touched.
 #include <hip/hip_runtime.h>
 
-#include "ba_extend.h"
-#include "ba_stats.h"
+#include "ba_launch.h"
 
 namespace {
 

@@ -3,7 +3,7 @@
 // caller's order, k_text_write renders. No fill kernel is touched.
 #include <hip/hip_runtime.h>
 
-#include "ba_text.h"
+#include "ba_launch.h"
 
 namespace {
 
