@@ -244,6 +244,11 @@ struct BaBatch {
     DevBuf stats, stats_pos;
     hipEvent_t ev_s0 = nullptr, ev_s1 = nullptr;
     float stats_ms = 0;
+    // exact full-matrix scores (ba_batch_exact): the waves' row buffers, the sorted request, its records and one work counter per launch,
+    // allocated on the first call (they grow, never shrink); time and cells of the last call
+    DevBuf ex_rows, ex_work, ex_out, ex_counter;
+    hipEvent_t ev_x0 = nullptr, ev_x1 = nullptr;
+    float exact_ms = 0; uint64_t exact_cells = 0;
     TextState text;          // alignment strings (ba_batch_text)
     uint64_t runs_done = 0;  // finished runs: what the text sizes are kept for
     uint64_t compact_cap = 0, compact_used_cap = 0; bool compacted = false; uint32_t* compact_host = nullptr;
@@ -290,6 +295,8 @@ struct BaBatch {
         if (ev_m1) (void)hipEventDestroy(ev_m1);
         if (ev_s0) (void)hipEventDestroy(ev_s0);
         if (ev_s1) (void)hipEventDestroy(ev_s1);
+        if (ev_x0) (void)hipEventDestroy(ev_x0);
+        if (ev_x1) (void)hipEventDestroy(ev_x1);
         if (stream2) (void)hipStreamDestroy(stream2);
         if (stream) (void)hipStreamDestroy(stream);
     }
@@ -1663,6 +1670,144 @@ static int batch_stats_device(BaBatch* b, bool caller_order) {
     return 0;
 }
 
+// ------------------------------------------------------------------ exact full-matrix scores (ba_*_exact)
+// k_exact (ba_exact.hip) over the images, matrix and gaps of a batch: no run is needed and none is read. The request is a list of device
+// positions (EXACT_NO_PAIR: an all-zero record); it is sorted by |q| * |r|, largest first, and cut into launches of at most
+// EXACT_LAUNCH_CELLS cells -- or of one pair per wave of the device, if that is more --, so that no single kernel holds the device for long
+// ("Exact scores"). Every launch is persistent: 16 waves per CU at most, one pair per wave at a time.
+static_assert(sizeof(BaExact) == sizeof(ba::Exact) && offsetof(BaExact, reference_idx) == offsetof(ba::Exact, reference_idx) &&
+              offsetof(BaExact, rows) == offsetof(ba::Exact, rows), "BaExact and ba::Exact differ");
+constexpr uint64_t EXACT_LAUNCH_CELLS = 1ull << 36;
+constexpr uint32_t EXACT_WAVES_PER_CU = 16;
+static int exact_check_lengths(const uint32_t* ql, const uint32_t* rl, size_t n, const uint32_t* name) {
+    for (size_t p = 0; p < n; p++)
+        if ((uint64_t)ql[p] + rl[p] > ba::EXACT_MAX_LEN2)
+            return fail("exact: pair %zu (|q| = %u, |r| = %u) is too long for int32 scores: |q| + |r| may be %llu at most", name ? (size_t)name[p] : p,
+                        ql[p], rl[p], (unsigned long long)ba::EXACT_MAX_LEN2);
+    return 0;
+}
+static int exact_refusals(const BaBatch* b, uint32_t what, const void* out) {
+    if (!out) return fail("null argument: out");
+    if (what != BA_EXACT_GLOBAL && what != BA_EXACT_EXTEND) return fail("exact: unknown quantity %u (BA_EXACT_GLOBAL or BA_EXACT_EXTEND)", what);
+    if (b->kind == BA_KIND_PROFILE_) return fail("exact: profile batches are not supported (position-specific gap costs)");
+    if (special_of(b->mode)) return fail("exact: batches with BA_LOCAL_START or BA_FREE_QUERY_* are not supported");
+    if (b->handle_mode) return fail("exact: not a batch");
+    if (b->in_flight) return fail("exact: the batch has a launch in flight (ba_batch_wait first)");
+    if (!b->n) return fail("exact: the batch holds no pairs (a reload failed)");
+    return 0;
+}
+static int batch_exact_device(BaBatch* b, uint32_t what, int32_t x_drop, const uint32_t* devpos, size_t m, BaExact* out) {
+    if (exact_refusals(b, what, out)) return 1;
+    b->exact_ms = 0; b->exact_cells = 0;
+    if (!m) return 0;
+    if (m > 0x7fffffffu) return fail("exact: too many records in one request");
+    HIP_TRY(hipSetDevice(b->device));
+    std::vector<uint32_t> ql(b->n), rl(b->n);
+    HIP_TRY(hipMemcpy(ql.data(), b->q_len.p, (size_t)b->n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rl.data(), b->r_len.p, (size_t)b->n * 4, hipMemcpyDeviceToHost));
+    if (exact_check_lengths(ql.data(), rl.data(), b->n, b->h_order.empty() ? nullptr : b->h_order.data())) return 1;
+    auto cost = [&](uint32_t k) { const uint32_t d = devpos[k]; return d == ba::EXACT_NO_PAIR ? 0ull : (uint64_t)ql[d] * rl[d]; };
+    std::vector<uint32_t> rec(m);
+    for (size_t k = 0; k < m; k++) rec[k] = (uint32_t)k;
+    std::stable_sort(rec.begin(), rec.end(), [&](uint32_t a, uint32_t c) { return cost(a) > cost(c); });
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, b->device));
+    const uint32_t max_wgs = (uint32_t)std::max(1, cus) * EXACT_WAVES_PER_CU / ba::EXACT_WAVES;
+    std::vector<uint32_t> work(2 * m), first{0};   // first: the launches' first records
+    uint32_t max_r = 0;
+    uint64_t cells = 0;
+    for (size_t s = 0; s < m; s++) {
+        const uint32_t d = devpos[rec[s]];
+        work[2 * s] = d; work[2 * s + 1] = rec[s];
+        if (d == ba::EXACT_NO_PAIR) continue;
+        max_r = std::max(max_r, rl[d]);
+        const uint64_t c = ((uint64_t)ql[d] + 1) * ((uint64_t)rl[d] + 1);
+        // (a launch is cut only once every wave of the device has a pair: long pairs would otherwise leave most of it idle)
+        if (cells + c > EXACT_LAUNCH_CELLS && s - first.back() >= (size_t)max_wgs * ba::EXACT_WAVES) { first.push_back((uint32_t)s); cells = 0; }
+        cells += c;
+    }
+    first.push_back((uint32_t)m);
+    const size_t launches = first.size() - 1;
+    const uint32_t wgs = (uint32_t)std::min<uint64_t>(max_wgs, (std::min<uint64_t>(m, first[1]) + ba::EXACT_WAVES - 1) / ba::EXACT_WAVES);   // (the first launch is the largest)
+    const uint64_t stride = ba::exact_row_stride(max_r), row_bytes = (uint64_t)wgs * ba::EXACT_WAVES * stride * 8;
+    if (b->ex_rows.bytes < row_bytes) {
+        size_t free_b = 0, total_b = 0;
+        mem_info(&free_b, &total_b);
+        if (row_bytes > free_b + b->ex_rows.bytes)
+            return fail("exact: the row buffers need %llu bytes of device memory (%u waves x %llu reference columns x 8), %zu are free", (unsigned long long)row_bytes,
+                        wgs * ba::EXACT_WAVES, (unsigned long long)stride, free_b + b->ex_rows.bytes);
+        if (b->ex_rows.alloc(row_bytes)) return 1;
+    }
+    if (b->ex_work.bytes < 2 * m * 4 && b->ex_work.alloc(2 * m * 4)) return 1;
+    if (b->ex_out.bytes < m * sizeof(ba::Exact) && b->ex_out.alloc(m * sizeof(ba::Exact))) return 1;
+    if (b->ex_counter.bytes < launches * 4 && b->ex_counter.alloc(launches * 4)) return 1;
+    HIP_TRY(hipMemcpy(b->ex_work.p, work.data(), 2 * m * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(b->ex_counter.p, 0, launches * 4, b->stream));
+    if (!b->ev_x0) HIP_TRY(hipEventCreate(&b->ev_x0));
+    if (!b->ev_x1) HIP_TRY(hipEventCreate(&b->ev_x1));
+    ba::ExactParams xp{};
+    xp.what = what; xp.x_drop = x_drop; xp.kind = seq_kind(b->kind); xp.gap_open = b->gap_open; xp.gap_extend = b->gap_extend;
+    xp.matrix = b->matrix.as<int8_t>(); xp.matrix_bytes = (uint32_t)std::min<size_t>(b->matrix.bytes, 1024);
+    xp.pool = b->pool.as<uint8_t>(); xp.q_off = b->q_off.as<uint64_t>(); xp.q_len = b->q_len.as<uint32_t>();
+    xp.r_off = b->r_off.as<uint64_t>(); xp.r_len = b->r_len.as<uint32_t>();
+    xp.rows = b->ex_rows.as<int32_t>(); xp.row_stride = stride; xp.out = b->ex_out.as<ba::Exact>();
+    HIP_TRY(hipEventRecord(b->ev_x0, b->stream));
+    for (size_t l = 0; l < launches; l++) {
+        xp.n = first[l + 1] - first[l];
+        xp.work = b->ex_work.as<uint32_t>() + 2 * (size_t)first[l];
+        xp.counter = b->ex_counter.as<uint32_t>() + l;
+        HIP_TRY(ba_launch_exact(b->stream, &xp, std::min<uint32_t>(wgs, (xp.n + ba::EXACT_WAVES - 1) / ba::EXACT_WAVES)));
+    }
+    HIP_TRY(hipEventRecord(b->ev_x1, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    HIP_TRY(hipEventElapsedTime(&b->exact_ms, b->ev_x0, b->ev_x1));
+    HIP_TRY(hipMemcpy(out, b->ex_out.p, m * sizeof(ba::Exact), hipMemcpyDeviceToHost));
+    cells = 0;
+    for (size_t k = 0; k < m; k++) if (devpos[k] != ba::EXACT_NO_PAIR) cells += (uint64_t)out[k].rows * ((uint64_t)rl[devpos[k]] + 1);
+    b->exact_cells = cells;
+    return 0;
+}
+// `which` (null: every pair) in the caller's order -> device positions
+static int batch_exact(BaBatch* b, uint32_t what, int32_t x_drop, const uint32_t* which, size_t n_which, BaExact* out) {
+    if (!b) return fail("null batch");
+    if (exact_refusals(b, what, out)) return 1;
+    const size_t m = which ? n_which : b->n;
+    std::vector<uint32_t> dev_of, devpos(m);
+    if (!b->h_order.empty()) { dev_of.resize(b->n); for (uint32_t s = 0; s < b->n; s++) dev_of[b->h_order[s]] = s; }
+    for (size_t k = 0; k < m; k++) {
+        const uint32_t p = which ? which[k] : (uint32_t)k;
+        if (p >= b->n) return fail("exact: which[%zu] = %u is out of range (the batch holds %u pairs)", k, p, b->n);
+        devpos[k] = dev_of.empty() ? p : dev_of[p];
+    }
+    return batch_exact_device(b, what, x_drop, devpos.data(), m, out);
+}
+static int extend_exact(BaExtendBatch* e, int32_t x_drop, const uint32_t* which, size_t n_which, BaExact* left, BaExact* right, int32_t* score) {
+    if (!e) return fail("null batch");
+    if (!left || !right || !score) return fail("null argument");
+    if (!e->n) return fail("exact: the batch holds no seeds (a reload failed)");
+    const size_t m = which ? n_which : e->n;
+    if (!m) return 0;
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<uint32_t> side(2 * (size_t)e->n), sel(m), devpos(2 * m);
+    HIP_TRY(hipMemcpy(side.data(), e->side.p, side.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < m; k++) {
+        const uint32_t s = which ? which[k] : (uint32_t)k;
+        if (s >= e->n) return fail("exact: which[%zu] = %u is out of range (the batch holds %u seeds)", k, s, e->n);
+        sel[k] = s; devpos[2 * k] = side[2 * (size_t)s]; devpos[2 * k + 1] = side[2 * (size_t)s + 1];
+    }
+    std::vector<BaExact> rec(2 * m, BaExact{});
+    if (e->inner && e->n_sides && batch_exact_device(e->inner.get(), BA_EXACT_EXTEND, x_drop, devpos.data(), 2 * m, rec.data())) return 1;
+    DevBuf d_sel, d_seed;
+    if (d_sel.alloc(m * 4) || d_seed.alloc(m * 4)) return 1;
+    HIP_TRY(hipMemcpy(d_sel.p, sel.data(), m * 4, hipMemcpyHostToDevice));
+    const ba::ExtendParams ep = e->params();
+    HIP_TRY(ba_launch_exact_seed(e->stream, &ep, d_sel.as<uint32_t>(), (uint32_t)m, d_seed.as<int32_t>()));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(score, d_seed.p, m * 4, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < m; k++) { left[k] = rec[2 * k]; right[k] = rec[2 * k + 1]; score[k] += rec[2 * k].score + rec[2 * k + 1].score; }
+    return 0;
+}
+
 // ------------------------------------------------------------------ alignment strings (ba_*_text)
 // The format and flags of `what`, against the batch's kind and mode (the other refusals are the stats calls').
 static int text_check(int kind, uint32_t mode, uint32_t what) {
@@ -1971,6 +2116,43 @@ int ba_batch_stats(BaBatch* b, BaAlignStats* out) {
     HIP_TRY(hipMemcpy(out, b->stats.p, (size_t)b->n * sizeof(ba::AlignStats), hipMemcpyDeviceToHost));
     return 0;
 }
+int ba_batch_exact(BaBatch* b, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, BaExact* out) {
+    return batch_exact(b, what, x_drop, which, n_which, out);
+}
+int ba_batch_exact_ms(BaBatch* b, float* ms, uint64_t* cells) {
+    if (!b) return fail("null batch");
+    if (ms) *ms = b->exact_ms;
+    if (cells) *cells = b->exact_cells;
+    return 0;
+}
+int ba_exact_check_lengths(const uint32_t* q_len, const uint32_t* r_len, uintptr_t n) {
+    if (n && (!q_len || !r_len)) return fail("null argument");
+    return exact_check_lengths(q_len, r_len, n, nullptr);
+}
+int ba_accuracy_summary(const int32_t* score, const uint32_t* qidx, const uint32_t* ridx, const uint32_t* status, const BaExact* exact, uintptr_t n,
+                        BaAccuracy* out) {
+    if (!out) return fail("null argument: out");
+    if (n && (!score || !exact)) return fail("null argument");
+    BaAccuracy a{};
+    a.n = n;
+    double rel = 0; uint64_t rel_n = 0;
+    for (size_t k = 0; k < n; k++) {
+        if (status && (status[k] & ba::STATS_FAILED)) { a.skipped++; continue; }
+        a.compared++;
+        const int64_t diff = (int64_t)exact[k].score - score[k];
+        if ((qidx && qidx[k] != exact[k].query_idx) || (ridx && ridx[k] != exact[k].reference_idx)) a.diff_end++;
+        if (!diff) continue;
+        const int32_t d32 = (int32_t)std::max<int64_t>(INT32_MIN, std::min<int64_t>(INT32_MAX, diff));
+        if (!a.wrong) a.min_diff = a.max_diff = d32;
+        a.wrong++;
+        if (diff > 0) a.below++; else a.above++;
+        a.min_diff = std::min(a.min_diff, d32); a.max_diff = std::max(a.max_diff, d32);
+        if (exact[k].score) { rel += (double)diff / std::fabs((double)exact[k].score); rel_n++; }
+    }
+    a.mean_rel_error = rel_n ? rel / (double)rel_n : 0.0;
+    *out = a;
+    return 0;
+}
 int ba_batch_text(BaBatch* b, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) {
     if (!b) return fail("null batch");
     if (!offsets) return fail("null argument: offsets");
@@ -2088,6 +2270,9 @@ int ba_extend_batch_stats(BaExtendBatch* e, BaAlignStats* out) {
 }
 // The spliced runs (caller's order, out_off / runs) from the extension's start; the oriented query and the reference read from the caller's
 // bytes on the device (raw), by k_pack_images' rule. (The sides' texts cannot be joined: the equal stretches merge across the seed.)
+int ba_extend_batch_exact(BaExtendBatch* e, int32_t x_drop, const uint32_t* which, uintptr_t n_which, BaExact* left, BaExact* right, int32_t* score) {
+    return extend_exact(e, x_drop, which, n_which, left, right, score);
+}
 int ba_extend_batch_text(BaExtendBatch* e, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) {
     if (!e) return fail("null batch");
     if (!offsets) return fail("null argument: offsets");
@@ -2401,6 +2586,28 @@ static int parts_stats(BaPartSet* m, BaAlignStats* out) {
     }
     return 0;
 }
+static int parts_exact(BaPartSet* m, uint32_t what, int32_t x_drop, const uint32_t* which, size_t n_which, BaExact* out) {   // every part computes its own pairs
+    if (!m) return fail("null batch");
+    if (!out) return fail("null argument: out");
+    const size_t cnt = which ? n_which : m->n;
+    std::vector<uint32_t> part_of(m->n), local_of(m->n);
+    for (size_t k = 0; k < m->part.size(); k++)
+        for (size_t i = 0; i < m->pos[k].size(); i++) { part_of[m->pos[k][i]] = (uint32_t)k; local_of[m->pos[k][i]] = (uint32_t)i; }
+    std::vector<std::vector<uint32_t>> local(m->part.size()), at(m->part.size());   // per part: its pairs of the request, and their records
+    for (size_t k = 0; k < cnt; k++) {
+        const uint32_t p = which ? which[k] : (uint32_t)k;
+        if (p >= m->n) return fail("exact: which[%zu] = %u is out of range (the batch holds %zu pairs)", k, p, m->n);
+        local[part_of[p]].push_back(local_of[p]); at[part_of[p]].push_back((uint32_t)k);
+    }
+    std::vector<BaExact> tmp;
+    for (size_t k = 0; k < m->part.size(); k++) {
+        if (local[k].empty()) continue;
+        tmp.resize(local[k].size());
+        if (batch_exact(m->part[k].get(), what, x_drop, local[k].data(), local[k].size(), tmp.data())) return 1;
+        for (size_t i = 0; i < tmp.size(); i++) out[at[k][i]] = tmp[i];
+    }
+    return 0;
+}
 static int parts_text(BaPartSet* m, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) {   // sized per part, then rendered per part
     if (!m) return fail("null batch");
     if (!offsets) return fail("null argument: offsets");
@@ -2521,6 +2728,7 @@ int ba_multibatch_results(BaMultiBatch* m, int32_t* score, uint32_t* qi, uint32_
 }
 int ba_multibatch_cigars(BaMultiBatch* m, uint32_t* runs, uint64_t capacity) { return parts_cigars(m, runs, capacity); }
 int ba_multibatch_stats(BaMultiBatch* m, BaAlignStats* out) { return parts_stats(m, out); }
+int ba_multibatch_exact(BaMultiBatch* m, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, BaExact* out) { return parts_exact(m, what, x_drop, which, n_which, out); }
 int ba_multibatch_text(BaMultiBatch* m, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) { return parts_text(m, what, offsets, text, capacity); }
 int ba_multibatch_kernel_ms(BaMultiBatch* m, float* ms, int capacity) {   // per slice, of the last run; returns the number of slices
     if (!m) return -1;
@@ -2634,6 +2842,7 @@ int ba_sized_batch_results(BaSizedBatch* m, int32_t* score, uint32_t* qi, uint32
 }
 int ba_sized_batch_cigars(BaSizedBatch* m, uint32_t* runs, uint64_t capacity) { return parts_cigars(m, runs, capacity); }
 int ba_sized_batch_stats(BaSizedBatch* m, BaAlignStats* out) { return parts_stats(m, out); }
+int ba_sized_batch_exact(BaSizedBatch* m, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, BaExact* out) { return parts_exact(m, what, x_drop, which, n_which, out); }
 int ba_sized_batch_text(BaSizedBatch* m, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) { return parts_text(m, what, offsets, text, capacity); }
 int ba_sized_batch_classes(BaSizedBatch* m, SizeRange* ranges, uint64_t* counts, int32_t* kernels, float* kernel_ms, int capacity) {   // the bins; returns their number
     if (!m) return -1;

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include "ba_exact.h"
 #include "ba_extend.h"
 #include "ba_params.h"
 #include "ba_stats.h"
@@ -67,6 +68,9 @@ hipError_t ba_launch_extend_gather(hipStream_t s, const ba::ExtendParams* ep);
 // ba_stats.hip
 hipError_t ba_launch_stats(hipStream_t s, const ba::StatsParams* sp);
 hipError_t ba_launch_stats_extend(hipStream_t s, const ba::ExtendParams* ep, const ba::AlignStats* side, ba::AlignStats* out);
+// ba_exact.hip
+hipError_t ba_launch_exact(hipStream_t s, const ba::ExactParams* xp, uint32_t wgs);
+hipError_t ba_launch_exact_seed(hipStream_t s, const ba::ExtendParams* ep, const uint32_t* which, uint32_t m, int32_t* out);
 // ba_text.hip
 hipError_t ba_launch_text_len(hipStream_t s, const ba::TextParams* tp);
 hipError_t ba_launch_text_write(hipStream_t s, const ba::TextParams* tp);

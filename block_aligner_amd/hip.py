@@ -57,6 +57,23 @@ if C.sizeof(AlignStatsC) != 48 or STATS_DTYPE.itemsize != 48:
 TEXT_CIGAR, TEXT_MD, TEXT_CS, TEXT_SOFT_CLIP = 0, 1, 2, 1 << 8   # ba_*_text: the format, and the CIGAR's soft-clip flag
 
 
+class ExactC(C.Structure):
+    """struct BaExact (include/block_aligner_hip.h): one record of the ba_*_exact calls."""
+    _fields_ = [("score", C.c_int32), ("query_idx", C.c_uint32), ("reference_idx", C.c_uint32), ("rows", C.c_uint32)]
+
+
+class AccuracyC(C.Structure):
+    """struct BaAccuracy: what ba_accuracy_summary reports."""
+    _fields_ = [("n", C.c_uint64), ("compared", C.c_uint64), ("skipped", C.c_uint64), ("wrong", C.c_uint64), ("below", C.c_uint64),
+                ("above", C.c_uint64), ("diff_end", C.c_uint64), ("mean_rel_error", C.c_double), ("min_diff", C.c_int32), ("max_diff", C.c_int32)]
+
+
+EXACT_DTYPE = np.dtype(ExactC)
+if C.sizeof(ExactC) != 16 or EXACT_DTYPE.itemsize != 16:
+    raise ImportError(f"struct BaExact must be 16 bytes, the binding declares {C.sizeof(ExactC)}")
+EXACT_GLOBAL, EXACT_EXTEND = 0, 1   # ba_*_exact: the quantity
+
+
 def _text_list(buf, off):
     s = buf.tobytes().decode("ascii")
     o = off.tolist()
@@ -172,6 +189,12 @@ def lib() -> C.CDLL:
             getattr(L, f"{f}_stats").argtypes = [vp, vp]
             getattr(L, f"{f}_text").argtypes = [vp, C.c_uint32, vp, vp, C.c_uint64]
             getattr(L, f"{f}_destroy").argtypes = [vp]
+        for f in ("ba_batch", "ba_sized_batch", "ba_multibatch"):
+            getattr(L, f"{f}_exact").argtypes = [vp, u32, i32, vp, sz, vp]
+        L.ba_extend_batch_exact.argtypes = [vp, i32, vp, sz, vp, vp, vp]
+        L.ba_batch_exact_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+        L.ba_exact_check_lengths.argtypes = [vp, vp, sz]
+        L.ba_accuracy_summary.argtypes = [vp, vp, vp, vp, vp, sz, C.POINTER(AccuracyC)]
         L.ba_batch_stats_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.ba_batch_text_ms.argtypes = [vp, C.POINTER(C.c_float)]
         _lib = L
@@ -245,6 +268,46 @@ def _size(size) -> SizeRangeC:
 
 def _gaps(gaps) -> GapsC:
     return GapsC(gaps.open, gaps.extend) if isinstance(gaps, S.Gaps) else GapsC(gaps[0], gaps[1])
+
+
+def accuracy_summary(score, exact, query_idx=None, reference_idx=None, status=None) -> dict:
+    """ba_accuracy_summary (needs no device): the results of a run (score[, query_idx, reference_idx, status]) against exact records of the
+    same pairs -- `exact` is an EXACT_DTYPE array, a dict of arrays as _Batch.exact() returns, or plain exact scores. -> dict: n, compared,
+    skipped (failure status), wrong (exact != score), below (score < exact), above, diff_end, mean_rel_error (mean of (exact - score) / |exact|
+    over the wrong pairs with exact != 0), min_diff, max_diff (of exact - score over the wrong pairs; 0 if none)."""
+    score = np.ascontiguousarray(score, dtype=np.int32)
+    n = len(score)
+    if isinstance(exact, dict):
+        rec = np.zeros(n, EXACT_DTYPE)
+        for k in EXACT_DTYPE.names:
+            rec[k] = exact[k]
+    elif getattr(exact, "dtype", None) == EXACT_DTYPE:
+        rec = np.ascontiguousarray(exact)
+    else:
+        rec = np.zeros(n, EXACT_DTYPE)
+        rec["score"] = exact
+    opt = [None if a is None else np.ascontiguousarray(a, dtype=np.uint32) for a in (query_idx, reference_idx, status)]
+    if len(rec) != n or any(a is not None and len(a) != n for a in opt):
+        raise ValueError("score, exact, query_idx, reference_idx and status must have one entry per pair")
+    out = AccuracyC()
+    if lib().ba_accuracy_summary(score.ctypes.data, *_ptrs(opt), rec.ctypes.data, n, C.byref(out)):
+        raise RuntimeError(last_error())
+    return {k: getattr(out, k) for k, _ in AccuracyC._fields_}
+
+
+def exact_check_lengths(q_len, r_len) -> None:
+    """The length guard of the exact calls on its own (needs no device): raises, naming the pair, if one is too long for int32 scores."""
+    q_len = np.ascontiguousarray(q_len, dtype=np.uint32); r_len = np.ascontiguousarray(r_len, dtype=np.uint32)
+    if lib().ba_exact_check_lengths(q_len.ctypes.data, r_len.ctypes.data, len(q_len)):
+        raise RuntimeError(last_error())
+
+
+def _which(which):
+    """-> (array or None, address, count) of a pair selection."""
+    if which is None:
+        return None, None, 0
+    w = np.ascontiguousarray(which, dtype=np.uint32)
+    return w, w.ctypes.data, len(w)
 
 
 def _pair_arrays(pool, q_off, q_len, *r):
@@ -479,6 +542,25 @@ class _Batch:
         out["edit_distance"] = out["mismatches"] + out["ins"] + out["del"]
         return out
 
+    def exact(self, what=None, x_drop=-1, which=None):
+        """Exact full-matrix scores of the batch's pairs, computed on the device (ba_*_exact; no run needed) -> dict of arrays score,
+        query_idx, reference_idx, rows. what: EXACT_GLOBAL (H[|q|][|r|]) or EXACT_EXTEND (the maximum over the matrix; with x_drop >= 0
+        under the row-wise X-drop rule); None = EXACT_EXTEND for an X-drop batch, EXACT_GLOBAL otherwise. which: pair indices in any order,
+        repeats allowed (record k belongs to which[k]); None = every pair."""
+        if what is None:
+            what = EXACT_EXTEND if self.mode & X_DROP else EXACT_GLOBAL
+        w, wp, wn = _which(which)
+        rec = np.zeros(self.n if w is None else wn, EXACT_DTYPE)
+        self._call("exact", int(what), int(x_drop), wp, wn, rec.ctypes.data)
+        return {k: rec[k].copy() for k in EXACT_DTYPE.names}
+
+    def accuracy(self, x_drop=-1, which=None):
+        """After a run: the batch's results against exact() of the same pairs (accuracy_summary) -> dict."""
+        ex = self.exact(None, x_drop, which)
+        res = self.results()
+        sel = slice(None) if which is None else np.asarray(which, dtype=np.int64)
+        return accuracy_summary(res["score"][sel], ex, res["query_idx"][sel], res["reference_idx"][sel], res["status"][sel])
+
     def text(self, what=TEXT_CIGAR, soft_clip=False):
         """TRACE batches after a run: every pair's CIGAR (TEXT_CIGAR, with soft_clip its S runs), SAM MD:Z value (TEXT_MD) or short cs:Z value
         (TEXT_CS), rendered on the device (ba_*_text) -> (buf: uint8 array, offsets: uint64 array of n + 1); pair p's text is
@@ -562,6 +644,12 @@ class BatchAligner(_Batch):
         ms = C.c_float()
         self._call("stats_ms", C.byref(ms))
         return ms.value
+
+    def exact_ms(self):
+        """(HIP-event milliseconds, cells) of the last exact() call: cells = the sum of rows * (|r| + 1) over the request."""
+        ms, cells = C.c_float(), C.c_uint64()
+        self._call("exact_ms", C.byref(ms), C.byref(cells))
+        return ms.value, int(cells.value)
 
     def text_ms(self) -> float:
         """HIP-event time of the text kernels the last text() call ran (the sizes, then the rendering), in milliseconds."""
@@ -707,6 +795,22 @@ class ExtendBatchAligner(_Batch):
         a = self._arrays(pool, q_off, q_len, r_off, r_len, q_seed, r_seed, seed_len, strand)
         self._call("reload", *_ptrs(a), len(a[2]))
         self.n = len(a[2])
+
+    def exact(self, x_drop=-1, which=None):
+        """EXACT_EXTEND on both sides of every seed (ba_extend_batch_exact; no run needed) -> dict: left and right (dicts of arrays score,
+        query_idx, reference_idx, rows; an empty side is all zeros) and score = left + the seed's ungapped score + right."""
+        w, wp, wn = _which(which)
+        m = self.n if w is None else wn
+        left, right, score = np.zeros(m, EXACT_DTYPE), np.zeros(m, EXACT_DTYPE), np.zeros(m, np.int32)
+        self._call("exact", int(x_drop), wp, wn, left.ctypes.data, right.ctypes.data, score.ctypes.data)
+        return dict(left={k: left[k].copy() for k in EXACT_DTYPE.names}, right={k: right[k].copy() for k in EXACT_DTYPE.names}, score=score)
+
+    def accuracy(self, x_drop=-1, which=None):
+        """After a run: the spliced scores against exact()'s (accuracy_summary without the end comparison) -> dict."""
+        ex = self.exact(x_drop, which)
+        res = self.results()
+        sel = slice(None) if which is None else np.asarray(which, dtype=np.int64)
+        return accuracy_summary(res["score"][sel], ex["score"], status=res["status"][sel])
 
     def times(self):
         """Device milliseconds: fill and splice of the last run(), image packers of the last create / reload."""

@@ -390,6 +390,64 @@ int ba_extend_batch_stats(BaExtendBatch* batch, struct BaAlignStats* out);
 /* HIP-event time (ms) of the last ba_batch_stats kernel on this batch */
 int ba_batch_stats_ms(BaBatch* batch, float* ms);
 
+/* ---- exact full-matrix scores and the accuracy of the block heuristic ("Exact scores and accuracy").
+ *
+ * Block alignment is a heuristic; these calls compute, on the device, what a full |q| x |r| matrix gives for the same images, matrix and gaps,
+ * so that a caller can count how often a block range misses the optimum on their own data. Scores are int32. A gap of length n costs
+ * open + (n - 1) extend. Rows are query positions i = 0 .. |q|, columns reference positions j = 0 .. |r|, H[0][0] = 0, textbook Gotoh H / E / F.
+ *   BA_EXACT_GLOBAL  H[|q|][|r|], reported with the end (|q|, |r|). An empty side gives the pure gap cost, two empty sides give 0.
+ *   BA_EXACT_EXTEND  x_drop < 0: the maximum of H over every cell, cell (0, 0) = 0 included.
+ *                    x_drop >= 0: rows are taken in order; rowmax_i = max over j of H[i][j] (row 0 includes cell (0, 0)), best = the largest
+ *                    rowmax of the rows seen so far, row i included; after row i, if rowmax_i < best - x_drop, stop: later rows do not count.
+ *                    Ties go to the smallest i, then the smallest j.
+ *                    This is the row-wise rule of the scalar DP the reference's x_drop_accuracy example compares with, but for one point: there
+ *                    cell (0, 0) is skipped, so a matrix without a positive cell yields a negative "best"; here the result is never below
+ *                    0 at (0, 0), which is also what Block::<_, true> reports.
+ * Two properties tie them to the batch results:
+ *   - BA_EXACT_EXTEND with x_drop < 0 is an upper bound on the score of every BA_X_DROP batch over the same pair;
+ *   - BA_EXACT_GLOBAL is an upper bound on the score of every batch without BA_X_DROP, and equals it when one block covers the matrix
+ *     (min = max block size > max(|q|, |r|)).
+ * rows = the query rows that counted: |q| + 1 unless the X-drop rule stopped earlier.
+ *
+ * which: pair indices in the caller's order, any order, repeats allowed; record k belongs to which[k]. NULL = every pair (n_which is ignored).
+ * The calls need no prior run and no BA_TRACE: they read the images, the matrix and the gaps only, and change no result of a run.
+ * Refused with a message (ba_last_error) and a nonzero return: a null batch, null out, an unknown `what`, an index out of range (the message
+ * names it), a batch with a launch in flight, a profile batch, a batch with BA_LOCAL_START or BA_FREE_QUERY_*, a pair whose (|q| + |r|) * 128
+ * does not stay above the minus-infinity sentinel -2^30 (the message names the pair), row buffers that do not fit device memory (the message
+ * gives the bytes needed). A request is cut into kernel launches of a bounded number of cells. The device buffers are allocated on the first
+ * call, grow, and are freed by destroy. */
+enum { BA_EXACT_GLOBAL = 0, BA_EXACT_EXTEND = 1 };
+struct BaExact {                 /* 16 bytes */
+    int32_t  score;
+    uint32_t query_idx, reference_idx;   /* the cell the score was read from */
+    uint32_t rows;               /* query rows that counted */
+};
+int ba_batch_exact(BaBatch* batch, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, struct BaExact* out);
+/* every part computes its own pairs (a multi-device batch: on its own device) */
+int ba_sized_batch_exact(BaSizedBatch* batch, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, struct BaExact* out);
+int ba_multibatch_exact(BaMultiBatch* batch, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, struct BaExact* out);
+/* HIP-event time (ms) and cells (the sum of rows * (|r| + 1) over the request) of the last ba_batch_exact call on this batch; either may be NULL */
+int ba_batch_exact_ms(BaBatch* batch, float* ms, uint64_t* cells);
+/* BA_EXACT_EXTEND on both sides of every seed in `which` (seed indices; NULL = all), over the sides the batch already holds: left[k] is over
+ * the reversed prefixes, right[k] over the suffixes, an empty side gives an all-zero record, and score[k] = left + the seed's ungapped score +
+ * right: an upper bound (x_drop < 0) on the extension's own score. */
+int ba_extend_batch_exact(BaExtendBatch* batch, int32_t x_drop, const uint32_t* which, uintptr_t n_which, struct BaExact* left,
+                          struct BaExact* right, int32_t* score);
+/* The length guard of the exact calls on its own (host only, no device): nonzero, naming the pair, if a pair is too long for int32 scores. */
+int ba_exact_check_lengths(const uint32_t* q_len, const uint32_t* r_len, uintptr_t n_pairs);
+/* Host only, no device: the results of a run against exact records of the same pairs. Pairs whose status has an overflow, lost or watchdog
+ * bit are skipped; diff = exact - score over the others; wrong counts diff != 0, below diff > 0 (the heuristic missed the optimum), above
+ * diff < 0; diff_end counts compared pairs whose end cell differs; mean_rel_error is the mean of diff / |exact| over the wrong pairs with
+ * exact != 0 (0 if there are none); min_diff / max_diff range over the wrong pairs (0 when nothing is wrong). query_idx, reference_idx and
+ * status may be NULL (no end comparison / nothing skipped). */
+struct BaAccuracy {
+    uint64_t n, compared, skipped, wrong, below, above, diff_end;
+    double   mean_rel_error;
+    int32_t  min_diff, max_diff;
+};
+int ba_accuracy_summary(const int32_t* score, const uint32_t* query_idx, const uint32_t* reference_idx, const uint32_t* status,
+                        const struct BaExact* exact, uintptr_t n, struct BaAccuracy* out);
+
 /* ---- alignment strings, rendered on the device from the CIGAR runs and the sequences the fill left there ("Alignment
  * strings"): the CIGAR (optionally soft-clipped), the SAM MD:Z value and minimap2's short cs:Z value of every traced alignment, in one text
  * buffer per call.
