@@ -2011,7 +2011,7 @@ struct Aligner {
             }
 #pragma unroll
             for (int d = 32; d >= 1; d >>= 1) sc += (uint32_t)__shfl_xor((int)sc, d, 64);
-            if (is_lane(0) && sc) atomicAdd(coldp()->prof + 60, (unsigned long long)sc);
+            if (is_lane(0) && sc && !(status & ST_CLASS_OVERFLOW)) atomicAdd(coldp()->prof + 60, (unsigned long long)sc);   // (a pair that lost the class bet is run again: nothing of this run is kept)
         }
         const uint32_t pair = (uint32_t)unpark<7>(parked), slot = (uint32_t)unpark<8>(parked);
         int score; uint32_t ri, rj;

@@ -2060,10 +2060,11 @@ int ba_batch_cigars(BaBatch* b, uint32_t* runs, uint64_t capacity) {
 #ifdef BA_DEV
 // Development library only: the device-side known-answer test of the lane primitives (k_lane_kat, ba_kernels.hip). x: n_cells int16 values of
 // D11_open, whole columns one after the other (form 0: 128 cells per column, four columns per wave; 1: 32 cells, sixteen per wave; 2 / 3 / 4: one
-// column of 128 / 64 / 32 cells per wave); out: the columns' R11.
+// column of 128 / 64 / 32 cells per wave; 5 / 6 / 7: k_multi's slots in the order of its loop of steps, four columns of 128 / two of 256 / one of 512 cells per wave);
+// out: the columns' R11.
 int ba_dev_lane_scan(int form, const int16_t* x, uint32_t n_cells, int gap_extend, int16_t* out) {
-    if (form < 0 || form > 4 || !x || !out) return fail("ba_dev_lane_scan: bad arguments");
-    const uint32_t per_wave = form <= 1 ? 512u : (form == 2 ? 128u : (form == 3 ? 64u : 32u));
+    if (form < 0 || form > 7 || !x || !out) return fail("ba_dev_lane_scan: bad arguments");
+    const uint32_t per_wave = (form <= 1 || form >= 5) ? 512u : (form == 2 ? 128u : (form == 3 ? 64u : 32u));
     if (n_cells == 0 || n_cells % per_wave) return fail("ba_dev_lane_scan: %u cells are not whole waves of %u", n_cells, per_wave);
     if (gap_extend > 0 || gap_extend < -128) return fail("ba_dev_lane_scan: gap_extend %d", gap_extend);
     DevBuf dx, dout;

@@ -105,13 +105,33 @@ __global__ void __launch_bounds__(64) k_traceback(const ba::BatchParams bp) {
 // Device-side known-answer test of the lane primitives (round 6; the reference's own: avx2.rs:469-489, plus the carry from vector to vector of
 // scan_block.rs:1144-1150): columns of x = D11_open in, R11 out, through the very functions the fill kernels call -- the scan constants
 // (make_fill_consts / make_multi_consts / make_small_consts) included. One wave per workgroup; a column starts from MIN = 0 above its first cell.
-//   form 0: k_multi's eight cells per lane, 16 lanes to a slot (four 128-cell columns per wave): scan8_* + multi_carry (wave_prefix_max16, G / w0)
+//   form 0: eight consecutive cells per lane, 16 lanes to a slot (four 128-cell columns per wave): scan8_* + multi_carry (wave_prefix_max16, G / w0).
+//           k_multi's order until round 7; no kernel runs this combination any more (k_multi: forms 5 .. 7, scan8_*: form 1) -- it pins multi_carry<16>
+//           and w0 against a second, independent in-lane scan
 //   form 1: k_small's eight cells per lane, 4 lanes to a slot (sixteen 32-cell columns per wave): scan8_* + small_carry (quad_prefix_max)
 //   form 2 / 3 / 4: two cells per lane, 64 / 32 / 16 lanes (one 128- / 64- / 32-cell column per wave): fast_scan (k_align, k_quad, the solo drivers)
+//   form 5 / 6 / 7: k_multi's slots as its loop of steps holds them (round 7): eight cells per lane, cells k and k + 4 to a register, 16 / 32 / 64 lanes
+//   to a slot (four 128-cell, two 256-cell columns or one 512-cell column per wave): scan_halves + multi_carry<16 / 32 / 64> + apply_halves
 // Reached only through the development library (ba_dev_lane_scan, ba_host.cpp).
 __global__ void __launch_bounds__(64) k_lane_kat(int form, const short* __restrict__ x, short* __restrict__ out, int gap_extend) {
     using namespace ba;
     const int lane = lane_id();
+    if (form >= 5) {
+        const short* xi = x + (size_t)blockIdx.x * 512 + lane * 8;
+        int r[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) r[k] = pk((int)xi[k], (int)xi[k + 4]);
+        const int ge2 = splat(gap_extend);
+        const int l = lane & (form == 5 ? 15 : (form == 6 ? 31 : 63));
+        const MultiConsts mc = make_multi_consts(l, gap_extend);
+        const int r3 = scan_halves(r, ge2, mc);
+        const int cs = form == 5 ? multi_carry<16>(r3, mc, l) : (form == 6 ? multi_carry<32>(r3, mc, l) : multi_carry<64>(r3, mc, l));
+        apply_halves(r, r3, cs, ge2, mc);
+        short* oi = out + (size_t)blockIdx.x * 512 + lane * 8;
+#pragma unroll
+        for (int k = 0; k < 4; k++) { oi[k] = as_s(r[k]).x; oi[k + 4] = as_s(r[k]).y; }
+        return;
+    }
     if (form <= 1) {
         const short* xi = x + (size_t)blockIdx.x * 512 + lane * 8;
         int xr[4], r[4];
@@ -124,7 +144,7 @@ __global__ void __launch_bounds__(64) k_lane_kat(int form, const short* __restri
         if (form == 0) {
             const MultiConsts mc = make_multi_consts(lane & 15, gap_extend);
 #pragma unroll
-            for (int k = 0; k < 4; k++) G[k] = mc.G[k];
+            for (int k = 0; k < 4; k++) G[k] = pk(max(-32768, (2 * k + 1) * gap_extend), max(-32768, (2 * k + 2) * gap_extend));   // what a gap that enters the lane above its first cell has lost on reaching cells 2k, 2k + 1
             scan8_chain(r, G[0]);
             cs = multi_carry(r[3], mc);
         } else {

@@ -69,23 +69,54 @@ template <int SL> __device__ __forceinline__ int slot_shl1_keep(int last, int sr
     else { const int t = __builtin_amdgcn_update_dpp(last, src, 0x130, 0xf, 0xf, false); return l == SL - 1 ? last : t; }   // (wave_shl:1; lane 63 has no source: keeps `last`)
 }
 
+// ---- The slots' registers (round 7): register k of a lane holds its cells k (low half) and k + 4 (high half), not 2k and 2k + 1. Shifting the lane's
+// eight cells down by one is then a rename for three of the four registers (D00: one DPP + one v_alignbit per column instead of one + four), and the
+// in-lane gap scan is ONE packed chain of three links that scans cells 0 .. 3 and 4 .. 7 side by side, joined by a single carry across the halves
+// (scan_halves / apply_halves: 20 instructions per column where the chain over consecutive pairs took 32). Only the registers of the loop of steps
+// and its two LDS buffers are in this order: the arena, the trace words and everything the per-pair driver and the traceback read keep the cells
+// consecutive (cells_split / cells_join at the loop's edges; the trace bytes are put in order once per two columns).
+__device__ __forceinline__ void cells_split(int (&v)[4]) {   // (c0 c1)(c2 c3)(c4 c5)(c6 c7) -> (c0 c4)(c1 c5)(c2 c6)(c3 c7)
+    const int a = v[0], b = v[1], c = v[2], d = v[3];
+    v[0] = __builtin_amdgcn_perm(c, a, 0x05040100); v[1] = __builtin_amdgcn_perm(c, a, 0x07060302);
+    v[2] = __builtin_amdgcn_perm(d, b, 0x05040100); v[3] = __builtin_amdgcn_perm(d, b, 0x07060302);
+}
+__device__ __forceinline__ void cells_join(int (&v)[4]) {    // ... and back
+    const int a = v[0], b = v[1], c = v[2], d = v[3];
+    v[0] = __builtin_amdgcn_perm(b, a, 0x05040100); v[1] = __builtin_amdgcn_perm(d, c, 0x05040100);
+    v[2] = __builtin_amdgcn_perm(b, a, 0x07060302); v[3] = __builtin_amdgcn_perm(d, c, 0x07060302);
+}
+__device__ __forceinline__ int4 cells_split(int4 q) { int v[4] = {q.x, q.y, q.z, q.w}; cells_split(v); return int4{v[0], v[1], v[2], v[3]}; }
+__device__ __forceinline__ int4 cells_join(int4 q) { int v[4] = {q.x, q.y, q.z, q.w}; cells_join(v); return int4{v[0], v[1], v[2], v[3]}; }
+// {a.lo (+) k.lo, a.lo (+) k.hi}: the low half against both halves of a wave-uniform constant, saturating
+__device__ __forceinline__ int adds_lo(int a, int k) {
+    int t;
+    asm("v_pk_add_i16 %0, %1, %2 op_sel_hi:[0,1] clamp" : "=v"(t) : "v"(a), "s"(k));
+    return t;
+}
+// {a.lo, max(a.hi, b.lo)}
+__device__ __forceinline__ int max_hi_lo(int a, int b) {
+    asm("v_max_i16_sdwa %0, %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_0" : "+v"(a) : "v"(b));
+    return a;
+}
+
 struct MultiConsts {
-    int G[4];             // {(2k+1) g, (2k+2) g}: what a gap that enters the lane above its first cell has lost on reaching register k
+    int g2, g3;           // splat(2g), splat(3g) (splat(g) is FillConsts::ge2): the same for cells k, k + 4 of register k, relative to the carry of their half
+    int K4, G48;          // {0, 4g}; {4g, 8g}
     int laneKG, lanem1KG; // l * 8g; (l - 1) * 8g, except row lane 0 which holds -32768 (no lane above: a candidate that never wins)
     int w0;               // {0, W}: the floor of the carry that enters the lane from above, per half. Per cell the column's R is also at least
                           // max(zero-shift-in artefact of the reference's in-vector scan, the MIN = 0 carry above the column) =: V(cell); for the lane's
-                          // first seven cells V = G[k] in every lane (artefact ((cell & 7) + 1) g >= carry (cell + 1) g), i.e. max(cs + G, G) =
+                          // first seven cells V = (cell + 1) g in every lane (artefact ((cell & 7) + 1) g >= carry (cell + 1) g), i.e. max(cs + G, G) =
                           // max(cs, 0) + G (saturating adds of non-positive constants compose); the eighth cell's V differs per lane -- 8g in lane 0,
                           // 12g in the other even lanes, (8l + 8) g in the odd ones -- and is written V = W + 8g: ONE max per column (cs against
-                          // {0, W}) replaces the four per-register maxima with V
+                          // {0, W}) replaces the per-register maxima with V
 };
 
 // (one definition for the kernels and k_lane_kat) l: the lane inside its slot's sixteen
 __device__ __forceinline__ MultiConsts make_multi_consts(int l, int gx) {
     MultiConsts mc;
     mc.laneKG = l * 8 * gx; mc.lanem1KG = l ? (l - 1) * 8 * gx : -32768;
-#pragma unroll
-    for (int k = 0; k < 4; k++) mc.G[k] = pk(max(-32768, (2 * k + 1) * gx), max(-32768, (2 * k + 2) * gx));
+    mc.g2 = splat(max(-32768, 2 * gx)); mc.g3 = splat(max(-32768, 3 * gx));
+    mc.K4 = pk(0, max(-32768, 4 * gx)); mc.G48 = pk(max(-32768, 4 * gx), max(-32768, 8 * gx));
     mc.w0 = pk(0, l == 0 ? 0 : ((l & 1) ? max(-32768, 8 * l * gx) : 4 * gx));   // (see MultiConsts)
     return mc;
 }
@@ -103,6 +134,24 @@ __device__ __forceinline__ int multi_carry(int r3, const MultiConsts& mc, int l 
     }
 }
 
+// R11 of a lane's eight cells in the order of the slots' registers (x[k] = D11_open of cells k, k + 4; avx2.rs:297-338 + scan_block.rs:1144-1150).
+// scan_halves: the packed chain, both halves at once; returns the lane's fourth register with its last cell's R complete inside the lane
+// (cell 7 against cell 3's gap), which is what multi_carry scans over the lanes.
+__device__ __forceinline__ int scan_halves(int (&r)[4], int ge2, const MultiConsts& mc) {
+#pragma unroll
+    for (int k = 1; k < 4; k++) r[k] = vmax(r[k], adds(r[k - 1], ge2));
+    return vmax(r[3], adds_lo(r[3], mc.K4));
+}
+// cs = {max(carry, 0), max(carry, W)} from multi_carry; r3 from scan_halves. What enters the high half -- the larger of cell 3's R and the carry four
+// cells further down -- and what enters the low half share one register, so that every register takes one add and one max; the eighth cell
+// has its own floor (MultiConsts::w0).
+__device__ __forceinline__ void apply_halves(int (&r)[4], int r3, int cs, int ge2, const MultiConsts& mc) {
+    const int t = max_hi_lo(adds_lo(cs, mc.K4), r[3]);
+    r[0] = vmax(r[0], adds(t, ge2)); r[1] = vmax(r[1], adds(t, mc.g2)); r[2] = vmax(r[2], adds(t, mc.g3));
+    r[3] = vmax(r3, adds(cs, mc.G48));
+}
+
+typedef int lds_v4i __attribute__((ext_vector_type(4)));   // (16 bytes through a pointer into LDS: the HIP vector classes assign only through generic pointers)
 struct MultiOut { int mx, act_max8, pas_max8, corner_new; };
 
 // One 8-column shift step for the four slots of a wave, 8 cells per lane (scan_block.rs:147-246 with place_block 1083-1228 and
@@ -125,19 +174,17 @@ __device__ __forceinline__ void multi_rect(const char* table, const FillConsts& 
     o.corner_new = slot_first<SL>(pd[3]) >> 16;   // D_corner for a following orthogonal step: the orthogonal border's entry 7, re-based
     ScoreKey<KIND> key[4];
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const uint32_t w = k < 2 ? vb.x : vb.y;
-        key[k] = make_key<KIND>((int)((w >> (16 * (k & 1))) & 0xffu), (int)((w >> (16 * (k & 1) + 8)) & 0xffu));
-    }
+    for (int k = 0; k < 4; k++) key[k] = make_key<KIND>((int)((vb.x >> (8 * k)) & 0xffu), (int)((vb.y >> (8 * k)) & 0xffu));   // cells k, k + 4
     uint32_t kb[4] = {0, 0, 0, 0}, cbs_lo = 0, cbs_hi = 0;   // NUC: see add_byte (ba_device.hpp)
     if constexpr (KIND == KIND_NUC) {
-        const uint32_t tb = (uint32_t)(uintptr_t)table, k01 = nuc_keys2(vb.x), k23 = nuc_keys2(vb.y);
+        const uint32_t tb = (uint32_t)(uintptr_t)table;
+        const uint32_t k01 = nuc_keys2((uint32_t)__builtin_amdgcn_perm((int)vb.y, (int)vb.x, 0x05010400)), k23 = nuc_keys2((uint32_t)__builtin_amdgcn_perm((int)vb.y, (int)vb.x, 0x07030602));   // bytes (0, 4, 1, 5) / (2, 6, 3, 7)
         kb[0] = add_word(k01, tb, 0); kb[1] = add_word(k01, tb, 1); kb[2] = add_word(k23, tb, 0); kb[3] = add_word(k23, tb, 1);
         cbs_lo = nuc_col_offsets(cb_lo); cbs_hi = nuc_col_offsets(cb_hi);
     }
     int dmax[4] = {0, 0, 0, 0}, tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int nvD[4] = {0, 0, 0, 0}, nvR[4] = {0, 0, 0, 0};   // the last cells of the 8 new columns: the orthogonal border's new entries (row lane 15)
-    int holdD = 0, holdR = 0;
+    int nvD[4] = {0, 0, 0, 0}, nvR[4] = {0, 0, 0, 0};   // the last cells of the 8 new columns: the orthogonal border's new entries (row lane 15), columns k, k + 4 to a register
+    int holdD[4] = {0, 0, 0, 0}, holdR[4] = {0, 0, 0, 0};
 #pragma unroll
     for (int j = 0; j < STEP; j++) {
         const int cb = (int)(((j < 4 ? cb_lo : cb_hi) >> (8 * (j & 3))) & 0xffu);
@@ -147,13 +194,14 @@ __device__ __forceinline__ void multi_rect(const char* table, const FillConsts& 
             if constexpr (KIND == KIND_NUC) sc[k] = lds_read_i32(add_byte(j < 4 ? cbs_lo : cbs_hi, kb[k], j));
             else sc[k] = fetch_score<KIND>(table, key[k], cb);
         }
-        // D00: the previous column shifted down one cell (scan_block.rs:1125); only column 0 has a cell above the block
+        // D00: the previous column shifted down one cell (scan_block.rs:1125); only column 0 has a cell above the block. Cells k - 1, k + 3 are
+        // register k - 1; the first register takes the lane above's cell 7 and this lane's cell 3
         int prev = slot_shr1_z<SL>(d[3], l);
         if (j == 0) prev = l == 0 ? (int)((uint32_t)corner << 16) : prev;
         int d00[4];
-        d00[0] = __builtin_amdgcn_alignbit(d[0], prev, 16);
+        d00[0] = __builtin_amdgcn_alignbit(d[3], prev, 16);
 #pragma unroll
-        for (int k = 1; k < 4; k++) d00[k] = __builtin_amdgcn_alignbit(d[k], d[k - 1], 16);
+        for (int k = 1; k < 4; k++) d00[k] = d[k - 1];
         int d11[4], copen[4], cn[4], x[4], r[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -164,16 +212,16 @@ __device__ __forceinline__ void multi_rect(const char* table, const FillConsts& 
             cn[k] = vmax(adds(c[k], fc.ge2), copen[k]);
             d11[k] = vmax(d11[k], cn[k]);
             x[k] = adds(d11[k], fc.ome2);                                  // D11_open
-            r[k] = scan8_inreg(x[k], fc.ge2);                              // inside the register
+            r[k] = x[k];
         }
         // R11: the chain over the lane's registers, then one 16-lane scan on values re-based by l * 8g
-        scan8_chain(r, mc.G[0]);
-        const int cs = multi_carry<SL>(r[3], mc, l);    // R of the lane above's last cell (no clamp: see fast_scan), floored: see MultiConsts::w0
+        const int r3 = scan_halves(r, fc.ge2, mc);
+        const int cs = multi_carry<SL>(r3, mc, l);      // R of the lane above's last cell (no clamp: see fast_scan), floored: see MultiConsts::w0
+        apply_halves(r, r3, cs, fc.ge2, mc);
         int dn[4];
         uint32_t sC[4], sR[4], sCo[4], sRo[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            r[k] = scan8_apply(r[k], cs, mc.G[k], k == 3);
             dn[k] = vmax(d11[k], r[k]);
             if (TRACE) {   // the cell's four flags as sign bits of saturating differences (see fast_rect); packed below, two registers at a time
                 sC[k] = (uint32_t)subs(cn[k], dn[k]); sR[k] = (uint32_t)subs(r[k], dn[k]); sCo[k] = (uint32_t)subs(copen[k], cn[k]); sRo[k] = (uint32_t)subs(x[k], r[k]);
@@ -184,31 +232,37 @@ __device__ __forceinline__ void multi_rect(const char* table, const FillConsts& 
         if (TRACE && SPM == 1) {   // zero mask (scan_block.rs:1184-1187): D >= the relative zero, so "differs" is the sign of rz - D
 #pragma unroll
             for (int p2 = 0; p2 < 2; p2++) {
-                const uint32_t pZ = (uint32_t)__builtin_amdgcn_perm(subs(rz2, dn[2 * p2 + 1]), subs(rz2, dn[2 * p2]), 0x0b0a0908);
+                const uint32_t pZ = (uint32_t)__builtin_amdgcn_perm(subs(rz2, dn[2 * p2 + 1]), subs(rz2, dn[2 * p2]), 0x0b090a08);   // (cells 2 p2, 2 p2 + 1, 2 p2 + 4, 2 p2 + 5: put in order at the end)
                 zacc[p2] |= pZ & (0x01010101u << j);
             }
         }
         if (TRACE) {
-            // Trace words of a slot's rectangle: 4 consecutive cells (the two registers of a pair) x 2 columns, a byte per cell, the even
+            // Trace words of a slot's rectangle: 4 consecutive cells x 2 columns, a byte per cell, the even
             // column in its low nibble; a lane's eight words -- its 8 cells x the step's 8 columns -- are contiguous in memory (word
-            // lane * 8 + (column >> 1) * 2 + register pair), so that the traceback finds everything around a path cell in one cache line.
+            // lane * 8 + (column >> 1) * 2 + (cell >> 2)), so that the traceback finds everything around a path cell in one cache line.
+            // A pair of registers holds cells 2 p2, 2 p2 + 1 and the two four further down: its bytes are gathered as (2 p2, 2 p2 + 1, 2 p2 + 4,
+            // 2 p2 + 5), and once two columns are complete two v_perm exchange the middle halves of the two words.
             // The sign bytes of two registers' differences are gathered by one v_perm each, so that the three bit-field inserts that build a
             // nibble {nRo, nCo, nR, nC} (see fast_rect) serve four cells instead of two.
 #pragma unroll
             for (int p2 = 0; p2 < 2; p2++) {
                 // (v_perm selectors 8 .. 11 replicate a sign bit over the byte: four clean 0x00 / 0xff masks, merged by three bit-field inserts
                 // into the nibble {nRo, nCo, nR, nC} in BOTH halves of every byte -- round 5: 7.5 instead of 11 instructions per register pair)
-                const uint32_t pC = (uint32_t)__builtin_amdgcn_perm((int)sC[2 * p2 + 1], (int)sC[2 * p2], 0x0b0a0908), pR = (uint32_t)__builtin_amdgcn_perm((int)sR[2 * p2 + 1], (int)sR[2 * p2], 0x0b0a0908);
-                const uint32_t pCo = (uint32_t)__builtin_amdgcn_perm((int)sCo[2 * p2 + 1], (int)sCo[2 * p2], 0x0b0a0908), pRo = (uint32_t)__builtin_amdgcn_perm((int)sRo[2 * p2 + 1], (int)sRo[2 * p2], 0x0b0a0908);
+                const uint32_t pC = (uint32_t)__builtin_amdgcn_perm((int)sC[2 * p2 + 1], (int)sC[2 * p2], 0x0b090a08), pR = (uint32_t)__builtin_amdgcn_perm((int)sR[2 * p2 + 1], (int)sR[2 * p2], 0x0b090a08);
+                const uint32_t pCo = (uint32_t)__builtin_amdgcn_perm((int)sCo[2 * p2 + 1], (int)sCo[2 * p2], 0x0b090a08), pRo = (uint32_t)__builtin_amdgcn_perm((int)sRo[2 * p2 + 1], (int)sRo[2 * p2], 0x0b090a08);
                 const uint32_t lo2 = bfi(0x55555555u, pC, pR), hi2 = bfi(0x55555555u, pCo, pRo);
                 const uint32_t nib = bfi(0x33333333u, lo2, hi2);
                 if (j & 1) tacc[2 * (j >> 1) + p2] = (int)bfi(0xF0F0F0F0u, nib, (uint32_t)tacc[2 * (j >> 1) + p2]);
                 else tacc[2 * (j >> 1) + p2] = (int)nib;   // (the high nibbles are the odd column's, written next)
             }
+            if (j & 1) {
+                const int wa = tacc[j - 1], wb = tacc[j];
+                tacc[j - 1] = __builtin_amdgcn_perm(wb, wa, 0x05040100); tacc[j] = __builtin_amdgcn_perm(wb, wa, 0x07060302);
+            }
         }
         // the last cell of the column feeds the orthogonal border (scan_block.rs:1213-1214): two columns to a register
-        if (j & 1) { nvD[j >> 1] = __builtin_amdgcn_perm(dn[3], holdD, 0x07060302); nvR[j >> 1] = __builtin_amdgcn_perm(r[3], holdR, 0x07060302); }
-        else { holdD = dn[3]; holdR = r[3]; }
+        if (j >= 4) { nvD[j - 4] = __builtin_amdgcn_perm(dn[3], holdD[j - 4], 0x07060302); nvR[j - 4] = __builtin_amdgcn_perm(r[3], holdR[j - 4], 0x07060302); }
+        else { holdD[j] = dn[3]; holdR[j] = r[3]; }
     }
     if (TRACE) {
 #ifndef MQ_X_NOTRSTORE
@@ -232,7 +286,7 @@ __device__ __forceinline__ void multi_rect(const char* table, const FillConsts& 
     const int mm = vmax(vmax(dmax[0], dmax[1]), vmax(dmax[2], dmax[3]));
     const int m32 = max(mm & 0xffff, (int)((uint32_t)mm >> 16));   // halves are >= 0 (D_max starts at MIN = 0)
     o.mx = slot_last<SL>(SL == 16 ? wave_prefix_max16(m32) : (SL == 64 ? wave_prefix_max(m32) : wave_prefix_max32(m32)));
-    if constexpr (TRACE && SPM == 1) { zout[0] = (int)~zacc[0]; zout[1] = (int)~zacc[1]; }
+    if constexpr (TRACE && SPM == 1) { zout[0] = ~__builtin_amdgcn_perm((int)zacc[1], (int)zacc[0], 0x05040100); zout[1] = ~__builtin_amdgcn_perm((int)zacc[1], (int)zacc[0], 0x07060302); }
 }
 
 // Per wave and slot, in an L2-resident arena (BatchParams::big):
@@ -640,11 +694,15 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
                     A_d[k] = live ? mq_load(b + 4 * k) : 0; A_c[k] = live ? mq_load(b + ARR + 4 * k) : 0;
                     P_d[k] = live ? mq_load(b + 2 * ARR + 4 * k) : 0; P_r[k] = live ? mq_load(b + 3 * ARR + 4 * k) : 0;
                 }
+                cells_split(A_d); cells_split(A_c); cells_split(P_d); cells_split(P_r);   // the registers' order: cells k, k + 4 (see cells_split)
             }
             // While the slots run, the two buffers of every slot live in this wave's LDS region (the solo borders' space): the checkpoint
-            // (buffer `sel`) comes from the arena now and goes back after the loop; the other one is rewritten before every step.
+            // (buffer `sel`) comes from the arena now and goes back after the loop; the other one is rewritten before every step. Both hold a
+            // lane's cells in the registers' order.
             char* const lbuf = base + (uint32_t)g * (2u * BUFL);                 // this slot's buffers: + which * BUFL
-            int* const lsc = (int*)(base + MQ_LDS_SCALARS) + (uint32_t)g * MQ_LSC_INTS;   // their scalars: + which * 9; + 20: eight constants of the slot's pair
+            constexpr uint32_t MQ_LSC_STATE = 9u, MQ_LSC_PAIR = 20u;   // ints: a buffer's scalars (see above: [0] .. [8]); where the eight constants of the slot's pair start
+            static_assert(2u * MQ_LSC_STATE <= MQ_LSC_PAIR && MQ_LSC_PAIR + 8u <= MQ_LSC_INTS && (4u * MQ_LSC_PAIR) % 16u == 0 && (4u * MQ_LSC_INTS) % 16u == 0, "a slot's scalars in LDS");
+            int* const lsc = (int*)(base + MQ_LDS_SCALARS) + (uint32_t)g * MQ_LSC_INTS;   // their scalars: + which * MQ_LSC_STATE; + MQ_LSC_PAIR: eight constants of the slot's pair
             lds_sync();
             // (score-only kernels have the registers: there the values stay where they were -- 119.8 against 125.5 ms at config 3 without traceback)
             const unsigned long long qa_r = TRACE ? 0ull : (unsigned long long)(bp.pool + (live ? bp.q_off[pair] : 0ull)), ra_r = TRACE ? 0ull : (unsigned long long)(bp.pool + (live ? bp.r_off[pair] : 0ull));
@@ -653,8 +711,8 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
                 // what a step needs of its pair only at its start -- the two sequence images and their lengths, the trace slot -- is read from
                 // LDS in every step instead of living in seven registers through the columns
                 const unsigned long long qa = (unsigned long long)(bp.pool + (live ? bp.q_off[pair] : 0ull)), ra = (unsigned long long)(bp.pool + (live ? bp.r_off[pair] : 0ull));
-                *(int4*)(lsc + 20) = int4{(int)(uint32_t)qa, (int)(uint32_t)(qa >> 32), (int)(uint32_t)ra, (int)(uint32_t)(ra >> 32)};
-                *(int4*)(lsc + 24) = int4{live ? (int)bp.q_len[pair] : 0, live ? (int)bp.r_len[pair] : 0, (int)tslot, 0};
+                *(int4*)(lsc + MQ_LSC_PAIR) = int4{(int)(uint32_t)qa, (int)(uint32_t)(qa >> 32), (int)(uint32_t)ra, (int)(uint32_t)(ra >> 32)};
+                *(int4*)(lsc + MQ_LSC_PAIR + 4) = int4{live ? (int)bp.q_len[pair] : 0, live ? (int)bp.r_len[pair] : 0, (int)tslot, 0};
             }
             if (live) {
                 const char* cb = slot_mem + sel * BUFA;
@@ -662,29 +720,44 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
 #pragma unroll
                 for (int a = 0; a < 4; a++) {
                     const char* sp = cb + a * ARR + l * 16;
-                    *(int4*)(d + a * ARR) = int4{mq_load(sp), mq_load(sp + 4), mq_load(sp + 8), mq_load(sp + 12)};
+                    *(int4*)(d + a * ARR) = cells_split(int4{mq_load(sp), mq_load(sp + 4), mq_load(sp + 8), mq_load(sp + 12)});
                 }
-                if (l < 9) lsc[sel * 9u + l] = mq_load(cb + BUFL + 4 * l);
+                if ((uint32_t)l < MQ_LSC_STATE) lsc[sel * MQ_LSC_STATE + l] = mq_load(cb + BUFL + 4 * l);
             }
             lds_sync();
             // sequence bytes of the next step, fetched one step ahead for both possible directions
             uint2 pf_qv = {0, 0}, pf_rv = {0, 0}, pf_qc = {0, 0}, pf_rc = {0, 0}; bool pf_ok = false;
             bool leave = false;
             // the slot's registers and the scalars of the step at the top into the buffer `which` (see above)
-            auto stage = [&](uint32_t which, uint32_t s_i, uint32_t s_j, int s_off, uint32_t s_tt, uint32_t s_nb, int s_dir, int s_offadd, int s_corner) {
-                char* b = lbuf + which * BUFL + l * 16;
-                *(int4*)(b) = int4{A_d[0], A_d[1], A_d[2], A_d[3]}; *(int4*)(b + ARR) = int4{A_c[0], A_c[1], A_c[2], A_c[3]};
-                *(int4*)(b + 2 * ARR) = int4{P_d[0], P_d[1], P_d[2], P_d[3]}; *(int4*)(b + 3 * ARR) = int4{P_r[0], P_r[1], P_r[2], P_r[3]};
+            // (lb: the LDS address of this lane's 16 bytes of the slot's first array in buffer 0, ls: of the slot's scalars)
+            auto stage = [&](uint32_t lb, uint32_t ls, uint32_t which, uint32_t s_i, uint32_t s_j, int s_off, uint32_t s_tt, uint32_t s_nb, int s_dir, int s_offadd, int s_corner) {
+                typedef __attribute__((address_space(3))) lds_v4i* lds_int4_ptr;
+                typedef __attribute__((address_space(3))) int* lds_int_ptr;
+                const lds_int4_ptr b = (lds_int4_ptr)(uintptr_t)(lb + which * BUFL);
+                b[0] = lds_v4i{A_d[0], A_d[1], A_d[2], A_d[3]}; b[ARR / 16] = lds_v4i{A_c[0], A_c[1], A_c[2], A_c[3]};
+                b[2 * ARR / 16] = lds_v4i{P_d[0], P_d[1], P_d[2], P_d[3]}; b[3 * ARR / 16] = lds_v4i{P_r[0], P_r[1], P_r[2], P_r[3]};
                 if (l == 0) {
-                    int* sc = lsc + which * 9u;
+                    const lds_int_ptr sc = (lds_int_ptr)(uintptr_t)ls + which * MQ_LSC_STATE;
                     sc[0] = 1; sc[1] = (int)s_i; sc[2] = (int)s_j; sc[3] = s_off; sc[4] = (int)s_tt; sc[5] = (int)s_nb; sc[6] = s_dir; sc[7] = s_offadd; sc[8] = s_corner;
                 }
             };
+            const uint32_t base32 = (uint32_t)(uintptr_t)base;   // (the low word of a generic pointer into LDS is the LDS address)
             do {
                 // ---- the step every live slot is about to take (scan_block.rs:147-246)
                 const bool right = dir == DIR_RIGHT;
+                // (the lane's number, and with it the slot's two addresses in LDS: from the hardware's lane count in every step, not from kernel-wide
+                // values -- the allocator kept those in scratch memory and reloaded them here, each time behind every outstanding memory operation)
+                uint32_t lid;
+                asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lid));
+                const uint32_t l8 = (lid & (uint32_t)(SL - 1)) * 8u;
+                const uint32_t lbuf_s = base32 + (lid / (uint32_t)SL) * (2u * BUFL) + 2u * l8;
+                const uint32_t lsc_s = base32 + (uint32_t)MQ_LDS_SCALARS + (lid / (uint32_t)SL) * (4u * (uint32_t)MQ_LSC_INTS);
                 int4 cA = {0, 0, 0, 0}, cB = {0, 0, 0, 0};
-                if (TRACE) { cA = *(const int4*)(lsc + 20); cB = *(const int4*)(lsc + 24); }
+                if (TRACE) {
+                    typedef const __attribute__((address_space(3))) lds_v4i* lds_cint4_ptr;
+                    const lds_v4i a4 = *(lds_cint4_ptr)(uintptr_t)(lsc_s + 4u * MQ_LSC_PAIR), b4 = *(lds_cint4_ptr)(uintptr_t)(lsc_s + 4u * (MQ_LSC_PAIR + 4u));
+                    cA = int4{a4.x, a4.y, a4.z, a4.w}; cB = int4{b4.x, b4.y, b4.z, b4.w};
+                }
                 const uint8_t* const qp = TRACE ? (const uint8_t*)((unsigned long long)(uint32_t)cA.x | ((unsigned long long)(uint32_t)cA.y << 32)) : (const uint8_t*)qa_r;
                 const uint8_t* const rp = TRACE ? (const uint8_t*)((unsigned long long)(uint32_t)cA.z | ((unsigned long long)(uint32_t)cA.w << 32)) : (const uint8_t*)ra_r;
                 const uint32_t qlen = TRACE ? (uint32_t)cB.x : qlen_r, rlen = TRACE ? (uint32_t)cB.y : rlen_r;
@@ -701,17 +774,11 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
                 const int corner = (prev_dir != dir && prev_dir != DIR_GROW) ? sat16(D_corner + off_add) : 0;
                 // the state before the step: for a slot that leaves (its registers do not survive the step) and for the checkpoint
 #ifndef MQ_X_NOSTAGE
-                if (live) stage(sel ^ 1u, si, sj, off_n, trace_top, nblocks, dir, off_add, corner);
+                if (live) stage(lbuf_s, lsc_s, sel ^ 1u, si, sj, off_n, trace_top, nblocks, dir, off_add, corner);
 #endif
-                // (the lane's number inside its row: from the hardware's lane count in every step, not from a kernel-wide value -- the allocator
-                // kept that one, widened to 64 bits, in scratch memory and reloaded it before the prefetch and before the trace stores, each
-                // time behind every outstanding memory operation)
                 // (should the allocator keep the column code's per-lane constants in scratch memory after all: reloaded here, before the prefetch
                 // is issued, a reload waits for nothing but the previous step's stores)
                 asm volatile("" : "+v"(mc.laneKG), "+v"(mc.lanem1KG), "+v"(mc.w0));
-                uint32_t l8;
-                asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l8));
-                l8 = (l8 & (uint32_t)(SL - 1)) * 8u;
                 uint2 vb, cbv;
                 {
                     const uint8_t* Vp = right ? qp : rp; const uint8_t* Cp = right ? rp : qp;
@@ -793,7 +860,7 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
             } while (!__any(leave));
             // ---- every slot's state at the top of the loop to memory: the registers of the slots that took the step (the others'
             // was staged before it)
-            if (live && !leave) stage(sel ^ 1u, si, sj, 0, trace_top, nblocks, dir, 0, 0);
+            if (live && !leave) stage((uint32_t)(uintptr_t)(lbuf + l * 16), (uint32_t)(uintptr_t)lsc, sel ^ 1u, si, sj, 0, trace_top, nblocks, dir, 0, 0);
             lds_sync();
             if (live) {   // both buffers back to the arena (solo mode needs the LDS region, and reads a pair's state from the arena)
 #pragma unroll
@@ -801,8 +868,8 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
                     const char* sp = lbuf + w * BUFL + l * 16;
                     char* d = slot_mem + w * BUFA + l * 16;
 #pragma unroll
-                    for (int a = 0; a < 4; a++) *(int4*)(d + a * ARR) = *(const int4*)(sp + a * ARR);
-                    if (l < 9) *(int*)(slot_mem + w * BUFA + BUFL + 4 * l) = lsc[w * 9 + l];
+                    for (int a = 0; a < 4; a++) *(int4*)(d + a * ARR) = cells_join(*(const int4*)(sp + a * ARR));
+                    if ((uint32_t)l < MQ_LSC_STATE) *(int*)(slot_mem + w * BUFA + BUFL + 4 * l) = lsc[w * MQ_LSC_STATE + l];
                 }
             }
             lds_sync();
