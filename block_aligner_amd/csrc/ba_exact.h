@@ -29,6 +29,20 @@ constexpr uint32_t EXACT_NO_PAIR = 0xffffffffu;   // ExactParams::work: no pair 
 // that the sweep's whole chunks of 64 columns stay inside.
 BA_HD constexpr uint64_t exact_row_stride(uint32_t max_r) { return ((uint64_t)max_r + 2 * EXACT_BAND) & ~(uint64_t)(EXACT_BAND - 1); }
 
+// The traced form (ba_*_exact_cigars): four bits per cell, what the backward walk needs to know of it.
+constexpr uint32_t EXACT_TR_DIAG = 1;   // H[i][j] == H[i-1][j-1] + s(q_i, r_j)
+constexpr uint32_t EXACT_TR_HV = 2;     // H[i][j] == V[i][j]
+constexpr uint32_t EXACT_TR_VEXT = 4;   // V[i][j] == V[i-1][j] + extend
+constexpr uint32_t EXACT_TR_ZEXT = 8;   // Z[i][j] == Z[i][j-1] + extend
+// One wave's trace region, in dwords: per band of 64 rows, one dword per lane and eight steps of the skewed sweep (|r| + 63 steps at most).
+// A pair is traced while |q| * |r| <= EXACT_TRACE_MAX_CELLS; with |q| + |r| <= EXACT_MAX_LEN2 the region then stays below
+// (2^31 + 70 * 2^23) / 2 bytes = 1.28 GiB.
+constexpr uint64_t EXACT_TRACE_MAX_CELLS = (uint64_t)1 << 31;
+BA_HD constexpr uint32_t exact_trace_words(uint32_t r_len) { return (r_len + EXACT_BAND - 1 + 7) >> 3; }
+BA_HD constexpr uint64_t exact_trace_stride(uint32_t q_len, uint32_t r_len) {
+    return (uint64_t)((q_len + EXACT_BAND - 1) / EXACT_BAND) * EXACT_BAND * exact_trace_words(r_len);
+}
+
 // k_exact: persistent, one wave per pair. Record k of the launch is pair work[2k] of the batch's device order and goes to out[work[2k + 1]];
 // the records are sorted by |q| * |r|, largest first, and the waves take them in that order through *counter.
 struct ExactParams {
@@ -46,6 +60,11 @@ struct ExactParams {
     int32_t* rows;               // per wave of the launch row_stride entries of two words: {H, vertical-gap state}
     uint64_t row_stride;
     Exact* out;
+    // the traced form only: per wave trace_stride dwords of trace; record k's reversed runs go to rev + rev_off[k] (room for |q| + |r|)
+    // and their number to nrun[k]; eq: match-type columns are '=' / 'X' by the image bytes
+    uint32_t* trace; uint64_t trace_stride;
+    uint32_t* rev; const uint64_t* rev_off; uint32_t* nrun;
+    uint32_t eq;
 };
 
 }  // namespace ba

@@ -249,6 +249,14 @@ struct BaBatch {
     DevBuf ex_rows, ex_work, ex_out, ex_counter;
     hipEvent_t ev_x0 = nullptr, ev_x1 = nullptr;
     float exact_ms = 0; uint64_t exact_cells = 0;
+    // optimal paths (ba_batch_exact_cigars): the waves' trace regions, every record's reversed runs and where they start, the run counts,
+    // their offsets and the run array, allocated on the first call (they grow, never shrink). The request whose records, offsets and runs
+    // they hold is kept, so that the second call of the two-call pattern only copies.
+    DevBuf xt_trace, xt_rev, xt_rev_off, xt_nrun, xt_off, xt_runs;
+    float xt_ms = 0; uint64_t xt_cells = 0;
+    bool xt_valid = false; uint32_t xt_what = 0; int32_t xt_x_drop = 0; uint64_t xt_loads = 0;
+    std::vector<uint32_t> xt_devpos; std::vector<BaExact> xt_out; std::vector<uint64_t> xt_h_off;
+    uint64_t loads = 0;      // reloads so far
     TextState text;          // alignment strings (ba_batch_text)
     uint64_t runs_done = 0;  // finished runs: what the text sizes are kept for
     uint64_t compact_cap = 0, compact_used_cap = 0; bool compacted = false; uint32_t* compact_host = nullptr;
@@ -302,12 +310,13 @@ struct BaBatch {
     }
 };
 
-static int check_align_params(bool profile, Gaps g, size_t min_size, size_t max_size, int32_t x_drop, uint32_t mode, std::string* why) {
+// linear_ok: open == extend passes (batch_build: such a batch serves the exact calls only, batch_launch refuses it)
+static int check_align_params(bool profile, Gaps g, size_t min_size, size_t max_size, int32_t x_drop, uint32_t mode, std::string* why, bool linear_ok = false) {
     // scan_block.rs:847-862 (align) / 942-956 (align_profile: only the extend cost, which lives in the profile)
     if (profile) { if (!(g.extend < 0)) { *why = "Gap extend cost must be negative!"; return 1; } }
     else {
         if (!(g.open < 0 && g.extend < 0)) { *why = "Gap costs must be negative!"; return 1; }
-        if (!(g.open < g.extend)) { *why = "Gap open must cost more than gap extend!"; return 1; }
+        if (!(g.open < g.extend) && !(linear_ok && g.open == g.extend)) { *why = "Gap open must cost more than gap extend!"; return 1; }
     }
     if (!(min_size < 65535 && max_size < 65535)) { *why = "Block sizes must be smaller than 2^16 - 1!"; return 1; }
     if ((min_size & (min_size - 1)) || (max_size & (max_size - 1))) { *why = "Block sizes must be powers of two!"; return 1; }
@@ -865,7 +874,9 @@ static BaBatch* batch_build(int kind, const void* matrix, Gaps gaps, SizeRange s
     const bool profile = kind == BA_KIND_PROFILE_;
     const size_t min_size = size.min < 16 ? 16 : size.min, max_size = size.max < 16 ? 16 : size.max;   // clamp to L (scan_block.rs:853-854)
     std::string why;
-    if (check_align_params(profile, gaps, min_size, max_size, x_drop, mode, &why)) { fail("%s", why.c_str()); return nullptr; }
+    // (open == extend, a linear gap cost: the block kernels, as the reference, need open < extend, the exact full-matrix calls do not. Such a
+    // batch is built for ba_*_exact and ba_*_exact_cigars; a launch is refused with the reference's message. Not for extension batches.)
+    if (check_align_params(profile, gaps, min_size, max_size, x_drop, mode, &why, !ext)) { fail("%s", why.c_str()); return nullptr; }
     if (min_size > max_size) { fail("min block size exceeds max block size"); return nullptr; }
     if (profile && (mode & BA_CIGAR_EQ)) { fail("=/X CIGARs need two sequences; a profile alignment has none to compare"); return nullptr; }
     if (kind == BA_KIND_BYTES && (mode & BA_X_DROP)) { /* allowed by the reference, documented as inaccurate (scores.rs:235-239) */ }
@@ -1083,7 +1094,7 @@ static int batch_reload(BaBatch* b, size_t n, bool already_converted, GetSeq get
     std::vector<uint64_t> toff, boff;
     if (b->pipe && pipe_cut(b, P.ql.data(), P.rl.data(), n, 0, toff, boff)) return fail("reload: the new pairs' trace regions exceed the batch's trace arena");
     // from here on the device arrays change: a failure leaves no pairs loaded (a later launch says so) instead of a mix
-    b->n = 0; b->ran = false;
+    b->n = 0; b->ran = false; b->loads++;
     HIP_TRY(hipMemcpy(b->q_off.p, P.qo.data(), n * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(b->q_len.p, P.ql.data(), n * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(b->r_off.p, P.ro.data(), n * 8, hipMemcpyHostToDevice));
@@ -1199,6 +1210,8 @@ static int batch_launch(BaBatch* b) {
     if (b->in_flight) return fail("the batch already has a launch in flight (ba_batch_wait first)");
     b->compacted = false;
     if (b->n == 0) return fail("the batch holds no pairs (its last reload failed)");
+    if (!b->handle_mode && b->kind != BA_KIND_PROFILE_ && b->gap_open == b->gap_extend)
+        return fail("Gap open must cost more than gap extend! (a batch with open == extend serves the exact calls only)");
     HIP_TRY(hipSetDevice(b->device));
     if (b->bet_lost && batch_drop_class_bet(b)) return 1;
     if (!b->handle_mode) {   // (a handle's work counter arrives zeroed with its upload; it has no hand-off structures)
@@ -1686,6 +1699,15 @@ static int exact_check_lengths(const uint32_t* ql, const uint32_t* rl, size_t n,
                         ql[p], rl[p], (unsigned long long)ba::EXACT_MAX_LEN2);
     return 0;
 }
+static_assert(ba::EXACT_TRACE_MAX_CELLS == BA_EXACT_TRACE_MAX_CELLS, "BA_EXACT_TRACE_MAX_CELLS and ba::EXACT_TRACE_MAX_CELLS differ");
+static int exact_trace_check_lengths(const uint32_t* ql, const uint32_t* rl, size_t n, const uint32_t* name) {
+    if (exact_check_lengths(ql, rl, n, name)) return 1;
+    for (size_t p = 0; p < n; p++)
+        if ((uint64_t)ql[p] * rl[p] > ba::EXACT_TRACE_MAX_CELLS)
+            return fail("exact: pair %zu (|q| = %u, |r| = %u) is too large for a traced matrix: |q| * |r| may be %llu at most (BA_EXACT_TRACE_MAX_CELLS)",
+                        name ? (size_t)name[p] : p, ql[p], rl[p], (unsigned long long)ba::EXACT_TRACE_MAX_CELLS);
+    return 0;
+}
 static int exact_refusals(const BaBatch* b, uint32_t what, const void* out) {
     if (!out) return fail("null argument: out");
     if (what != BA_EXACT_GLOBAL && what != BA_EXACT_EXTEND) return fail("exact: unknown quantity %u (BA_EXACT_GLOBAL or BA_EXACT_EXTEND)", what);
@@ -1696,9 +1718,12 @@ static int exact_refusals(const BaBatch* b, uint32_t what, const void* out) {
     if (!b->n) return fail("exact: the batch holds no pairs (a reload failed)");
     return 0;
 }
-static int batch_exact_device(BaBatch* b, uint32_t what, int32_t x_drop, const uint32_t* devpos, size_t m, BaExact* out) {
+// traced: the paths too (ba_batch_exact_cigars) -- the record's runs are left on the device in b->xt_runs at the offsets of b->xt_off
+static int batch_exact_device(BaBatch* b, uint32_t what, int32_t x_drop, const uint32_t* devpos, size_t m, BaExact* out, bool traced = false) {
     if (exact_refusals(b, what, out)) return 1;
-    b->exact_ms = 0; b->exact_cells = 0;
+    float& ms_out = traced ? b->xt_ms : b->exact_ms;
+    uint64_t& cells_out = traced ? b->xt_cells : b->exact_cells;
+    ms_out = 0; cells_out = 0;
     if (!m) return 0;
     if (m > 0x7fffffffu) return fail("exact: too many records in one request");
     HIP_TRY(hipSetDevice(b->device));
@@ -1706,6 +1731,11 @@ static int batch_exact_device(BaBatch* b, uint32_t what, int32_t x_drop, const u
     HIP_TRY(hipMemcpy(ql.data(), b->q_len.p, (size_t)b->n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(rl.data(), b->r_len.p, (size_t)b->n * 4, hipMemcpyDeviceToHost));
     if (exact_check_lengths(ql.data(), rl.data(), b->n, b->h_order.empty() ? nullptr : b->h_order.data())) return 1;
+    if (traced)   // (the requested pairs only: the others need no region)
+        for (size_t k = 0; k < m; k++) {
+            const uint32_t d = devpos[k];
+            if (d != ba::EXACT_NO_PAIR && exact_trace_check_lengths(&ql[d], &rl[d], 1, b->h_order.empty() ? &d : &b->h_order[d])) return 1;
+        }
     auto cost = [&](uint32_t k) { const uint32_t d = devpos[k]; return d == ba::EXACT_NO_PAIR ? 0ull : (uint64_t)ql[d] * rl[d]; };
     std::vector<uint32_t> rec(m);
     for (size_t k = 0; k < m; k++) rec[k] = (uint32_t)k;
@@ -1728,7 +1758,50 @@ static int batch_exact_device(BaBatch* b, uint32_t what, int32_t x_drop, const u
     }
     first.push_back((uint32_t)m);
     const size_t launches = first.size() - 1;
-    const uint32_t wgs = (uint32_t)std::min<uint64_t>(max_wgs, (std::min<uint64_t>(m, first[1]) + ba::EXACT_WAVES - 1) / ba::EXACT_WAVES);   // (the first launch is the largest)
+    uint32_t wgs = (uint32_t)std::min<uint64_t>(max_wgs, (std::min<uint64_t>(m, first[1]) + ba::EXACT_WAVES - 1) / ba::EXACT_WAVES);   // (the first launch is the largest)
+    uint32_t tr_waves = 0;
+    uint64_t tr_stride = 0;
+    std::vector<uint64_t> rev_off;
+    if (traced) {
+        // every record's reversed runs (|q| + |r| at most), the counts and the offsets first; the trace regions take what is left
+        rev_off.resize(m + 1);
+        rev_off[0] = 0;
+        for (size_t k = 0; k < m; k++) {
+            const uint32_t d = devpos[k];
+            rev_off[k + 1] = rev_off[k] + (d == ba::EXACT_NO_PAIR ? 0ull : (uint64_t)ql[d] + rl[d]);
+            if (d != ba::EXACT_NO_PAIR) tr_stride = std::max(tr_stride, ba::exact_trace_stride(ql[d], rl[d]));
+        }
+        tr_stride = std::max<uint64_t>(tr_stride, 64);
+        const uint64_t rev_bytes = std::max<uint64_t>(rev_off[m], 1) * 4;
+        if (b->xt_rev.bytes < rev_bytes) {
+            size_t free_b = 0, total_b = 0;
+            mem_info(&free_b, &total_b);
+            if (rev_bytes > free_b + b->xt_rev.bytes)
+                return fail("exact: the runs of the request need %llu bytes of device memory before they are merged (4 x the sum of |q| + |r|), %zu are free",
+                            (unsigned long long)rev_bytes, free_b + b->xt_rev.bytes);
+            if (b->xt_rev.alloc(rev_bytes)) return 1;
+        }
+        if (b->xt_rev_off.bytes < (m + 1) * 8 && b->xt_rev_off.alloc((m + 1) * 8)) return 1;
+        if (b->xt_nrun.bytes < m * 4 && b->xt_nrun.alloc(m * 4)) return 1;
+        if (b->xt_off.bytes < (m + 1) * 8 && b->xt_off.alloc((m + 1) * 8)) return 1;
+        // as many concurrent waves as free memory holds regions of the largest pair (a sixteenth is left for the run array), one at least
+        const uint64_t region = tr_stride * 4;
+        uint32_t want = wgs * ba::EXACT_WAVES;
+        if (b->xt_trace.bytes < want * region) {
+            size_t free_b = 0, total_b = 0;
+            mem_info(&free_b, &total_b);
+            const uint64_t avail = (uint64_t)free_b + b->xt_trace.bytes;
+            const uint64_t fit = (avail - avail / 16) / region;
+            if (!fit)
+                return fail("exact: one trace region needs %llu bytes of device memory (the request's largest pair at 4 bits per cell), %llu are free",
+                            (unsigned long long)region, (unsigned long long)avail);
+            want = (uint32_t)std::min<uint64_t>(want, fit);
+            if (want >= ba::EXACT_WAVES) want -= want % ba::EXACT_WAVES;
+            if (b->xt_trace.bytes < want * region && b->xt_trace.alloc(want * region)) return 1;
+        }
+        tr_waves = want;
+        wgs = (tr_waves + ba::EXACT_WAVES - 1) / ba::EXACT_WAVES;
+    }
     const uint64_t stride = ba::exact_row_stride(max_r), row_bytes = (uint64_t)wgs * ba::EXACT_WAVES * stride * 8;
     if (b->ex_rows.bytes < row_bytes) {
         size_t free_b = 0, total_b = 0;
@@ -1751,35 +1824,87 @@ static int batch_exact_device(BaBatch* b, uint32_t what, int32_t x_drop, const u
     xp.pool = b->pool.as<uint8_t>(); xp.q_off = b->q_off.as<uint64_t>(); xp.q_len = b->q_len.as<uint32_t>();
     xp.r_off = b->r_off.as<uint64_t>(); xp.r_len = b->r_len.as<uint32_t>();
     xp.rows = b->ex_rows.as<int32_t>(); xp.row_stride = stride; xp.out = b->ex_out.as<ba::Exact>();
+    if (traced) {
+        HIP_TRY(hipMemcpy(b->xt_rev_off.p, rev_off.data(), (m + 1) * 8, hipMemcpyHostToDevice));
+        xp.trace = b->xt_trace.as<uint32_t>(); xp.trace_stride = tr_stride;
+        xp.rev = b->xt_rev.as<uint32_t>(); xp.rev_off = b->xt_rev_off.as<uint64_t>(); xp.nrun = b->xt_nrun.as<uint32_t>();
+        xp.eq = (b->mode & BA_CIGAR_EQ) ? 1u : 0u;
+    }
     HIP_TRY(hipEventRecord(b->ev_x0, b->stream));
     for (size_t l = 0; l < launches; l++) {
         xp.n = first[l + 1] - first[l];
         xp.work = b->ex_work.as<uint32_t>() + 2 * (size_t)first[l];
         xp.counter = b->ex_counter.as<uint32_t>() + l;
-        HIP_TRY(ba_launch_exact(b->stream, &xp, std::min<uint32_t>(wgs, (xp.n + ba::EXACT_WAVES - 1) / ba::EXACT_WAVES)));
+        if (traced) {
+            uint32_t waves = std::min<uint32_t>(tr_waves, xp.n);
+            if (waves >= ba::EXACT_WAVES) waves -= waves % ba::EXACT_WAVES;
+            HIP_TRY(ba_launch_exact_trace(b->stream, &xp, waves));
+        } else
+            HIP_TRY(ba_launch_exact(b->stream, &xp, std::min<uint32_t>(wgs, (xp.n + ba::EXACT_WAVES - 1) / ba::EXACT_WAVES)));
+    }
+    if (traced) {   // sizes -> offsets -> one run array, in record order
+        HIP_TRY(ba_launch_offsets(b->stream, b->xt_nrun.as<uint32_t>(), b->xt_off.as<uint64_t>(), (uint32_t)m));
+        uint64_t total = 0;
+        HIP_TRY(hipMemcpyAsync(&total, b->xt_off.as<uint64_t>() + m, 8, hipMemcpyDeviceToHost, b->stream));
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        if (b->xt_runs.bytes < total * 4 && b->xt_runs.alloc(total * 4)) return 1;
+        HIP_TRY(ba_launch_exact_runs(b->stream, b->xt_rev.as<uint32_t>(), b->xt_rev_off.as<uint64_t>(), b->xt_nrun.as<uint32_t>(), b->xt_off.as<uint64_t>(),
+                                     b->xt_runs.as<uint32_t>(), (uint32_t)m));
     }
     HIP_TRY(hipEventRecord(b->ev_x1, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
-    HIP_TRY(hipEventElapsedTime(&b->exact_ms, b->ev_x0, b->ev_x1));
+    HIP_TRY(hipEventElapsedTime(&ms_out, b->ev_x0, b->ev_x1));
     HIP_TRY(hipMemcpy(out, b->ex_out.p, m * sizeof(ba::Exact), hipMemcpyDeviceToHost));
     cells = 0;
     for (size_t k = 0; k < m; k++) if (devpos[k] != ba::EXACT_NO_PAIR) cells += (uint64_t)out[k].rows * ((uint64_t)rl[devpos[k]] + 1);
-    b->exact_cells = cells;
+    cells_out = cells;
     return 0;
 }
 // `which` (null: every pair) in the caller's order -> device positions
-static int batch_exact(BaBatch* b, uint32_t what, int32_t x_drop, const uint32_t* which, size_t n_which, BaExact* out) {
-    if (!b) return fail("null batch");
-    if (exact_refusals(b, what, out)) return 1;
+static int exact_devpos(const BaBatch* b, const uint32_t* which, size_t n_which, std::vector<uint32_t>& devpos) {
     const size_t m = which ? n_which : b->n;
-    std::vector<uint32_t> dev_of, devpos(m);
+    std::vector<uint32_t> dev_of;
+    devpos.resize(m);
     if (!b->h_order.empty()) { dev_of.resize(b->n); for (uint32_t s = 0; s < b->n; s++) dev_of[b->h_order[s]] = s; }
     for (size_t k = 0; k < m; k++) {
         const uint32_t p = which ? which[k] : (uint32_t)k;
         if (p >= b->n) return fail("exact: which[%zu] = %u is out of range (the batch holds %u pairs)", k, p, b->n);
         devpos[k] = dev_of.empty() ? p : dev_of[p];
     }
-    return batch_exact_device(b, what, x_drop, devpos.data(), m, out);
+    return 0;
+}
+static int batch_exact(BaBatch* b, uint32_t what, int32_t x_drop, const uint32_t* which, size_t n_which, BaExact* out) {
+    if (!b) return fail("null batch");
+    if (exact_refusals(b, what, out)) return 1;
+    std::vector<uint32_t> devpos;
+    if (exact_devpos(b, which, n_which, devpos)) return 1;
+    return batch_exact_device(b, what, x_drop, devpos.data(), devpos.size(), out);
+}
+// The records, the run offsets (records + 1) and, with `runs`, the runs. A request equal to the last one on the same pairs is answered from
+// what that one left on the device.
+static int batch_exact_cigars(BaBatch* b, uint32_t what, int32_t x_drop, const uint32_t* which, size_t n_which, BaExact* out, uint64_t* run_off, uint32_t* runs,
+                              uint64_t capacity) {
+    if (!b) return fail("null batch");
+    if (!run_off) return fail("null argument: run_off");
+    if (exact_refusals(b, what, out)) return 1;
+    std::vector<uint32_t> devpos;
+    if (exact_devpos(b, which, n_which, devpos)) return 1;
+    const size_t m = devpos.size();
+    const bool kept = b->xt_valid && b->xt_what == what && b->xt_x_drop == x_drop && b->xt_loads == b->loads && b->xt_devpos == devpos;
+    if (!kept) {
+        b->xt_valid = false;
+        b->xt_out.assign(m, BaExact{}); b->xt_h_off.assign(m + 1, 0);
+        if (batch_exact_device(b, what, x_drop, devpos.data(), m, b->xt_out.data(), true)) return 1;
+        if (m) HIP_TRY(hipMemcpy(b->xt_h_off.data(), b->xt_off.p, (m + 1) * 8, hipMemcpyDeviceToHost));
+        b->xt_what = what; b->xt_x_drop = x_drop; b->xt_loads = b->loads; b->xt_devpos = devpos; b->xt_valid = true;
+    } else HIP_TRY(hipSetDevice(b->device));
+    std::copy(b->xt_out.begin(), b->xt_out.end(), out);
+    std::copy(b->xt_h_off.begin(), b->xt_h_off.end(), run_off);
+    if (!runs) return 0;
+    const uint64_t total = b->xt_h_off[m];
+    if (capacity < total) return fail("exact: the runs buffer holds %llu runs, the request has %llu", (unsigned long long)capacity, (unsigned long long)total);
+    if (total) HIP_TRY(hipMemcpy(runs, b->xt_runs.p, total * 4, hipMemcpyDeviceToHost));
+    return 0;
 }
 static int extend_exact(BaExtendBatch* e, int32_t x_drop, const uint32_t* which, size_t n_which, BaExact* left, BaExact* right, int32_t* score) {
     if (!e) return fail("null batch");
@@ -2125,6 +2250,20 @@ int ba_batch_exact_ms(BaBatch* b, float* ms, uint64_t* cells) {
     if (ms) *ms = b->exact_ms;
     if (cells) *cells = b->exact_cells;
     return 0;
+}
+int ba_batch_exact_cigars(BaBatch* b, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, BaExact* out, uint64_t* run_off, uint32_t* runs,
+                          uint64_t capacity) {
+    return batch_exact_cigars(b, what, x_drop, which, n_which, out, run_off, runs, capacity);
+}
+int ba_batch_exact_cigars_ms(BaBatch* b, float* ms, uint64_t* cells) {
+    if (!b) return fail("null batch");
+    if (ms) *ms = b->xt_ms;
+    if (cells) *cells = b->xt_cells;
+    return 0;
+}
+int ba_exact_trace_check_lengths(const uint32_t* q_len, const uint32_t* r_len, uintptr_t n) {
+    if (n && (!q_len || !r_len)) return fail("null argument");
+    return exact_trace_check_lengths(q_len, r_len, n, nullptr);
 }
 int ba_exact_check_lengths(const uint32_t* q_len, const uint32_t* r_len, uintptr_t n) {
     if (n && (!q_len || !r_len)) return fail("null argument");
@@ -2609,6 +2748,44 @@ static int parts_exact(BaPartSet* m, uint32_t what, int32_t x_drop, const uint32
     }
     return 0;
 }
+// ... and its own paths: the parts' offsets become run counts in the caller's order, then offsets; with `runs`, every part's runs are
+// scattered to them (a part answers that second call from its device buffers)
+static int parts_exact_cigars(BaPartSet* m, uint32_t what, int32_t x_drop, const uint32_t* which, size_t n_which, BaExact* out, uint64_t* run_off,
+                              uint32_t* runs, uint64_t capacity) {
+    if (!m) return fail("null batch");
+    if (!out) return fail("null argument: out");
+    if (!run_off) return fail("null argument: run_off");
+    const size_t cnt = which ? n_which : m->n;
+    std::vector<uint32_t> part_of(m->n), local_of(m->n);
+    for (size_t k = 0; k < m->part.size(); k++)
+        for (size_t i = 0; i < m->pos[k].size(); i++) { part_of[m->pos[k][i]] = (uint32_t)k; local_of[m->pos[k][i]] = (uint32_t)i; }
+    std::vector<std::vector<uint32_t>> local(m->part.size()), at(m->part.size());
+    for (size_t k = 0; k < cnt; k++) {
+        const uint32_t p = which ? which[k] : (uint32_t)k;
+        if (p >= m->n) return fail("exact: which[%zu] = %u is out of range (the batch holds %zu pairs)", k, p, m->n);
+        local[part_of[p]].push_back(local_of[p]); at[part_of[p]].push_back((uint32_t)k);
+    }
+    std::vector<BaExact> tmp;
+    std::vector<std::vector<uint64_t>> po(m->part.size());
+    std::fill(run_off, run_off + cnt + 1, 0);
+    for (size_t k = 0; k < m->part.size(); k++) {
+        if (local[k].empty()) continue;
+        tmp.resize(local[k].size()); po[k].resize(local[k].size() + 1);
+        if (batch_exact_cigars(m->part[k].get(), what, x_drop, local[k].data(), local[k].size(), tmp.data(), po[k].data(), nullptr, 0)) return 1;
+        for (size_t i = 0; i < tmp.size(); i++) { out[at[k][i]] = tmp[i]; run_off[at[k][i] + 1] = po[k][i + 1] - po[k][i]; }
+    }
+    for (size_t k = 0; k < cnt; k++) run_off[k + 1] += run_off[k];
+    if (!runs) return 0;
+    if (capacity < run_off[cnt]) return fail("exact: the runs buffer holds %llu runs, the request has %llu", (unsigned long long)capacity, (unsigned long long)run_off[cnt]);
+    std::vector<uint32_t> pr;
+    for (size_t k = 0; k < m->part.size(); k++) {
+        if (local[k].empty()) continue;
+        tmp.resize(local[k].size()); pr.resize((size_t)std::max<uint64_t>(po[k].back(), 1));
+        if (batch_exact_cigars(m->part[k].get(), what, x_drop, local[k].data(), local[k].size(), tmp.data(), po[k].data(), pr.data(), po[k].back())) return 1;
+        for (size_t i = 0; i < tmp.size(); i++) std::copy(pr.begin() + po[k][i], pr.begin() + po[k][i + 1], runs + run_off[at[k][i]]);
+    }
+    return 0;
+}
 static int parts_text(BaPartSet* m, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) {   // sized per part, then rendered per part
     if (!m) return fail("null batch");
     if (!offsets) return fail("null argument: offsets");
@@ -2729,6 +2906,10 @@ int ba_multibatch_results(BaMultiBatch* m, int32_t* score, uint32_t* qi, uint32_
 }
 int ba_multibatch_cigars(BaMultiBatch* m, uint32_t* runs, uint64_t capacity) { return parts_cigars(m, runs, capacity); }
 int ba_multibatch_stats(BaMultiBatch* m, BaAlignStats* out) { return parts_stats(m, out); }
+int ba_multibatch_exact_cigars(BaMultiBatch* m, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, BaExact* out, uint64_t* run_off,
+                               uint32_t* runs, uint64_t capacity) {
+    return parts_exact_cigars(m, what, x_drop, which, n_which, out, run_off, runs, capacity);
+}
 int ba_multibatch_exact(BaMultiBatch* m, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, BaExact* out) { return parts_exact(m, what, x_drop, which, n_which, out); }
 int ba_multibatch_text(BaMultiBatch* m, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) { return parts_text(m, what, offsets, text, capacity); }
 int ba_multibatch_kernel_ms(BaMultiBatch* m, float* ms, int capacity) {   // per slice, of the last run; returns the number of slices
@@ -2843,6 +3024,10 @@ int ba_sized_batch_results(BaSizedBatch* m, int32_t* score, uint32_t* qi, uint32
 }
 int ba_sized_batch_cigars(BaSizedBatch* m, uint32_t* runs, uint64_t capacity) { return parts_cigars(m, runs, capacity); }
 int ba_sized_batch_stats(BaSizedBatch* m, BaAlignStats* out) { return parts_stats(m, out); }
+int ba_sized_batch_exact_cigars(BaSizedBatch* m, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, BaExact* out, uint64_t* run_off,
+                                uint32_t* runs, uint64_t capacity) {
+    return parts_exact_cigars(m, what, x_drop, which, n_which, out, run_off, runs, capacity);
+}
 int ba_sized_batch_exact(BaSizedBatch* m, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, BaExact* out) { return parts_exact(m, what, x_drop, which, n_which, out); }
 int ba_sized_batch_text(BaSizedBatch* m, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) { return parts_text(m, what, offsets, text, capacity); }
 int ba_sized_batch_classes(BaSizedBatch* m, SizeRange* ranges, uint64_t* counts, int32_t* kernels, float* kernel_ms, int capacity) {   // the bins; returns their number

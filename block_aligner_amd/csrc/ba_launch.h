@@ -70,8 +70,12 @@ hipError_t ba_launch_stats(hipStream_t s, const ba::StatsParams* sp);
 hipError_t ba_launch_stats_extend(hipStream_t s, const ba::ExtendParams* ep, const ba::AlignStats* side, ba::AlignStats* out);
 // ba_exact.hip
 hipError_t ba_launch_exact(hipStream_t s, const ba::ExactParams* xp, uint32_t wgs);
+hipError_t ba_launch_exact_trace(hipStream_t s, const ba::ExactParams* xp, uint32_t waves);
+hipError_t ba_launch_exact_runs(hipStream_t s, const uint32_t* rev, const uint64_t* rev_off, const uint32_t* nrun, const uint64_t* off, uint32_t* runs,
+                                uint32_t m);
 hipError_t ba_launch_exact_seed(hipStream_t s, const ba::ExtendParams* ep, const uint32_t* which, uint32_t m, int32_t* out);
 // ba_text.hip
 hipError_t ba_launch_text_len(hipStream_t s, const ba::TextParams* tp);
 hipError_t ba_launch_text_write(hipStream_t s, const ba::TextParams* tp);
+hipError_t ba_launch_offsets(hipStream_t s, const uint32_t* len, uint64_t* offsets, uint32_t n);   // k_text_offsets on its own
 }

@@ -247,6 +247,11 @@ extern "C" hipError_t ba_launch_text_len(hipStream_t s, const ba::TextParams* tp
     k_text_offsets<<<dim3(1), dim3(1024), 0, s>>>(tp->len, tp->offsets, tp->n);
     return hipGetLastError();
 }
+// the scan on its own (the exact paths' run offsets): offsets[0 .. n] of len[0 .. n)
+extern "C" hipError_t ba_launch_offsets(hipStream_t s, const uint32_t* len, uint64_t* offsets, uint32_t n) {
+    k_text_offsets<<<dim3(1), dim3(1024), 0, s>>>(len, offsets, n);
+    return hipGetLastError();
+}
 extern "C" hipError_t ba_launch_text_write(hipStream_t s, const ba::TextParams* tp) {
     if (!tp->n) return hipSuccess;
     const uint32_t wgs = (tp->n + TEXT_WAVES - 1) / TEXT_WAVES;

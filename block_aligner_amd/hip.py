@@ -72,6 +72,7 @@ EXACT_DTYPE = np.dtype(ExactC)
 if C.sizeof(ExactC) != 16 or EXACT_DTYPE.itemsize != 16:
     raise ImportError(f"struct BaExact must be 16 bytes, the binding declares {C.sizeof(ExactC)}")
 EXACT_GLOBAL, EXACT_EXTEND = 0, 1   # ba_*_exact: the quantity
+EXACT_TRACE_MAX_CELLS = 1 << 31     # ba_*_exact_cigars: |q| * |r| of a pair
 
 
 def _text_list(buf, off):
@@ -191,7 +192,10 @@ def lib() -> C.CDLL:
             getattr(L, f"{f}_destroy").argtypes = [vp]
         for f in ("ba_batch", "ba_sized_batch", "ba_multibatch"):
             getattr(L, f"{f}_exact").argtypes = [vp, u32, i32, vp, sz, vp]
+            getattr(L, f"{f}_exact_cigars").argtypes = [vp, u32, i32, vp, sz, vp, vp, vp, C.c_uint64]
         L.ba_extend_batch_exact.argtypes = [vp, i32, vp, sz, vp, vp, vp]
+        L.ba_batch_exact_cigars_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+        L.ba_exact_trace_check_lengths.argtypes = [vp, vp, sz]
         L.ba_batch_exact_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
         L.ba_exact_check_lengths.argtypes = [vp, vp, sz]
         L.ba_accuracy_summary.argtypes = [vp, vp, vp, vp, vp, sz, C.POINTER(AccuracyC)]
@@ -293,6 +297,15 @@ def accuracy_summary(score, exact, query_idx=None, reference_idx=None, status=No
     if lib().ba_accuracy_summary(score.ctypes.data, *_ptrs(opt), rec.ctypes.data, n, C.byref(out)):
         raise RuntimeError(last_error())
     return {k: getattr(out, k) for k, _ in AccuracyC._fields_}
+
+
+def exact_trace_check_lengths(q_len, r_len) -> None:
+    """The length guards of exact_cigars() on their own (needs no device): exact_check_lengths' and |q| * |r| <= EXACT_TRACE_MAX_CELLS."""
+    q_len, r_len = np.ascontiguousarray(q_len, np.uint32), np.ascontiguousarray(r_len, np.uint32)
+    if len(q_len) != len(r_len):
+        raise ValueError("q_len and r_len must have one entry per pair")
+    if lib().ba_exact_trace_check_lengths(q_len.ctypes.data, r_len.ctypes.data, len(q_len)):
+        raise RuntimeError(last_error())
 
 
 def exact_check_lengths(q_len, r_len) -> None:
@@ -554,6 +567,20 @@ class _Batch:
         self._call("exact", int(what), int(x_drop), wp, wn, rec.ctypes.data)
         return {k: rec[k].copy() for k in EXACT_DTYPE.names}
 
+    def exact_cigars(self, what=None, x_drop=-1, which=None):
+        """The optimal alignment paths of the exact full-matrix DP, computed on the device (ba_*_exact_cigars; no run needed) -> (records as
+        exact(), runs, off): runs[off[k]:off[k + 1]] are record k's packed (len << 4 | op) runs, in the format of cigars(); '=' / 'X' in a
+        CIGAR_EQ batch, 'M' otherwise. what, x_drop and which as in exact()."""
+        if what is None:
+            what = EXACT_EXTEND if self.mode & X_DROP else EXACT_GLOBAL
+        w, wp, wn = _which(which)
+        m = self.n if w is None else wn
+        rec, off = np.zeros(m, EXACT_DTYPE), np.zeros(m + 1, np.uint64)   # the two-call pattern: records and offsets, then the runs
+        self._call("exact_cigars", int(what), int(x_drop), wp, wn, rec.ctypes.data, off.ctypes.data, None, 0)
+        runs = np.zeros(int(off[-1]), np.uint32)
+        self._call("exact_cigars", int(what), int(x_drop), wp, wn, rec.ctypes.data, off.ctypes.data, runs.ctypes.data, runs.size)
+        return {k: rec[k].copy() for k in EXACT_DTYPE.names}, runs, off
+
     def accuracy(self, x_drop=-1, which=None):
         """After a run: the batch's results against exact() of the same pairs (accuracy_summary) -> dict."""
         ex = self.exact(None, x_drop, which)
@@ -649,6 +676,12 @@ class BatchAligner(_Batch):
         """(HIP-event milliseconds, cells) of the last exact() call: cells = the sum of rows * (|r| + 1) over the request."""
         ms, cells = C.c_float(), C.c_uint64()
         self._call("exact_ms", C.byref(ms), C.byref(cells))
+        return ms.value, int(cells.value)
+
+    def exact_cigars_ms(self):
+        """(HIP-event milliseconds, cells) of the last exact_cigars() call that computed: sweep, walk, offsets and gather."""
+        ms, cells = C.c_float(), C.c_uint64()
+        self._call("exact_cigars_ms", C.byref(ms), C.byref(cells))
         return ms.value, int(cells.value)
 
     def text_ms(self) -> float:
@@ -795,6 +828,10 @@ class ExtendBatchAligner(_Batch):
         a = self._arrays(pool, q_off, q_len, r_off, r_len, q_seed, r_seed, seed_len, strand)
         self._call("reload", *_ptrs(a), len(a[2]))
         self.n = len(a[2])
+
+    @property
+    def exact_cigars(self):
+        raise AttributeError("extension batches have no exact_cigars (exact paths are out of scope for them: INTEGRATION.md)")
 
     def exact(self, x_drop=-1, which=None):
         """EXACT_EXTEND on both sides of every seed (ba_extend_batch_exact; no run needed) -> dict: left and right (dicts of arrays score,

@@ -435,6 +435,53 @@ int ba_extend_batch_exact(BaExtendBatch* batch, int32_t x_drop, const uint32_t* 
                           struct BaExact* right, int32_t* score);
 /* The length guard of the exact calls on its own (host only, no device): nonzero, naming the pair, if a pair is too long for int32 scores. */
 int ba_exact_check_lengths(const uint32_t* q_len, const uint32_t* r_len, uintptr_t n_pairs);
+/* ---- optimal alignment paths of the exact full-matrix DP ("Exact scores and accuracy").
+ *
+ * The calls above say how far a block range is from the optimum; these return the optimum's alignment, as packed CIGAR runs of the traced
+ * batches' format (length << 4 | op, ba_batch_cigars), for the same `what`, `x_drop` and `which`. The records are those of ba_*_exact.
+ *
+ * Definition. H is the matrix above. V[i][j] is the best score ending in a gap that consumes the query (CIGAR I), Z[i][j] the best score
+ * ending in a gap that consumes the reference (D); for i, j >= 1
+ *     V[i][j] = max(H[i-1][j] + open, V[i-1][j] + extend)        Z[i][j] = max(H[i][j-1] + open, Z[i][j-1] + extend)
+ * and V and Z are "no cell" (minus infinity) in row 0 and column 0. The path ends at the record's cell (query_idx, reference_idx) -- (|q|, |r|)
+ * for BA_EXACT_GLOBAL, the argmax under the tie rule above for BA_EXACT_EXTEND, with or without x_drop -- and starts at (0, 0). It is walked
+ * backwards from the end cell, starting in state H:
+ *   state H at (i, j):  i == 0: emit D x j and stop.  j == 0: emit I x i and stop.
+ *                       else if H[i][j] == H[i-1][j-1] + s(q_i, r_j): emit one match-type column, go to (i-1, j-1), state H;
+ *                       else if H[i][j] == V[i][j]: go to state V;  else: go to state Z.
+ *   state V at (i, j):  emit I. If V[i][j] == V[i-1][j] + extend: go to (i-1, j), state V (extension is preferred); else to (i-1, j), state H.
+ *   state Z at (i, j):  emit D. If Z[i][j] == Z[i][j-1] + extend: go to (i, j-1), state Z; else to (i, j-1), state H.
+ * The runs are returned in alignment order, adjacent runs of one op merged (score-neutral: with open < extend the rule never closes and
+ * reopens a gap at one cell, with open == extend the cost is linear). Match-type columns are M; in a BA_CIGAR_EQ batch they are = where the
+ * two image bytes are equal and X elsewhere (the rule of the statistics' `matches`). A record with score 0 at (0, 0) has no runs, and so has
+ * the record of an empty side in an extension batch's sense. Rescoring the runs (the matrix per match-type column, open + (n - 1) extend
+ * per gap run) gives exactly `score`; they consume exactly query_idx query and reference_idx reference positions.
+ *
+ * Two-call pattern, as ba_batch_text: out (records) and run_off (records + 1 run offsets) are always filled. runs == NULL stops there; a runs
+ * buffer of fewer than run_off[records] entries is refused with the count needed, the offsets still filled. A call with the arguments of the
+ * one before it on the same batch, and no reload between them, copies what that call left on the device and computes nothing.
+ *
+ * Linear gap costs: ba_batch_create (and the sized and multi-device creates) accept open == extend for sequence matrices. Such a batch serves
+ * ba_*_exact and ba_*_exact_cigars only: the block kernels, as the reference, need open < extend, and run / launch on it is refused with
+ * "Gap open must cost more than gap extend!". Extension batches and the Block handles refuse open == extend as before.
+ *
+ * Refusals: those of ba_*_exact, null run_off, and a requested pair with |q| * |r| > BA_EXACT_TRACE_MAX_CELLS (the message names the pair). The
+ * sweep keeps four bits per cell in a trace region per resident wave, sized for the largest requested pair (with the length limit above, below
+ * 1.3 GiB); as many waves run at once as free device memory holds regions, one at least, and a request whose single region does not fit is
+ * refused with the bytes needed. Every record's runs wait, unmerged with their neighbours' offsets, in 4 * (|q| + |r|) bytes until the offsets
+ * are known. The buffers are allocated on the first call, grow, and are freed by destroy. Extension batches have no such call. */
+#define BA_EXACT_TRACE_MAX_CELLS 2147483648ull   /* 2^31 */
+int ba_batch_exact_cigars(BaBatch* batch, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, struct BaExact* out,
+                          uint64_t* run_off, uint32_t* runs, uint64_t capacity);
+/* every part computes its own pairs (a multi-device batch: on its own device) */
+int ba_sized_batch_exact_cigars(BaSizedBatch* batch, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, struct BaExact* out,
+                                uint64_t* run_off, uint32_t* runs, uint64_t capacity);
+int ba_multibatch_exact_cigars(BaMultiBatch* batch, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, struct BaExact* out,
+                               uint64_t* run_off, uint32_t* runs, uint64_t capacity);
+/* HIP-event time (ms; sweep, walk, offsets and gather) and cells of the last ba_batch_exact_cigars call that computed; either may be NULL */
+int ba_batch_exact_cigars_ms(BaBatch* batch, float* ms, uint64_t* cells);
+/* The length guards of the path calls on their own (host only, no device): ba_exact_check_lengths' and |q| * |r| <= BA_EXACT_TRACE_MAX_CELLS. */
+int ba_exact_trace_check_lengths(const uint32_t* q_len, const uint32_t* r_len, uintptr_t n_pairs);
 /* Host only, no device: the results of a run against exact records of the same pairs. Pairs whose status has an overflow, lost or watchdog
  * bit are skipped; diff = exact - score over the others; wrong counts diff != 0, below diff > 0 (the heuristic missed the optimum), above
  * diff < 0; diff_end counts compared pairs whose end cell differs; mean_rel_error is the mean of diff / |exact| over the wrong pairs with
