@@ -1678,6 +1678,7 @@ struct Aligner {
             restore_ckpt_borders(prev_size);
             trace_top = ub_tt; nblocks = ub_nb; park<3>(parked, (int)ub_tt); park<4>(parked, (int)ub_nb);
             y_drop_iter = 0; pf_ok = false;
+            park<14>(parked, 0);   // (end clip: a traced kernel clips inside chains only, and this one is computed again in full)
         };
         BA_TSTAMP(tr0);
         BA_TADD(prof, 47, tq0, tr0);
@@ -1761,6 +1762,19 @@ struct Aligner {
             BA_TSTAMP(tsb);
             const uint32_t tb = trace_top;
             const bool spec = TRACE && chain && dir == DIR_GROW;   // this grow step runs without trace flags and location bookkeeping
+            // ---- end clip. A block that covers both sequence ends is the pair's last: the driver breaks right after it
+            // (below), and under X-drop all that survives the break is best_max and its location. With F_PAD_NEG -- every matrix entry of the
+            // padding byte is negative -- a column of padding holds no cell above best_max, so the rectangle stops behind the last column of its
+            // column sequence (column lenC; place_rect8's early break of the global modes stops at the same column). Clipped: the untraced
+            // rectangles of a speculative chain (a clipped block that still raises the best is rolled back and repeated traced and unclipped,
+            // as ever) and every rectangle of the score-only kernels -- there the location of a new best is that of the full rectangle
+            // (padding cells are strictly below the maximum: none enters the tie-break of place_rect / place_rect8), so nothing is repeated.
+            // The block record, the reserved trace space and `cells` keep the full width.
+            uint32_t rwc = rw;
+            if constexpr (XDROP && (KIND == KIND_NUC || KIND == KIND_AA) && !SPECIAL && !kBig) {
+                if ((!TRACE || spec) && !fast && (h_flags & F_PAD_NEG) && si + block_size > qlen && sj + block_size > rlen)
+                    rwc = lenC < rj ? 0u : (lenC + 1u - rj < rw ? lenC + 1u - rj : rw);   // (column lenC is the last residue: images are [NULL] + bytes + padding)
+            }
             if (TRACE && !fast) {   // add_block(i, j, width, height, right) in matrix orientation (scan_block.rs:154,204,257,284)
                 if (right) add_block(ri, rj, rw, rh, true, spec);
                 else add_block(rj, ri, rh, rw, false, spec);
@@ -1773,9 +1787,9 @@ struct Aligner {
             Best cur{0, 0, 0};
             FastOut fo{}; int run_exit = RUN_EXIT_POST;
             const uint32_t sp = special ? ((h_flags & F_LOCAL) ? SP_LOCAL : 0u) | (((h_flags & F_FQS) && right) ? SP_FQS_ROW0 : 0u) | (FQE ? SP_FQE : 0u) : 0u;
-#define BA_PLACE1(N, PD) cur = place_rect<N, KIND, TRACE, XDROP, PD>(L, fc, seqV, seqC, lenV, lenC, ri, rj, rw, rh, Dc, Cc, Dr, Rr, corner, rz, off_add, tout, cells, prof, sp, &fq, &pv)
+#define BA_PLACE1(N, PD) cur = place_rect<N, KIND, TRACE, XDROP, PD>(L, fc, seqV, seqC, lenV, lenC, ri, rj, rwc, rh, Dc, Cc, Dr, Rr, corner, rz, off_add, tout, cells, prof, sp, &fq, &pv)
 #define BA_PLACE_T(N) do { if constexpr (KIND == KIND_PROFILE) { if (right) BA_PLACE1(N, 1); else BA_PLACE1(N, 2); } else BA_PLACE1(N, 0); } while (0)
-#define BA_PLACE_S(N) cur = place_rect<N, KIND, false, XDROP, 0, false>(L, fc, seqV, seqC, lenV, lenC, ri, rj, rw, rh, Dc, Cc, Dr, Rr, corner, rz, off_add, nullptr, cells, prof, sp, &fq, &pv)
+#define BA_PLACE_S(N) cur = place_rect<N, KIND, false, XDROP, 0, false>(L, fc, seqV, seqC, lenV, lenC, ri, rj, rwc, rh, Dc, Cc, Dr, Rr, corner, rz, off_add, nullptr, cells, prof, sp, &fq, &pv)
 #define BA_PLACE(N) do { if constexpr (TRACE && KIND != KIND_PROFILE && !SPECIAL && !kBig) { if (spec) BA_PLACE_S(N); else BA_PLACE_T(N); } else BA_PLACE_T(N); } while (0)
             if (kBig && rh > BIG_TILE) {
                 // ---- row tiles of BIG_TILE cells (TileCtx): the tile above hands its last row over through big_top
@@ -1854,8 +1868,8 @@ struct Aligner {
             else if (PMAX >= 2 && rh == 256) BA_PLACE(2);
             // (512 rows and more: eight cells per lane, see place_rect8 -- sequence kinds without special modes)
 #define BA_PLACE8(N8) do { if constexpr (KIND != KIND_PROFILE && !SPECIAL && !kBig) { \
-                if (TRACE && spec) cur = place_rect8<N8, KIND, false, XDROP, false>(L, fc, seqV, seqC, lenV, lenC, ri, rj, rw, Dc, Cc, Dr, Rr, corner, rz, off_add, nullptr, cells); \
-                else cur = place_rect8<N8, KIND, TRACE, XDROP>(L, fc, seqV, seqC, lenV, lenC, ri, rj, rw, Dc, Cc, Dr, Rr, corner, rz, off_add, tout, cells); } } while (0)
+                if (TRACE && spec) cur = place_rect8<N8, KIND, false, XDROP, false>(L, fc, seqV, seqC, lenV, lenC, ri, rj, rwc, Dc, Cc, Dr, Rr, corner, rz, off_add, nullptr, cells); \
+                else cur = place_rect8<N8, KIND, TRACE, XDROP>(L, fc, seqV, seqC, lenV, lenC, ri, rj, rwc, Dc, Cc, Dr, Rr, corner, rz, off_add, tout, cells); } } while (0)
             else if (PMAX >= 4 && rh == 512) { if constexpr (KIND != KIND_PROFILE && !SPECIAL && !kBig) BA_PLACE8(1); else BA_PLACE(4); }
             else if (PMAX >= 8 && rh == 1024) { if constexpr (KIND != KIND_PROFILE && !SPECIAL && !kBig) BA_PLACE8(2); else BA_PLACE(8); }
             else if (PMAX >= 16 && rh == 2048) { if constexpr (KIND != KIND_PROFILE && !SPECIAL && !kBig) BA_PLACE8(4); else BA_PLACE(16); }
@@ -1864,6 +1878,18 @@ struct Aligner {
 #undef BA_PLACE_S
 #undef BA_PLACE_T
 #undef BA_PLACE1
+            if (rwc != rw) {   // (end clip) what the skipped columns still owe
+                const uint32_t skipped = (rw - rwc) * rh;
+                cells += skipped;                                              // the reference computes them: `cells` stays its count
+                park<14>(parked, unpark<14>(parked) + (int)skipped);         // the pair's share of the launch counter (prof[61], below)
+                if (dir == DIR_GROW && gphase == 0) {
+                    // The down part of a grow feeds the lower end of the right part's vector border, one entry per column. The skipped columns are
+                    // query rows past the end -- padding rows of the right part --, and what LDS holds there is of some other offset base and
+                    // could pass for a maximum: those entries are set to -32768, below everything (in-range rows never read them).
+                    for (uint32_t k = rwc + (uint32_t)lane_id(); k < rw; k += 64u) { Dr[k] = (short)-32768; Rr[k] = (short)-32768; }
+                    lds_sync();
+                }
+            }
             BA_TSTAMP(ts2);
             BA_TADD(prof, 12, ts0, ts1); BA_TADD(prof, 13, ts1, ts2);
             if (dir == DIR_GROW && gphase == 0) {   // first rectangle of a grow: its maximum waits (parked) for the second one
@@ -2012,6 +2038,11 @@ struct Aligner {
 #pragma unroll
             for (int d = 32; d >= 1; d >>= 1) sc += (uint32_t)__shfl_xor((int)sc, d, 64);
             if (is_lane(0) && sc && !(status & ST_CLASS_OVERFLOW)) atomicAdd(coldp()->prof + 60, (unsigned long long)sc);   // (a pair that lost the class bet is run again: nothing of this run is kept)
+        }
+        if constexpr (XDROP && (KIND == KIND_NUC || KIND == KIND_AA) && !SPECIAL && !kBig) {
+            // (end clip) the cells this pair's last block did not compute, into a counter of the launch next to the speculative cells
+            const uint32_t sk = (uint32_t)unpark<14>(parked);
+            if (sk && coldp()->prof && is_lane(0) && !(status & ST_CLASS_OVERFLOW)) atomicAdd(coldp()->prof + 61, (unsigned long long)sk);
         }
         const uint32_t pair = (uint32_t)unpark<7>(parked), slot = (uint32_t)unpark<8>(parked);
         int score; uint32_t ri, rj;

@@ -261,6 +261,7 @@ struct BaBatch {
     uint64_t runs_done = 0;  // finished runs: what the text sizes are kept for
     uint64_t compact_cap = 0, compact_used_cap = 0; bool compacted = false; uint32_t* compact_host = nullptr;
     unsigned long long* h_total = nullptr;   // page-locked mailbox the gather writes its total to (read without a copy)
+    bool pad_negative = false;  // every matrix entry of the padding byte's row and column is negative (pad_negative() at creation): the kernels may clip an X-drop alignment's last block (F_PAD_NEG)
     bool handle_mode = false;   // the device state of one Block handle: one pair per launch, CIGARs only on request (k_traceback)
     DevBuf hblk, rblk;          // handle mode: everything uploaded per align / everything read back, one buffer each
     BatchParams params() const {
@@ -269,7 +270,7 @@ struct BaBatch {
         bp.q_off = q_off.as<uint64_t>(); bp.q_len = q_len.as<uint32_t>();
         bp.r_off = r_off.as<uint64_t>(); bp.r_len = r_len.as<uint32_t>();
         bp.n = n; bp.gap_open = gap_open; bp.gap_extend = gap_extend;
-        bp.min_size = min_size; bp.max_size = max_size; bp.x_drop = x_drop; bp.flags = mode | (dev_env("BA_NO_FAST") ? 0x100u : 0u) | ((dev_env("BA_SKIP_WALK") || dev_env("BA_NO_TRACEBACK")) ? 0x200u : 0u) | ((handle_mode || dev_env("BA_NO_SPEC")) ? 0x400u : 0u) | (dev_env("BA_NO_TB_WAVES") ? 0x800u : 0u) | (dev_env("BA_NO_REFILL") ? 0x1000u : 0u) | (dev_env("BA_NO_STEAL") ? 0x2000u : 0u);   // (0x400: no speculative grows -- a handle's trace may be walked from any cell)
+        bp.min_size = min_size; bp.max_size = max_size; bp.x_drop = x_drop; bp.flags = mode | (dev_env("BA_NO_FAST") ? 0x100u : 0u) | ((dev_env("BA_SKIP_WALK") || dev_env("BA_NO_TRACEBACK")) ? 0x200u : 0u) | ((handle_mode || dev_env("BA_NO_SPEC")) ? 0x400u : 0u) | (dev_env("BA_NO_TB_WAVES") ? 0x800u : 0u) | (dev_env("BA_NO_REFILL") ? 0x1000u : 0u) | (dev_env("BA_NO_STEAL") ? 0x2000u : 0u) | ((pad_negative && !dev_env("BA_NO_END_CLIP")) ? (uint32_t)ba::F_PAD_NEG : 0u);   // (0x400: no speculative grows -- a handle's trace may be walked from any cell)
         bp.matrix = matrix.as<int8_t>();
         bp.score = score.as<int32_t>(); bp.query_idx = qidx.as<uint32_t>(); bp.reference_idx = ridx.as<uint32_t>();
         bp.cig_ops = ((mode & BA_TRACE) && !handle_mode && !dev_env("BA_NO_TRACEBACK")) ? cig_ops.as<uint32_t>() : nullptr;   // env: development switch
@@ -853,6 +854,26 @@ static int upload_images(BaBatch* b, const Packed& P, size_t n) {
     return 0;
 }
 
+// Is every score that involves the padding byte negative? Then no cell of a padding row or column can exceed the cells and borders it is
+// computed from, which is what lets the kernels skip the padding columns of an X-drop alignment's last block (ba_driver.hpp run(), DESIGN.md
+// section 4). The reference's index masks decide which entries that byte reads: a NucMatrix is indexed [c & 7][a & 15] (scores.rs:157,179), so
+// 'Z' shares its row with 'B', 'J' and 'R' and its column with 'J' -- the whole row and the whole column count; an AAMatrix is indexed
+// [c - 'A'][a - 'A'] with the padding at 26. Byte matrices (padding equals padding: a match) and profiles never qualify.
+static bool pad_negative(int kind, const void* matrix) {
+    const int8_t* m = (const int8_t*)matrix;
+    if (!m) return false;
+    if (kind == BA_KIND_NUC) {
+        const int row = 'Z' & 7, col = 'Z' & 15;
+        for (int a = 0; a < 16; a++) if (m[row * 16 + a] >= 0) return false;
+        for (int c = 0; c < 8; c++) if (m[c * 16 + col] >= 0) return false;
+        return true;
+    }
+    if (kind == BA_KIND_AA) {
+        for (int a = 0; a < 27; a++) if (m[26 * 32 + a] >= 0 || m[a * 32 + 26] >= 0) return false;
+        return true;
+    }
+    return false;
+}
 static int upload_dev_of(BaBatch* b);
 static void plan_walks(BaBatch* b, const std::vector<uint32_t>& ql, const std::vector<uint32_t>& rl);
 static void plan_exclusive(BaBatch* b, const std::vector<uint32_t>& ql, const std::vector<uint32_t>& rl);
@@ -1059,6 +1080,7 @@ static BaBatch* batch_build(int kind, const void* matrix, Gaps gaps, SizeRange s
         if (kind == BA_KIND_BYTES) { const ByteMatrix* bm = (const ByteMatrix*)matrix; tmp[0] = bm->match_score; tmp[1] = bm->mismatch_score; }
         else if (mat_bytes) memcpy(tmp, matrix, mat_bytes);
         BA_H2D(matrix, tmp, 1024);
+        b->pad_negative = pad_negative(kind, matrix);
     }
 #undef BA_H2D
     lap("host-to-device copies");
@@ -1333,6 +1355,7 @@ static int batch_retry(BaBatch* b, const std::vector<uint32_t>& idx, float* retr
     BaBatch sub;
     sub.device = b->device; sub.kind = b->kind; sub.mode = b->mode; sub.n = (uint32_t)k; sub.min_size = b->min_size; sub.max_size = b->max_size;
     sub.pclass = b->opt_class ? (uint32_t)BA_PCLASS_BIG : b->pclass; sub.gap_open = b->gap_open; sub.gap_extend = b->gap_extend; sub.x_drop = b->x_drop;
+    sub.pad_negative = b->pad_negative;
     std::vector<uint64_t> qo(k), ro(k), co(k + 1);
     std::vector<uint32_t> sql(k), srl(k);
     uint64_t maxlen2 = 0, cig_total = 0;
@@ -2225,6 +2248,16 @@ int ba_batch_spec_cells(BaBatch* b, uint64_t* cells) {
     if (!b->ran) return fail("ba_batch_run has not been called");
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipMemcpy(cells, (const char*)b->prof.p + 60 * 8, 8, hipMemcpyDeviceToHost));
+    return 0;
+}
+// Cells of the last run that were not computed: the padding columns of X-drop alignments' last blocks (ba_driver.hpp run(), the end clip).
+// They are part of the pairs' `cells` -- the reference computes them --; the speculative cells of ba_batch_spec_cells keep counting full
+// rectangles. 0 without X-drop, for byte-matrix and profile batches, in the special modes, and for a matrix that scores its padding byte at 0 or above.
+int ba_batch_skipped_cells(BaBatch* b, uint64_t* cells) {
+    if (!b || !cells) return fail("null argument");
+    if (!b->ran) return fail("ba_batch_run has not been called");
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipMemcpy(cells, (const char*)b->prof.p + 61 * 8, 8, hipMemcpyDeviceToHost));
     return 0;
 }
 int ba_batch_kernel(BaBatch* b) {   // 0 the per-pair kernel (row-tiled class included), 1 k_multi, 2 k_quad beside it, 3 k_small

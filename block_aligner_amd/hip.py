@@ -168,6 +168,7 @@ def lib() -> C.CDLL:
         L.ba_batch_kernel.argtypes = [vp]
         L.ba_batch_geometry.argtypes = [vp]
         L.ba_batch_spec_cells.argtypes = [vp, vp]
+        L.ba_batch_skipped_cells.argtypes = [vp, vp]
         L.ba_build_id.restype = C.c_char_p
         L.ba_multibatch_create.restype = vp
         L.ba_multibatch_create.argtypes = [C.c_int, vp, GapsC, SizeRangeC, i32, u32, vp, vp, vp, vp, vp, sz, vp, C.c_int]
@@ -696,6 +697,12 @@ class BatchAligner(_Batch):
         """Cells of the last run's speculative, untraced rectangles (X-drop + TRACE): a part of results()["cells"]."""
         o = C.c_uint64()
         self._call("spec_cells", C.byref(o))
+        return int(o.value)
+
+    def skipped_cells(self) -> int:
+        """Cells of the last run that were not computed: padding columns of the blocks that close X-drop alignments. Counted in results()["cells"]."""
+        o = C.c_uint64()
+        self._call("skipped_cells", C.byref(o))
         return int(o.value)
 
     def info(self):

@@ -264,6 +264,10 @@ int ba_batch_geometry(BaBatch* batch);
  * can lie on no path: filled without trace flags and location bookkeeping) -- a part of the computed cells that needed 14 instead of 20
  * int16 operations per cell (bench.py: roofline.ops_required). */
 int ba_batch_spec_cells(BaBatch* batch, uint64_t* cells);
+/* X-drop batches over a NucMatrix or an AAMatrix whose padding byte scores below 0 against every byte (new_simple and the stock matrices do):
+ * cells of the last run that were NOT computed -- the columns past the sequence ends in the block that closes an alignment, which can hold
+ * no new best. They are counted in the pairs' `cells` all the same (the reference computes them). 0 for every other batch. */
+int ba_batch_skipped_cells(BaBatch* batch, uint64_t* cells);
 /* Large TRACE batches size their trace slots for the expected stack, not for the reference's worst case (Trace::new,
  * scan_block.rs:1363-1366); pairs that outgrow a slot are re-run with full-size slots inside ba_batch_run / ba_batch_wait. (Large: from 4096 pairs, or
  * from 256 pairs of 10 kbp and more.) Likewise a batch whose block range starts at 128 .. 1024 cells and ends above 2048 is launched in the 2048-cell class;
