@@ -67,4 +67,20 @@ struct ExactParams {
     uint32_t eq;
 };
 
+// ------------------------------------------------------------------ the batch's own mode (BA_EXACT_OWN_MODE; ba_exact_modes.hip)
+constexpr uint32_t EXACT_OWN_MODE = 1u << 8;   // flag bit of `what`, beside EXACT_GLOBAL / EXACT_EXTEND
+// the start rule of a sequence batch: as k_exact's; H[0][j] = 0 (BA_FREE_QUERY_START_GAPS); H[0][j] = H[i][0] = 0 and H floored at 0 (BA_LOCAL_START)
+constexpr uint32_t EXACT_START_GLOBAL = 0, EXACT_START_FREE_ROW0 = 1, EXACT_START_LOCAL = 2;
+// A profile column adds three int8 terms to a path at most (a score or gap_extend, gap_open_C / gap_open_R, gap_close_C): a path's score
+// lies within (|q| + |r|) * 384 of zero.
+constexpr uint64_t EXACT_MAX_LEN2_PROFILE = ((uint64_t)1 << 30) / 384 - 1;
+// k_exact_mode / k_exact_profile: ExactParams (the traced fields unused; kind may be KIND_PROFILE, r_off then names AAProfile images and
+// the row buffer holds {T, vertical-gap state}) and what the mode adds.
+struct ExactModeParams {
+    ExactParams x;
+    uint32_t start;              // EXACT_START_* (sequence kinds)
+    uint32_t end_free;           // BA_FREE_QUERY_END_GAPS: EXACT_GLOBAL reads the maximum of the last row
+    uint32_t max_size;           // profiles: the batch's largest block, which sizes the images (profile_positions)
+};
+
 }  // namespace ba

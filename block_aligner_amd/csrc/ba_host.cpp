@@ -1722,6 +1722,14 @@ static int exact_check_lengths(const uint32_t* ql, const uint32_t* rl, size_t n,
                         ql[p], rl[p], (unsigned long long)ba::EXACT_MAX_LEN2);
     return 0;
 }
+// profile batches (BA_EXACT_OWN_MODE): three int8 terms per column
+static int exact_check_lengths_profile(const uint32_t* ql, const uint32_t* rl, size_t n, const uint32_t* name) {
+    for (size_t p = 0; p < n; p++)
+        if ((uint64_t)ql[p] + rl[p] > ba::EXACT_MAX_LEN2_PROFILE)
+            return fail("exact: pair %zu (|q| = %u, profile length = %u) is too long for int32 scores: |q| + |r| may be %llu at most for a profile batch",
+                        name ? (size_t)name[p] : p, ql[p], rl[p], (unsigned long long)ba::EXACT_MAX_LEN2_PROFILE);
+    return 0;
+}
 static_assert(ba::EXACT_TRACE_MAX_CELLS == BA_EXACT_TRACE_MAX_CELLS, "BA_EXACT_TRACE_MAX_CELLS and ba::EXACT_TRACE_MAX_CELLS differ");
 static int exact_trace_check_lengths(const uint32_t* ql, const uint32_t* rl, size_t n, const uint32_t* name) {
     if (exact_check_lengths(ql, rl, n, name)) return 1;
@@ -1731,11 +1739,25 @@ static int exact_trace_check_lengths(const uint32_t* ql, const uint32_t* rl, siz
                         name ? (size_t)name[p] : p, ql[p], rl[p], (unsigned long long)ba::EXACT_TRACE_MAX_CELLS);
     return 0;
 }
-static int exact_refusals(const BaBatch* b, uint32_t what, const void* out) {
+static_assert(ba::EXACT_OWN_MODE == BA_EXACT_OWN_MODE, "BA_EXACT_OWN_MODE and ba::EXACT_OWN_MODE differ");
+// the batch's own mode asks for another sweep than k_exact's: the flag is set and the batch is not a plain sequence batch
+static bool exact_own_sweep(const BaBatch* b, uint32_t what) {
+    return (what & BA_EXACT_OWN_MODE) && (b->kind == BA_KIND_PROFILE_ || special_of(b->mode));
+}
+// paths: the call returns optimal paths too (ba_*_exact_cigars)
+static int exact_refusals(const BaBatch* b, uint32_t what, const void* out, bool paths = false) {
     if (!out) return fail("null argument: out");
-    if (what != BA_EXACT_GLOBAL && what != BA_EXACT_EXTEND) return fail("exact: unknown quantity %u (BA_EXACT_GLOBAL or BA_EXACT_EXTEND)", what);
-    if (b->kind == BA_KIND_PROFILE_) return fail("exact: profile batches are not supported (position-specific gap costs)");
-    if (special_of(b->mode)) return fail("exact: batches with BA_LOCAL_START or BA_FREE_QUERY_* are not supported");
+    const uint32_t quantity = what & ~(uint32_t)BA_EXACT_OWN_MODE;
+    if (quantity != BA_EXACT_GLOBAL && quantity != BA_EXACT_EXTEND) return fail("exact: unknown quantity %u (BA_EXACT_GLOBAL or BA_EXACT_EXTEND)", what);
+    if (!(what & BA_EXACT_OWN_MODE)) {
+        if (b->kind == BA_KIND_PROFILE_) return fail("exact: profile batches are not supported (position-specific gap costs)");
+        if (special_of(b->mode)) return fail("exact: batches with BA_LOCAL_START or BA_FREE_QUERY_* are not supported");
+    } else {
+        if (b->kind == BA_KIND_PROFILE_ && special_of(b->mode))
+            return fail("exact: BA_EXACT_OWN_MODE does not cover a profile batch with BA_LOCAL_START or BA_FREE_QUERY_* (that combination has no definition yet)");
+        if (paths && exact_own_sweep(b, what))
+            return fail("exact: BA_EXACT_OWN_MODE gives scores only: no paths for a profile batch or a batch with BA_LOCAL_START or BA_FREE_QUERY_* (ba_*_exact)");
+    }
     if (b->handle_mode) return fail("exact: not a batch");
     if (b->in_flight) return fail("exact: the batch has a launch in flight (ba_batch_wait first)");
     if (!b->n) return fail("exact: the batch holds no pairs (a reload failed)");
@@ -1743,7 +1765,9 @@ static int exact_refusals(const BaBatch* b, uint32_t what, const void* out) {
 }
 // traced: the paths too (ba_batch_exact_cigars) -- the record's runs are left on the device in b->xt_runs at the offsets of b->xt_off
 static int batch_exact_device(BaBatch* b, uint32_t what, int32_t x_drop, const uint32_t* devpos, size_t m, BaExact* out, bool traced = false) {
-    if (exact_refusals(b, what, out)) return 1;
+    if (exact_refusals(b, what, out, traced)) return 1;
+    const bool own = exact_own_sweep(b, what), profile = b->kind == BA_KIND_PROFILE_;   // (on a plain sequence batch the flag changes nothing)
+    what &= ~(uint32_t)BA_EXACT_OWN_MODE;
     float& ms_out = traced ? b->xt_ms : b->exact_ms;
     uint64_t& cells_out = traced ? b->xt_cells : b->exact_cells;
     ms_out = 0; cells_out = 0;
@@ -1753,12 +1777,13 @@ static int batch_exact_device(BaBatch* b, uint32_t what, int32_t x_drop, const u
     std::vector<uint32_t> ql(b->n), rl(b->n);
     HIP_TRY(hipMemcpy(ql.data(), b->q_len.p, (size_t)b->n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(rl.data(), b->r_len.p, (size_t)b->n * 4, hipMemcpyDeviceToHost));
-    if (exact_check_lengths(ql.data(), rl.data(), b->n, b->h_order.empty() ? nullptr : b->h_order.data())) return 1;
+    if ((profile ? exact_check_lengths_profile : exact_check_lengths)(ql.data(), rl.data(), b->n, b->h_order.empty() ? nullptr : b->h_order.data())) return 1;
     if (traced)   // (the requested pairs only: the others need no region)
         for (size_t k = 0; k < m; k++) {
             const uint32_t d = devpos[k];
             if (d != ba::EXACT_NO_PAIR && exact_trace_check_lengths(&ql[d], &rl[d], 1, b->h_order.empty() ? &d : &b->h_order[d])) return 1;
         }
+    // (the profile sweep shares this cost model: it also walks row 0, one row in |q| + 1, which neither the order nor the cuts notice)
     auto cost = [&](uint32_t k) { const uint32_t d = devpos[k]; return d == ba::EXACT_NO_PAIR ? 0ull : (uint64_t)ql[d] * rl[d]; };
     std::vector<uint32_t> rec(m);
     for (size_t k = 0; k < m; k++) rec[k] = (uint32_t)k;
@@ -1842,7 +1867,7 @@ static int batch_exact_device(BaBatch* b, uint32_t what, int32_t x_drop, const u
     if (!b->ev_x0) HIP_TRY(hipEventCreate(&b->ev_x0));
     if (!b->ev_x1) HIP_TRY(hipEventCreate(&b->ev_x1));
     ba::ExactParams xp{};
-    xp.what = what; xp.x_drop = x_drop; xp.kind = seq_kind(b->kind); xp.gap_open = b->gap_open; xp.gap_extend = b->gap_extend;
+    xp.what = what; xp.x_drop = x_drop; xp.kind = own ? b->kind : seq_kind(b->kind); xp.gap_open = b->gap_open; xp.gap_extend = b->gap_extend;
     xp.matrix = b->matrix.as<int8_t>(); xp.matrix_bytes = (uint32_t)std::min<size_t>(b->matrix.bytes, 1024);
     xp.pool = b->pool.as<uint8_t>(); xp.q_off = b->q_off.as<uint64_t>(); xp.q_len = b->q_len.as<uint32_t>();
     xp.r_off = b->r_off.as<uint64_t>(); xp.r_len = b->r_len.as<uint32_t>();
@@ -1862,6 +1887,13 @@ static int batch_exact_device(BaBatch* b, uint32_t what, int32_t x_drop, const u
             uint32_t waves = std::min<uint32_t>(tr_waves, xp.n);
             if (waves >= ba::EXACT_WAVES) waves -= waves % ba::EXACT_WAVES;
             HIP_TRY(ba_launch_exact_trace(b->stream, &xp, waves));
+        } else if (own) {   // k_exact_mode / k_exact_profile: the same records, row buffers (two words per column) and launch geometry
+            ba::ExactModeParams mp{};
+            mp.x = xp;
+            mp.start = (b->mode & BA_LOCAL_START) ? ba::EXACT_START_LOCAL : (b->mode & BA_FREE_QUERY_START_GAPS) ? ba::EXACT_START_FREE_ROW0 : ba::EXACT_START_GLOBAL;
+            mp.end_free = (b->mode & BA_FREE_QUERY_END_GAPS) ? 1u : 0u;
+            mp.max_size = (uint32_t)b->max_size;
+            HIP_TRY(ba_launch_exact_modes(b->stream, &mp, std::min<uint32_t>(wgs, (xp.n + ba::EXACT_WAVES - 1) / ba::EXACT_WAVES)));
         } else
             HIP_TRY(ba_launch_exact(b->stream, &xp, std::min<uint32_t>(wgs, (xp.n + ba::EXACT_WAVES - 1) / ba::EXACT_WAVES)));
     }
@@ -1909,7 +1941,7 @@ static int batch_exact_cigars(BaBatch* b, uint32_t what, int32_t x_drop, const u
                               uint64_t capacity) {
     if (!b) return fail("null batch");
     if (!run_off) return fail("null argument: run_off");
-    if (exact_refusals(b, what, out)) return 1;
+    if (exact_refusals(b, what, out, true)) return 1;
     std::vector<uint32_t> devpos;
     if (exact_devpos(b, which, n_which, devpos)) return 1;
     const size_t m = devpos.size();
@@ -2297,6 +2329,10 @@ int ba_batch_exact_cigars_ms(BaBatch* b, float* ms, uint64_t* cells) {
 int ba_exact_trace_check_lengths(const uint32_t* q_len, const uint32_t* r_len, uintptr_t n) {
     if (n && (!q_len || !r_len)) return fail("null argument");
     return exact_trace_check_lengths(q_len, r_len, n, nullptr);
+}
+int ba_exact_check_lengths_profile(const uint32_t* q_len, const uint32_t* r_len, uintptr_t n) {
+    if (n && (!q_len || !r_len)) return fail("null argument");
+    return exact_check_lengths_profile(q_len, r_len, n, nullptr);
 }
 int ba_exact_check_lengths(const uint32_t* q_len, const uint32_t* r_len, uintptr_t n) {
     if (n && (!q_len || !r_len)) return fail("null argument");

@@ -74,6 +74,8 @@ hipError_t ba_launch_exact_trace(hipStream_t s, const ba::ExactParams* xp, uint3
 hipError_t ba_launch_exact_runs(hipStream_t s, const uint32_t* rev, const uint64_t* rev_off, const uint32_t* nrun, const uint64_t* off, uint32_t* runs,
                                 uint32_t m);
 hipError_t ba_launch_exact_seed(hipStream_t s, const ba::ExtendParams* ep, const uint32_t* which, uint32_t m, int32_t* out);
+// ba_exact_modes.hip
+hipError_t ba_launch_exact_modes(hipStream_t s, const ba::ExactModeParams* mp, uint32_t wgs);
 // ba_text.hip
 hipError_t ba_launch_text_len(hipStream_t s, const ba::TextParams* tp);
 hipError_t ba_launch_text_write(hipStream_t s, const ba::TextParams* tp);

@@ -72,6 +72,7 @@ EXACT_DTYPE = np.dtype(ExactC)
 if C.sizeof(ExactC) != 16 or EXACT_DTYPE.itemsize != 16:
     raise ImportError(f"struct BaExact must be 16 bytes, the binding declares {C.sizeof(ExactC)}")
 EXACT_GLOBAL, EXACT_EXTEND = 0, 1   # ba_*_exact: the quantity
+EXACT_OWN_MODE = 1 << 8             # ... and the flag bit: under the batch's own start / end rules, or its profile's gap costs
 EXACT_TRACE_MAX_CELLS = 1 << 31     # ba_*_exact_cigars: |q| * |r| of a pair
 
 
@@ -199,6 +200,7 @@ def lib() -> C.CDLL:
         L.ba_exact_trace_check_lengths.argtypes = [vp, vp, sz]
         L.ba_batch_exact_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
         L.ba_exact_check_lengths.argtypes = [vp, vp, sz]
+        L.ba_exact_check_lengths_profile.argtypes = [vp, vp, sz]
         L.ba_accuracy_summary.argtypes = [vp, vp, vp, vp, vp, sz, C.POINTER(AccuracyC)]
         L.ba_batch_stats_ms.argtypes = [vp, C.POINTER(C.c_float)]
         L.ba_batch_text_ms.argtypes = [vp, C.POINTER(C.c_float)]
@@ -306,6 +308,16 @@ def exact_trace_check_lengths(q_len, r_len) -> None:
     if len(q_len) != len(r_len):
         raise ValueError("q_len and r_len must have one entry per pair")
     if lib().ba_exact_trace_check_lengths(q_len.ctypes.data, r_len.ctypes.data, len(q_len)):
+        raise RuntimeError(last_error())
+
+
+def exact_check_lengths_profile(q_len, r_len) -> None:
+    """The length guard of exact(own_mode=True) on a profile batch on its own (needs no device; r_len: profile lengths): raises, naming the
+    pair, if (|q| + |r|) * 384 -- three int8 terms per column -- does not stay above the sentinel -2^30."""
+    q_len, r_len = np.ascontiguousarray(q_len, dtype=np.uint32), np.ascontiguousarray(r_len, dtype=np.uint32)
+    if len(q_len) != len(r_len):
+        raise ValueError("q_len and r_len must have one entry per pair")
+    if lib().ba_exact_check_lengths_profile(q_len.ctypes.data, r_len.ctypes.data, len(q_len)):
         raise RuntimeError(last_error())
 
 
@@ -556,13 +568,17 @@ class _Batch:
         out["edit_distance"] = out["mismatches"] + out["ins"] + out["del"]
         return out
 
-    def exact(self, what=None, x_drop=-1, which=None):
+    def exact(self, what=None, x_drop=-1, which=None, own_mode=False):
         """Exact full-matrix scores of the batch's pairs, computed on the device (ba_*_exact; no run needed) -> dict of arrays score,
         query_idx, reference_idx, rows. what: EXACT_GLOBAL (H[|q|][|r|]) or EXACT_EXTEND (the maximum over the matrix; with x_drop >= 0
         under the row-wise X-drop rule); None = EXACT_EXTEND for an X-drop batch, EXACT_GLOBAL otherwise. which: pair indices in any order,
-        repeats allowed (record k belongs to which[k]); None = every pair."""
+        repeats allowed (record k belongs to which[k]); None = every pair. own_mode (EXACT_OWN_MODE in what): the matrix of the batch's own
+        mode -- LOCAL_START / FREE_QUERY_* start and end rules, a profile's position-specific gap costs --, which is refused without it;
+        on a plain sequence batch it changes nothing."""
         if what is None:
             what = EXACT_EXTEND if self.mode & X_DROP else EXACT_GLOBAL
+        if own_mode:
+            what = int(what) | EXACT_OWN_MODE
         w, wp, wn = _which(which)
         rec = np.zeros(self.n if w is None else wn, EXACT_DTYPE)
         self._call("exact", int(what), int(x_drop), wp, wn, rec.ctypes.data)
@@ -582,9 +598,9 @@ class _Batch:
         self._call("exact_cigars", int(what), int(x_drop), wp, wn, rec.ctypes.data, off.ctypes.data, runs.ctypes.data, runs.size)
         return {k: rec[k].copy() for k in EXACT_DTYPE.names}, runs, off
 
-    def accuracy(self, x_drop=-1, which=None):
-        """After a run: the batch's results against exact() of the same pairs (accuracy_summary) -> dict."""
-        ex = self.exact(None, x_drop, which)
+    def accuracy(self, x_drop=-1, which=None, own_mode=False):
+        """After a run: the batch's results against exact() of the same pairs (accuracy_summary) -> dict. own_mode as in exact()."""
+        ex = self.exact(None, x_drop, which, own_mode)
         res = self.results()
         sel = slice(None) if which is None else np.asarray(which, dtype=np.int64)
         return accuracy_summary(res["score"][sel], ex, res["query_idx"][sel], res["reference_idx"][sel], res["status"][sel])
@@ -840,9 +856,13 @@ class ExtendBatchAligner(_Batch):
     def exact_cigars(self):
         raise AttributeError("extension batches have no exact_cigars (exact paths are out of scope for them: INTEGRATION.md)")
 
-    def exact(self, x_drop=-1, which=None):
+    def exact(self, x_drop=-1, which=None, own_mode=False):
         """EXACT_EXTEND on both sides of every seed (ba_extend_batch_exact; no run needed) -> dict: left and right (dicts of arrays score,
-        query_idx, reference_idx, rows; an empty side is all zeros) and score = left + the seed's ungapped score + right."""
+        query_idx, reference_idx, rows; an empty side is all zeros) and score = left + the seed's ungapped score + right. own_mode is
+        refused: ba_extend_batch_exact has no `what`, and an extension batch is created without the modes the flag is for."""
+        if own_mode:
+            raise RuntimeError("exact: EXACT_OWN_MODE does not apply to extension batches (they are created without LOCAL_START / "
+                               "FREE_QUERY_* and without profiles; ba_extend_batch_exact takes no `what`)")
         w, wp, wn = _which(which)
         m = self.n if w is None else wn
         left, right, score = np.zeros(m, EXACT_DTYPE), np.zeros(m, EXACT_DTYPE), np.zeros(m, np.int32)

@@ -439,6 +439,58 @@ int ba_extend_batch_exact(BaExtendBatch* batch, int32_t x_drop, const uint32_t* 
                           struct BaExact* right, int32_t* score);
 /* The length guard of the exact calls on its own (host only, no device): nonzero, naming the pair, if a pair is too long for int32 scores. */
 int ba_exact_check_lengths(const uint32_t* q_len, const uint32_t* r_len, uintptr_t n_pairs);
+/* ---- exact scores in the batch's own mode ("Exact scores and accuracy").
+ *
+ * BA_EXACT_OWN_MODE is a flag bit, OR-ed into BA_EXACT_GLOBAL or BA_EXACT_EXTEND in the `what` of ba_batch_exact, ba_sized_batch_exact and
+ * ba_multibatch_exact. Without it every call is as described above, refusals included. With it on a plain sequence batch (none of
+ * BA_LOCAL_START / BA_FREE_QUERY_*) the records are those without it. With it on a batch with one of those mode bits, or on a profile
+ * batch (ba_batch_create_profile), the full matrix is computed under the batch's own start and end rules. Rows are query positions
+ * i = 0 .. |q|, columns reference or profile positions j = 0 .. |r|, scores are int32; `rows` and the tie rules are as above.
+ *
+ * Sequence matrices. H, V (vertical gap) and Z (horizontal gap) are those above. The mode bits choose the start rule:
+ *   none                      as above;
+ *   BA_FREE_QUERY_START_GAPS  H[0][j] = 0 for every j; column 0 is as in the global case;
+ *   BA_LOCAL_START            H[0][j] = H[i][0] = 0, and H[i][j] = max(0, H[i-1][j-1] + s(q_i, r_j), V[i][j], Z[i][j]).
+ * (A batch cannot have both start bits; either goes with BA_FREE_QUERY_END_GAPS.) The quantity chooses the end rule:
+ *   BA_EXACT_GLOBAL   H[|q|][|r|] -- in a BA_FREE_QUERY_END_GAPS batch instead the maximum over j = 0 .. |r| of H[|q|][j], ties to the
+ *                     smallest j, reported at (|q|, j), with no floor at 0;
+ *   BA_EXACT_EXTEND   as above: the maximum over every cell, row 0 included, under the row-wise X-drop rule when x_drop >= 0.
+ *
+ * Profile batches. Let e = gap_extend, oC[j], cC[j], oR[j] the profile's gap_open_C, gap_close_C and gap_open_R at position j = 0 .. |r|,
+ * and s(j, a) the score of residue a at position j >= 1. Z is "no cell" in column 0, V in row 0, T[0][0] = 0 and T is "no cell" in the
+ * rest of column 0:
+ *   H[0][0] = 0
+ *   Z[i][j] = max(H[i][j-1] + oC[j] + e, Z[i][j-1] + e)                         j >= 1, every i >= 0
+ *   T[i][j] = max(H[i-1][j-1] + s(j, q_i) (i, j >= 1), Z[i][j] + cC[j] (j >= 1))
+ *   V[i][j] = max(T[i-1][j] + oR[j] + e, V[i-1][j] + e)                         i >= 1, every j >= 0
+ *   H[i][j] = max(T[i][j], V[i][j])
+ * So a run of n profile positions j .. j+n-1 against no residue costs oC[j] + n e + cC[j+n-1], and a run of n residues after position j
+ * costs oR[j] + n e. The vertical gap opens from T, as in the reference's prefix scan over the partially computed column; for oR <= 0
+ * that coincides with opening from H. BA_EXACT_GLOBAL and BA_EXACT_EXTEND are read off this H as above (row 0 is a row like the others:
+ * its maximum need not be cell (0, 0)). Positions the caller never set hold the reference's default of -128 and are taken as they are.
+ *
+ * What ties these to the batch results:
+ *   - a batch without BA_X_DROP never scores above OWN_MODE BA_EXACT_GLOBAL of its own mode, and equals it when one block covers the
+ *     matrix (min = max block size > max(|q|, |r|));
+ *   - for a profile batch the bound needs gap costs that do not depend on the position (gap_open_C = gap_open_R, gap_close_C = 0, as
+ *     the reference's pssm_accuracy example sets them). The definition is the recurrence of the rectangles whose vectors run along the
+ *     query, the only kind when one block covers the matrix, where equality holds for any costs; the rectangles a smaller block range
+ *     also places along the profile take the runs of profile positions through the prefix scan instead, which is another recurrence
+ *     once the costs depend on the position, and a run of the reference can then score a few points above the definition's optimum
+ *     (`above` of the summary);
+ *   - a BA_X_DROP batch never scores above OWN_MODE BA_EXACT_EXTEND with x_drop < 0;
+ *   - BA_FREE_QUERY_END_GAPS is the exception: the score a run reports follows the reference's lane rule -- the best of every block row
+ *     whose index is |q| modulo 16, padded rows included, never below 0 -- and may exceed the exact value; path_score of ba_*_stats never
+ *     does. For |q| < 16 with one block over the matrix the reported score equals max(exact, 0).
+ *
+ * Refused, beside the refusals above that do not concern the mode: BA_EXACT_OWN_MODE on a profile batch that also has BA_LOCAL_START or
+ * BA_FREE_QUERY_* (that combination has no definition yet); BA_EXACT_OWN_MODE passed to ba_*_exact_cigars on a profile batch or a batch
+ * with one of the mode bits (scores only: the four trace bits per cell have no room for "the path starts here"); a pair of a profile
+ * batch whose (|q| + |r|) * 384 -- three int8 terms per column -- does not stay above the sentinel -2^30 (the message names the pair).
+ * ba_extend_batch_exact has no `what`: extension batches are created without these modes and without profiles. */
+enum { BA_EXACT_OWN_MODE = 1u << 8 };   /* OR-ed into BA_EXACT_GLOBAL / BA_EXACT_EXTEND */
+/* The length guard of BA_EXACT_OWN_MODE on profile batches on its own (host only, no device): r_len are profile lengths. */
+int ba_exact_check_lengths_profile(const uint32_t* q_len, const uint32_t* r_len, uintptr_t n_pairs);
 /* ---- optimal alignment paths of the exact full-matrix DP ("Exact scores and accuracy").
  *
  * The calls above say how far a block range is from the optimum; these return the optimum's alignment, as packed CIGAR runs of the traced
