@@ -83,4 +83,32 @@ struct ExactModeParams {
     uint32_t max_size;           // profiles: the batch's largest block, which sizes the images (profile_positions)
 };
 
+// ------------------------------------------------------------------ optimal paths in the batch's own mode (ba_*_exact_paths; ba_exact_modes.hip,
+// compiled with BA_EXACT_TRACED). The traced fields of ExactParams are used as k_exact uses them; the nibble layout is exact_trace_words'. The
+// kernels take one more argument, start_cell: record k's walk stopped at cell (start_cell[2k], start_cell[2k + 1]).
+// Sequence kinds keep EXACT_TR_*, with one change that costs no memory: the walk never reads HV under DIAG, so the sweep clears HV
+// there, and DIAG | HV together mark "H == 0" in a BA_LOCAL_START matrix: the path starts here.
+constexpr uint32_t EXACT_TR_STOP = EXACT_TR_DIAG | EXACT_TR_HV;
+// Profiles: H == T, T == H[i-1][j-1] + s (never set in row 0), and VEXT / ZEXT as above. Row 0 is a swept row: a pair has
+// ceil((|q| + 1) / 64) bands and is traced while (|q| + 1) * |r| <= EXACT_TRACE_MAX_CELLS.
+constexpr uint32_t EXACT_TR_HT = 1, EXACT_TR_TDIAG = 2;
+// One record of ba_*_exact_paths: the layout of struct BaExactPath, 6 words.
+struct ExactPath {
+    int32_t score;
+    uint32_t q_start, r_start, q_end, r_end, rows;
+};
+static_assert(sizeof(ExactPath) == 24, "ExactPath layout");
+// k_exact_join: the runs of the requested seeds of an extension batch from the traced EXTEND records of their sides (record 2k the left
+// side of seed sel[k], over the reversed prefixes, record 2k + 1 the right one): the left runs turned round, the seed's ungapped columns,
+// the right runs, merged. runs == nullptr: only the counts, to nrun.
+struct ExactJoinParams {
+    uint32_t m;                  // requested seeds
+    uint32_t eq;                 // the seed's columns are '=' / 'X' by the image bytes
+    const uint32_t* sel;         // their seed indices
+    const uint32_t* seed_len; const uint8_t* seed_pool; const uint64_t* seed_q; const uint64_t* seed_r;
+    const uint32_t* side_runs; const uint64_t* side_off;   // the sides' runs in alignment order and their 2m + 1 offsets
+    uint32_t* nrun;              // m counts (first pass)
+    const uint64_t* off; uint32_t* runs;   // second pass: seed k's runs go to runs + off[k]
+};
+
 }  // namespace ba

@@ -14,6 +14,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include <atomic>
 #include <chrono>
@@ -256,6 +257,11 @@ struct BaBatch {
     float xt_ms = 0; uint64_t xt_cells = 0;
     bool xt_valid = false; uint32_t xt_what = 0; int32_t xt_x_drop = 0; uint64_t xt_loads = 0;
     std::vector<uint32_t> xt_devpos; std::vector<BaExact> xt_out; std::vector<uint64_t> xt_h_off;
+    // ... shared with the paths of the batch's own mode (ba_batch_exact_paths), which add every record's start cell; xt_form says whose
+    // request the buffers hold (EXACT_FORM_*)
+    int xt_form = 0;
+    float xp_ms = 0; uint64_t xp_cells = 0;   // time and cells of the last ba_batch_exact_paths call that computed
+    DevBuf xt_start; std::vector<uint32_t> xt_h_start;
     uint64_t loads = 0;      // reloads so far
     TextState text;          // alignment strings (ba_batch_text)
     uint64_t runs_done = 0;  // finished runs: what the text sizes are kept for
@@ -1575,6 +1581,11 @@ struct BaExtendBatch {
     uint64_t runs_done = 0;
     float fill_ms = 0, pack_ms = 0, splice_ms = 0;
     bool ran = false;
+    // optimal paths (ba_extend_batch_exact_paths): the requested seeds, their run counts, offsets and joined runs on the device, and the
+    // request they belong to with its records, kept for the second call of the two-call pattern (a load drops it)
+    DevBuf xp_sel, xp_nrun, xp_off, xp_runs, xp_seed, xp_no_off;   // (xp_seed: the seeds' ungapped scores; xp_no_off: zero offsets for a set without sides)
+    bool xp_valid = false; int32_t xp_x_drop = 0;
+    std::vector<uint32_t> xp_which; std::vector<BaExactPath> xp_out; std::vector<BaExact> xp_left, xp_right; std::vector<uint64_t> xp_h_off;
     ba::ExtendParams params() const {
         ba::ExtendParams ep{};
         ep.n = n; ep.kind = seq_kind(kind); ep.flags = mode; ep.matrix = matrix.as<int8_t>();
@@ -1621,7 +1632,7 @@ static int ext_load(BaExtendBatch* e, const ExtSet& S, size_t n, const void* mat
         if (S.seed_bytes > e->cap_seed) return fail("reload: the seeds (%llu image bytes) exceed the batch's capacity of %llu", (unsigned long long)S.seed_bytes, (unsigned long long)e->cap_seed);
         if (n_sides && !e->inner) return fail("reload: the set has sides to align, and the batch was created with none");
     }
-    e->n = 0; e->ran = false; e->pack_ms = 0;   // (a failure from here on leaves no seeds loaded)
+    e->n = 0; e->ran = false; e->pack_ms = 0; e->xp_valid = false;   // (a failure from here on leaves no seeds loaded)
     HIP_TRY(hipMemcpy(e->raw.p, S.lo, S.bytes, hipMemcpyHostToDevice));
     ExtImages X;
     X.host_base = S.lo; X.dev_base = e->raw.as<uint8_t>(); X.flags = S.flags.data(); X.seed_of = S.seed_of.data(); X.pack_ms = &e->pack_ms;
@@ -1739,6 +1750,16 @@ static int exact_trace_check_lengths(const uint32_t* ql, const uint32_t* rl, siz
                         name ? (size_t)name[p] : p, ql[p], rl[p], (unsigned long long)ba::EXACT_TRACE_MAX_CELLS);
     return 0;
 }
+// profile batches (ba_*_exact_paths): the profile sweep owns row 0, so a pair has |q| + 1 traced rows
+static int exact_trace_check_lengths_profile(const uint32_t* ql, const uint32_t* rl, size_t n, const uint32_t* name) {
+    if (exact_check_lengths_profile(ql, rl, n, name)) return 1;
+    for (size_t p = 0; p < n; p++)
+        if (((uint64_t)ql[p] + 1) * rl[p] > ba::EXACT_TRACE_MAX_CELLS)
+            return fail("exact: pair %zu (|q| = %u, profile length = %u) is too large for a traced matrix: (|q| + 1) * |r| may be %llu at most (BA_EXACT_TRACE_MAX_CELLS)",
+                        name ? (size_t)name[p] : p, ql[p], rl[p], (unsigned long long)ba::EXACT_TRACE_MAX_CELLS);
+    return 0;
+}
+static_assert(sizeof(BaExactPath) == sizeof(ba::ExactPath) && offsetof(BaExactPath, r_end) == offsetof(ba::ExactPath, r_end), "BaExactPath and ba::ExactPath differ");
 static_assert(ba::EXACT_OWN_MODE == BA_EXACT_OWN_MODE, "BA_EXACT_OWN_MODE and ba::EXACT_OWN_MODE differ");
 // the batch's own mode asks for another sweep than k_exact's: the flag is set and the batch is not a plain sequence batch
 static bool exact_own_sweep(const BaBatch* b, uint32_t what) {
@@ -1763,13 +1784,18 @@ static int exact_refusals(const BaBatch* b, uint32_t what, const void* out, bool
     if (!b->n) return fail("exact: the batch holds no pairs (a reload failed)");
     return 0;
 }
-// traced: the paths too (ba_batch_exact_cigars) -- the record's runs are left on the device in b->xt_runs at the offsets of b->xt_off
-static int batch_exact_device(BaBatch* b, uint32_t what, int32_t x_drop, const uint32_t* devpos, size_t m, BaExact* out, bool traced = false) {
-    if (exact_refusals(b, what, out, traced)) return 1;
-    const bool own = exact_own_sweep(b, what), profile = b->kind == BA_KIND_PROFILE_;   // (on a plain sequence batch the flag changes nothing)
+// form: scores only; the paths too (ba_batch_exact_cigars) -- the record's runs are left on the device in b->xt_runs at the offsets of
+// b->xt_off; or the paths in the batch's own mode (ba_batch_exact_paths), whatever the batch: the traced kernels of ba_exact_modes.hip, which
+// also leave the start cells in b->xt_start
+enum { EXACT_FORM_SCORES = 0, EXACT_FORM_CIGARS = 1, EXACT_FORM_PATHS = 2 };
+static int batch_exact_device(BaBatch* b, uint32_t what, int32_t x_drop, const uint32_t* devpos, size_t m, BaExact* out, int form = EXACT_FORM_SCORES) {
+    const bool traced = form != EXACT_FORM_SCORES, paths = form == EXACT_FORM_PATHS;
+    if (paths) what |= BA_EXACT_OWN_MODE;
+    if (exact_refusals(b, what, out, form == EXACT_FORM_CIGARS)) return 1;
+    const bool profile = b->kind == BA_KIND_PROFILE_, own = paths || exact_own_sweep(b, what);   // (on a plain sequence batch the flag changes nothing)
     what &= ~(uint32_t)BA_EXACT_OWN_MODE;
-    float& ms_out = traced ? b->xt_ms : b->exact_ms;
-    uint64_t& cells_out = traced ? b->xt_cells : b->exact_cells;
+    float& ms_out = paths ? b->xp_ms : traced ? b->xt_ms : b->exact_ms;
+    uint64_t& cells_out = paths ? b->xp_cells : traced ? b->xt_cells : b->exact_cells;
     ms_out = 0; cells_out = 0;
     if (!m) return 0;
     if (m > 0x7fffffffu) return fail("exact: too many records in one request");
@@ -1781,7 +1807,9 @@ static int batch_exact_device(BaBatch* b, uint32_t what, int32_t x_drop, const u
     if (traced)   // (the requested pairs only: the others need no region)
         for (size_t k = 0; k < m; k++) {
             const uint32_t d = devpos[k];
-            if (d != ba::EXACT_NO_PAIR && exact_trace_check_lengths(&ql[d], &rl[d], 1, b->h_order.empty() ? &d : &b->h_order[d])) return 1;
+            if (d == ba::EXACT_NO_PAIR) continue;
+            const uint32_t* name = b->h_order.empty() ? &d : &b->h_order[d];
+            if (profile ? exact_trace_check_lengths_profile(&ql[d], &rl[d], 1, name) : exact_trace_check_lengths(&ql[d], &rl[d], 1, name)) return 1;
         }
     // (the profile sweep shares this cost model: it also walks row 0, one row in |q| + 1, which neither the order nor the cuts notice)
     auto cost = [&](uint32_t k) { const uint32_t d = devpos[k]; return d == ba::EXACT_NO_PAIR ? 0ull : (uint64_t)ql[d] * rl[d]; };
@@ -1817,7 +1845,7 @@ static int batch_exact_device(BaBatch* b, uint32_t what, int32_t x_drop, const u
         for (size_t k = 0; k < m; k++) {
             const uint32_t d = devpos[k];
             rev_off[k + 1] = rev_off[k] + (d == ba::EXACT_NO_PAIR ? 0ull : (uint64_t)ql[d] + rl[d]);
-            if (d != ba::EXACT_NO_PAIR) tr_stride = std::max(tr_stride, ba::exact_trace_stride(ql[d], rl[d]));
+            if (d != ba::EXACT_NO_PAIR) tr_stride = std::max(tr_stride, ba::exact_trace_stride(ql[d] + (profile ? 1u : 0u), rl[d]));   // (row 0 of a profile is swept)
         }
         tr_stride = std::max<uint64_t>(tr_stride, 64);
         const uint64_t rev_bytes = std::max<uint64_t>(rev_off[m], 1) * 4;
@@ -1832,6 +1860,7 @@ static int batch_exact_device(BaBatch* b, uint32_t what, int32_t x_drop, const u
         if (b->xt_rev_off.bytes < (m + 1) * 8 && b->xt_rev_off.alloc((m + 1) * 8)) return 1;
         if (b->xt_nrun.bytes < m * 4 && b->xt_nrun.alloc(m * 4)) return 1;
         if (b->xt_off.bytes < (m + 1) * 8 && b->xt_off.alloc((m + 1) * 8)) return 1;
+        if (paths && b->xt_start.bytes < m * 8 && b->xt_start.alloc(m * 8)) return 1;
         // as many concurrent waves as free memory holds regions of the largest pair (a sixteenth is left for the run array), one at least
         const uint64_t region = tr_stride * 4;
         uint32_t want = wgs * ba::EXACT_WAVES;
@@ -1883,9 +1912,9 @@ static int batch_exact_device(BaBatch* b, uint32_t what, int32_t x_drop, const u
         xp.n = first[l + 1] - first[l];
         xp.work = b->ex_work.as<uint32_t>() + 2 * (size_t)first[l];
         xp.counter = b->ex_counter.as<uint32_t>() + l;
-        if (traced) {
-            uint32_t waves = std::min<uint32_t>(tr_waves, xp.n);
-            if (waves >= ba::EXACT_WAVES) waves -= waves % ba::EXACT_WAVES;
+        uint32_t waves = std::min<uint32_t>(tr_waves, xp.n);   // (the traced forms)
+        if (waves >= ba::EXACT_WAVES) waves -= waves % ba::EXACT_WAVES;
+        if (traced && !paths) {
             HIP_TRY(ba_launch_exact_trace(b->stream, &xp, waves));
         } else if (own) {   // k_exact_mode / k_exact_profile: the same records, row buffers (two words per column) and launch geometry
             ba::ExactModeParams mp{};
@@ -1893,7 +1922,8 @@ static int batch_exact_device(BaBatch* b, uint32_t what, int32_t x_drop, const u
             mp.start = (b->mode & BA_LOCAL_START) ? ba::EXACT_START_LOCAL : (b->mode & BA_FREE_QUERY_START_GAPS) ? ba::EXACT_START_FREE_ROW0 : ba::EXACT_START_GLOBAL;
             mp.end_free = (b->mode & BA_FREE_QUERY_END_GAPS) ? 1u : 0u;
             mp.max_size = (uint32_t)b->max_size;
-            HIP_TRY(ba_launch_exact_modes(b->stream, &mp, std::min<uint32_t>(wgs, (xp.n + ba::EXACT_WAVES - 1) / ba::EXACT_WAVES)));
+            if (paths) HIP_TRY(ba_launch_exact_modes_trace(b->stream, &mp, b->xt_start.as<uint32_t>(), waves));
+            else HIP_TRY(ba_launch_exact_modes(b->stream, &mp, std::min<uint32_t>(wgs, (xp.n + ba::EXACT_WAVES - 1) / ba::EXACT_WAVES)));
         } else
             HIP_TRY(ba_launch_exact(b->stream, &xp, std::min<uint32_t>(wgs, (xp.n + ba::EXACT_WAVES - 1) / ba::EXACT_WAVES)));
     }
@@ -1937,23 +1967,34 @@ static int batch_exact(BaBatch* b, uint32_t what, int32_t x_drop, const uint32_t
 }
 // The records, the run offsets (records + 1) and, with `runs`, the runs. A request equal to the last one on the same pairs is answered from
 // what that one left on the device.
-static int batch_exact_cigars(BaBatch* b, uint32_t what, int32_t x_drop, const uint32_t* which, size_t n_which, BaExact* out, uint64_t* run_off, uint32_t* runs,
+// Rec = BaExact: ba_batch_exact_cigars. Rec = BaExactPath: ba_batch_exact_paths -- the matrix of the batch's own mode, with the start cells.
+template <class Rec>
+static int batch_exact_cigars(BaBatch* b, uint32_t what, int32_t x_drop, const uint32_t* which, size_t n_which, Rec* out, uint64_t* run_off, uint32_t* runs,
                               uint64_t capacity) {
+    constexpr int form = std::is_same<Rec, BaExact>::value ? EXACT_FORM_CIGARS : EXACT_FORM_PATHS;
     if (!b) return fail("null batch");
+    if (!out) return fail("null argument: out");
     if (!run_off) return fail("null argument: run_off");
-    if (exact_refusals(b, what, out, true)) return 1;
+    if (form == EXACT_FORM_PATHS) what |= BA_EXACT_OWN_MODE;   // (the flag may be given and changes nothing)
+    if (exact_refusals(b, what, out, form == EXACT_FORM_CIGARS)) return 1;
     std::vector<uint32_t> devpos;
     if (exact_devpos(b, which, n_which, devpos)) return 1;
     const size_t m = devpos.size();
-    const bool kept = b->xt_valid && b->xt_what == what && b->xt_x_drop == x_drop && b->xt_loads == b->loads && b->xt_devpos == devpos;
+    const bool kept = b->xt_valid && b->xt_form == form && b->xt_what == what && b->xt_x_drop == x_drop && b->xt_loads == b->loads && b->xt_devpos == devpos;
     if (!kept) {
         b->xt_valid = false;
-        b->xt_out.assign(m, BaExact{}); b->xt_h_off.assign(m + 1, 0);
-        if (batch_exact_device(b, what, x_drop, devpos.data(), m, b->xt_out.data(), true)) return 1;
+        b->xt_out.assign(m, BaExact{}); b->xt_h_off.assign(m + 1, 0); b->xt_h_start.assign(2 * m, 0);
+        if (batch_exact_device(b, what, x_drop, devpos.data(), m, b->xt_out.data(), form)) return 1;
         if (m) HIP_TRY(hipMemcpy(b->xt_h_off.data(), b->xt_off.p, (m + 1) * 8, hipMemcpyDeviceToHost));
-        b->xt_what = what; b->xt_x_drop = x_drop; b->xt_loads = b->loads; b->xt_devpos = devpos; b->xt_valid = true;
+        if (m && form == EXACT_FORM_PATHS) HIP_TRY(hipMemcpy(b->xt_h_start.data(), b->xt_start.p, m * 8, hipMemcpyDeviceToHost));
+        b->xt_form = form; b->xt_what = what; b->xt_x_drop = x_drop; b->xt_loads = b->loads; b->xt_devpos = devpos; b->xt_valid = true;
     } else HIP_TRY(hipSetDevice(b->device));
-    std::copy(b->xt_out.begin(), b->xt_out.end(), out);
+    if constexpr (std::is_same<Rec, BaExact>::value) std::copy(b->xt_out.begin(), b->xt_out.end(), out);
+    else
+        for (size_t k = 0; k < m; k++) {
+            const BaExact& x = b->xt_out[k];
+            out[k] = BaExactPath{x.score, b->xt_h_start[2 * k], b->xt_h_start[2 * k + 1], x.query_idx, x.reference_idx, x.rows};
+        }
     std::copy(b->xt_h_off.begin(), b->xt_h_off.end(), run_off);
     if (!runs) return 0;
     const uint64_t total = b->xt_h_off[m];
@@ -1985,6 +2026,87 @@ static int extend_exact(BaExtendBatch* e, int32_t x_drop, const uint32_t* which,
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipMemcpy(score, d_seed.p, m * 4, hipMemcpyDeviceToHost));
     for (size_t k = 0; k < m; k++) { left[k] = rec[2 * k]; right[k] = rec[2 * k + 1]; score[k] += rec[2 * k].score + rec[2 * k + 1].score; }
+    return 0;
+}
+// The optimal path of every requested seed: both sides' EXTEND paths from the traced k_exact over the inner batch (record 2k the left side,
+// over the reversed prefixes, 2k + 1 the right one; their runs stay on the device), joined with the seed's ungapped columns by k_exact_join
+// -- counts, offsets, runs. The records are in the coordinates of ba_extend_batch_results.
+static int extend_exact_paths(BaExtendBatch* e, int32_t x_drop, const uint32_t* which, size_t n_which, BaExactPath* out, BaExact* left, BaExact* right,
+                              uint64_t* run_off, uint32_t* runs, uint64_t capacity) {
+    if (!e) return fail("null batch");
+    if (!out) return fail("null argument: out");
+    if (!run_off) return fail("null argument: run_off");
+    if (!e->n) return fail("exact: the batch holds no seeds (a reload failed)");
+    const size_t m = which ? n_which : e->n;
+    if (m > 0x3fffffffu) return fail("exact: too many records in one request");
+    std::vector<uint32_t> sel(m);
+    for (size_t k = 0; k < m; k++) {
+        sel[k] = which ? which[k] : (uint32_t)k;
+        if (sel[k] >= e->n) return fail("exact: which[%zu] = %u is out of range (the batch holds %u seeds)", k, sel[k], e->n);
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    const bool kept = e->xp_valid && e->xp_x_drop == x_drop && e->xp_which == sel;
+    if (!kept) {
+        e->xp_valid = false;
+        e->xp_out.assign(m, BaExactPath{}); e->xp_left.assign(m, BaExact{}); e->xp_right.assign(m, BaExact{}); e->xp_h_off.assign(m + 1, 0);
+        if (m) {
+            std::vector<uint32_t> side(2 * (size_t)e->n), devpos(2 * m), q_seed(e->n), r_seed(e->n), seed_len(e->n);
+            HIP_TRY(hipMemcpy(side.data(), e->side.p, side.size() * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(q_seed.data(), e->q_seed.p, (size_t)e->n * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(r_seed.data(), e->r_seed.p, (size_t)e->n * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(seed_len.data(), e->seed_len.p, (size_t)e->n * 4, hipMemcpyDeviceToHost));
+            for (size_t k = 0; k < m; k++) { devpos[2 * k] = side[2 * (size_t)sel[k]]; devpos[2 * k + 1] = side[2 * (size_t)sel[k] + 1]; }
+            std::vector<BaExact> rec(2 * m, BaExact{});
+            const bool sides = e->inner && e->n_sides;
+            if (sides) {
+                e->inner->xt_valid = false;   // (the inner batch's buffers now hold this request)
+                if (batch_exact_device(e->inner.get(), BA_EXACT_EXTEND, x_drop, devpos.data(), 2 * m, rec.data(), EXACT_FORM_CIGARS)) return 1;
+            } else {   // every side's run range is empty
+                if (e->xp_no_off.bytes < (2 * m + 1) * 8 && e->xp_no_off.alloc((2 * m + 1) * 8)) return 1;
+                HIP_TRY(hipMemset(e->xp_no_off.p, 0, (2 * m + 1) * 8));
+            }
+            if (e->xp_seed.bytes < m * 4 && e->xp_seed.alloc(m * 4)) return 1;
+            if (e->xp_sel.bytes < m * 4 && e->xp_sel.alloc(m * 4)) return 1;
+            if (e->xp_nrun.bytes < m * 4 && e->xp_nrun.alloc(m * 4)) return 1;
+            if (e->xp_off.bytes < (m + 1) * 8 && e->xp_off.alloc((m + 1) * 8)) return 1;
+            HIP_TRY(hipMemcpy(e->xp_sel.p, sel.data(), m * 4, hipMemcpyHostToDevice));
+            const ba::ExtendParams ep = e->params();
+            HIP_TRY(ba_launch_exact_seed(e->stream, &ep, e->xp_sel.as<uint32_t>(), (uint32_t)m, e->xp_seed.as<int32_t>()));
+            ba::ExactJoinParams jp{};
+            jp.m = (uint32_t)m; jp.eq = (e->mode & BA_CIGAR_EQ) ? 1u : 0u; jp.sel = e->xp_sel.as<uint32_t>();
+            jp.seed_len = ep.seed_len; jp.seed_pool = ep.seed_pool; jp.seed_q = ep.seed_q; jp.seed_r = ep.seed_r;
+            jp.side_runs = sides ? e->inner->xt_runs.as<uint32_t>() : nullptr;
+            jp.side_off = sides ? e->inner->xt_off.as<uint64_t>() : e->xp_no_off.as<uint64_t>();
+            jp.nrun = e->xp_nrun.as<uint32_t>(); jp.off = e->xp_off.as<uint64_t>(); jp.runs = nullptr;
+            HIP_TRY(ba_launch_exact_join(e->stream, &jp));
+            HIP_TRY(ba_launch_offsets(e->stream, e->xp_nrun.as<uint32_t>(), e->xp_off.as<uint64_t>(), (uint32_t)m));
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            HIP_TRY(hipMemcpy(e->xp_h_off.data(), e->xp_off.p, (m + 1) * 8, hipMemcpyDeviceToHost));
+            const uint64_t total = e->xp_h_off[m];
+            if (e->xp_runs.bytes < total * 4 && e->xp_runs.alloc(total * 4)) return 1;
+            jp.runs = e->xp_runs.as<uint32_t>();
+            HIP_TRY(ba_launch_exact_join(e->stream, &jp));
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            std::vector<int32_t> seed_score(m);
+            HIP_TRY(hipMemcpy(seed_score.data(), e->xp_seed.p, m * 4, hipMemcpyDeviceToHost));
+            for (size_t k = 0; k < m; k++) {
+                const BaExact &l = rec[2 * k], &r = rec[2 * k + 1];
+                const uint32_t s = sel[k];
+                e->xp_left[k] = l; e->xp_right[k] = r;
+                e->xp_out[k] = BaExactPath{l.score + seed_score[k] + r.score, q_seed[s] - l.query_idx, r_seed[s] - l.reference_idx,
+                                           q_seed[s] + seed_len[s] + r.query_idx, r_seed[s] + seed_len[s] + r.reference_idx, l.rows + r.rows};
+            }
+        }
+        e->xp_x_drop = x_drop; e->xp_which = sel; e->xp_valid = true;
+    }
+    std::copy(e->xp_out.begin(), e->xp_out.end(), out);
+    if (left) std::copy(e->xp_left.begin(), e->xp_left.end(), left);
+    if (right) std::copy(e->xp_right.begin(), e->xp_right.end(), right);
+    std::copy(e->xp_h_off.begin(), e->xp_h_off.end(), run_off);
+    if (!runs) return 0;
+    const uint64_t total = e->xp_h_off[m];
+    if (capacity < total) return fail("exact: the runs buffer holds %llu runs, the request has %llu", (unsigned long long)capacity, (unsigned long long)total);
+    if (total) HIP_TRY(hipMemcpy(runs, e->xp_runs.p, total * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2326,6 +2448,27 @@ int ba_batch_exact_cigars_ms(BaBatch* b, float* ms, uint64_t* cells) {
     if (cells) *cells = b->xt_cells;
     return 0;
 }
+// (the ba_*_exact_paths calls name a null out or run_off whatever the batch is)
+static int exact_paths_args(const void* out, const void* run_off) {
+    if (!out) return fail("null argument: out");
+    if (!run_off) return fail("null argument: run_off");
+    return 0;
+}
+int ba_batch_exact_paths(BaBatch* b, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, BaExactPath* out, uint64_t* run_off, uint32_t* runs,
+                         uintptr_t runs_cap) {
+    if (exact_paths_args(out, run_off)) return 1;
+    return batch_exact_cigars(b, what, x_drop, which, n_which, out, run_off, runs, runs_cap);
+}
+int ba_batch_exact_paths_ms(BaBatch* b, float* ms, uint64_t* cells) {
+    if (!b) return fail("null batch");
+    if (ms) *ms = b->xp_ms;
+    if (cells) *cells = b->xp_cells;
+    return 0;
+}
+int ba_exact_paths_check_lengths_profile(const uint32_t* q_len, const uint32_t* r_len, uintptr_t n) {
+    if (n && (!q_len || !r_len)) return fail("null argument");
+    return exact_trace_check_lengths_profile(q_len, r_len, n, nullptr);
+}
 int ba_exact_trace_check_lengths(const uint32_t* q_len, const uint32_t* r_len, uintptr_t n) {
     if (n && (!q_len || !r_len)) return fail("null argument");
     return exact_trace_check_lengths(q_len, r_len, n, nullptr);
@@ -2481,6 +2624,11 @@ int ba_extend_batch_stats(BaExtendBatch* e, BaAlignStats* out) {
 // bytes on the device (raw), by k_pack_images' rule. (The sides' texts cannot be joined: the equal stretches merge across the seed.)
 int ba_extend_batch_exact(BaExtendBatch* e, int32_t x_drop, const uint32_t* which, uintptr_t n_which, BaExact* left, BaExact* right, int32_t* score) {
     return extend_exact(e, x_drop, which, n_which, left, right, score);
+}
+int ba_extend_batch_exact_paths(BaExtendBatch* e, int32_t x_drop, const uint32_t* which, uintptr_t n_which, BaExactPath* out, BaExact* left, BaExact* right,
+                                uint64_t* run_off, uint32_t* runs, uintptr_t runs_cap) {
+    if (exact_paths_args(out, run_off)) return 1;
+    return extend_exact_paths(e, x_drop, which, n_which, out, left, right, run_off, runs, runs_cap);
 }
 int ba_extend_batch_text(BaExtendBatch* e, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) {
     if (!e) return fail("null batch");
@@ -2819,7 +2967,8 @@ static int parts_exact(BaPartSet* m, uint32_t what, int32_t x_drop, const uint32
 }
 // ... and its own paths: the parts' offsets become run counts in the caller's order, then offsets; with `runs`, every part's runs are
 // scattered to them (a part answers that second call from its device buffers)
-static int parts_exact_cigars(BaPartSet* m, uint32_t what, int32_t x_drop, const uint32_t* which, size_t n_which, BaExact* out, uint64_t* run_off,
+template <class Rec>
+static int parts_exact_cigars(BaPartSet* m, uint32_t what, int32_t x_drop, const uint32_t* which, size_t n_which, Rec* out, uint64_t* run_off,
                               uint32_t* runs, uint64_t capacity) {
     if (!m) return fail("null batch");
     if (!out) return fail("null argument: out");
@@ -2834,7 +2983,7 @@ static int parts_exact_cigars(BaPartSet* m, uint32_t what, int32_t x_drop, const
         if (p >= m->n) return fail("exact: which[%zu] = %u is out of range (the batch holds %zu pairs)", k, p, m->n);
         local[part_of[p]].push_back(local_of[p]); at[part_of[p]].push_back((uint32_t)k);
     }
-    std::vector<BaExact> tmp;
+    std::vector<Rec> tmp;
     std::vector<std::vector<uint64_t>> po(m->part.size());
     std::fill(run_off, run_off + cnt + 1, 0);
     for (size_t k = 0; k < m->part.size(); k++) {
@@ -2979,6 +3128,11 @@ int ba_multibatch_exact_cigars(BaMultiBatch* m, uint32_t what, int32_t x_drop, c
                                uint32_t* runs, uint64_t capacity) {
     return parts_exact_cigars(m, what, x_drop, which, n_which, out, run_off, runs, capacity);
 }
+int ba_multibatch_exact_paths(BaMultiBatch* m, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, BaExactPath* out, uint64_t* run_off,
+                              uint32_t* runs, uintptr_t runs_cap) {
+    if (exact_paths_args(out, run_off)) return 1;
+    return parts_exact_cigars(m, what, x_drop, which, n_which, out, run_off, runs, runs_cap);
+}
 int ba_multibatch_exact(BaMultiBatch* m, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, BaExact* out) { return parts_exact(m, what, x_drop, which, n_which, out); }
 int ba_multibatch_text(BaMultiBatch* m, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) { return parts_text(m, what, offsets, text, capacity); }
 int ba_multibatch_kernel_ms(BaMultiBatch* m, float* ms, int capacity) {   // per slice, of the last run; returns the number of slices
@@ -3096,6 +3250,11 @@ int ba_sized_batch_stats(BaSizedBatch* m, BaAlignStats* out) { return parts_stat
 int ba_sized_batch_exact_cigars(BaSizedBatch* m, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, BaExact* out, uint64_t* run_off,
                                 uint32_t* runs, uint64_t capacity) {
     return parts_exact_cigars(m, what, x_drop, which, n_which, out, run_off, runs, capacity);
+}
+int ba_sized_batch_exact_paths(BaSizedBatch* m, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, BaExactPath* out, uint64_t* run_off,
+                               uint32_t* runs, uintptr_t runs_cap) {
+    if (exact_paths_args(out, run_off)) return 1;
+    return parts_exact_cigars(m, what, x_drop, which, n_which, out, run_off, runs, runs_cap);
 }
 int ba_sized_batch_exact(BaSizedBatch* m, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, BaExact* out) { return parts_exact(m, what, x_drop, which, n_which, out); }
 int ba_sized_batch_text(BaSizedBatch* m, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) { return parts_text(m, what, offsets, text, capacity); }

@@ -76,6 +76,8 @@ hipError_t ba_launch_exact_runs(hipStream_t s, const uint32_t* rev, const uint64
 hipError_t ba_launch_exact_seed(hipStream_t s, const ba::ExtendParams* ep, const uint32_t* which, uint32_t m, int32_t* out);
 // ba_exact_modes.hip
 hipError_t ba_launch_exact_modes(hipStream_t s, const ba::ExactModeParams* mp, uint32_t wgs);
+hipError_t ba_launch_exact_modes_trace(hipStream_t s, const ba::ExactModeParams* mp, uint32_t* start_cell, uint32_t waves);   // (the BA_EXACT_TRACED unit)
+hipError_t ba_launch_exact_join(hipStream_t s, const ba::ExactJoinParams* jp);
 // ba_text.hip
 hipError_t ba_launch_text_len(hipStream_t s, const ba::TextParams* tp);
 hipError_t ba_launch_text_write(hipStream_t s, const ba::TextParams* tp);

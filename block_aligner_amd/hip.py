@@ -62,6 +62,12 @@ class ExactC(C.Structure):
     _fields_ = [("score", C.c_int32), ("query_idx", C.c_uint32), ("reference_idx", C.c_uint32), ("rows", C.c_uint32)]
 
 
+class ExactPathC(C.Structure):
+    """struct BaExactPath: one record of the ba_*_exact_paths calls."""
+    _fields_ = [("score", C.c_int32), ("q_start", C.c_uint32), ("r_start", C.c_uint32), ("q_end", C.c_uint32), ("r_end", C.c_uint32),
+                ("rows", C.c_uint32)]
+
+
 class AccuracyC(C.Structure):
     """struct BaAccuracy: what ba_accuracy_summary reports."""
     _fields_ = [("n", C.c_uint64), ("compared", C.c_uint64), ("skipped", C.c_uint64), ("wrong", C.c_uint64), ("below", C.c_uint64),
@@ -71,6 +77,9 @@ class AccuracyC(C.Structure):
 EXACT_DTYPE = np.dtype(ExactC)
 if C.sizeof(ExactC) != 16 or EXACT_DTYPE.itemsize != 16:
     raise ImportError(f"struct BaExact must be 16 bytes, the binding declares {C.sizeof(ExactC)}")
+EXACT_PATH_DTYPE = np.dtype(ExactPathC)
+if C.sizeof(ExactPathC) != 24 or EXACT_PATH_DTYPE.itemsize != 24:
+    raise ImportError(f"struct BaExactPath must be 24 bytes, the binding declares {C.sizeof(ExactPathC)}")
 EXACT_GLOBAL, EXACT_EXTEND = 0, 1   # ba_*_exact: the quantity
 EXACT_OWN_MODE = 1 << 8             # ... and the flag bit: under the batch's own start / end rules, or its profile's gap costs
 EXACT_TRACE_MAX_CELLS = 1 << 31     # ba_*_exact_cigars: |q| * |r| of a pair
@@ -195,7 +204,11 @@ def lib() -> C.CDLL:
         for f in ("ba_batch", "ba_sized_batch", "ba_multibatch"):
             getattr(L, f"{f}_exact").argtypes = [vp, u32, i32, vp, sz, vp]
             getattr(L, f"{f}_exact_cigars").argtypes = [vp, u32, i32, vp, sz, vp, vp, vp, C.c_uint64]
+            getattr(L, f"{f}_exact_paths").argtypes = [vp, u32, i32, vp, sz, vp, vp, vp, sz]
         L.ba_extend_batch_exact.argtypes = [vp, i32, vp, sz, vp, vp, vp]
+        L.ba_extend_batch_exact_paths.argtypes = [vp, i32, vp, sz, vp, vp, vp, vp, vp, sz]
+        L.ba_batch_exact_paths_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+        L.ba_exact_paths_check_lengths_profile.argtypes = [vp, vp, sz]
         L.ba_batch_exact_cigars_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
         L.ba_exact_trace_check_lengths.argtypes = [vp, vp, sz]
         L.ba_batch_exact_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
@@ -308,6 +321,15 @@ def exact_trace_check_lengths(q_len, r_len) -> None:
     if len(q_len) != len(r_len):
         raise ValueError("q_len and r_len must have one entry per pair")
     if lib().ba_exact_trace_check_lengths(q_len.ctypes.data, r_len.ctypes.data, len(q_len)):
+        raise RuntimeError(last_error())
+
+
+def exact_paths_check_lengths_profile(q_len, r_len) -> None:
+    """The length guards of exact_paths() on a profile batch on their own (needs no device; r_len: profile lengths):
+    exact_check_lengths_profile's and (|q| + 1) * |r| <= EXACT_TRACE_MAX_CELLS."""
+    q_len = np.ascontiguousarray(q_len, dtype=np.uint32)
+    r_len = np.ascontiguousarray(r_len, dtype=np.uint32)
+    if lib().ba_exact_paths_check_lengths_profile(q_len.ctypes.data, r_len.ctypes.data, len(q_len)):
         raise RuntimeError(last_error())
 
 
@@ -598,6 +620,23 @@ class _Batch:
         self._call("exact_cigars", int(what), int(x_drop), wp, wn, rec.ctypes.data, off.ctypes.data, runs.ctypes.data, runs.size)
         return {k: rec[k].copy() for k in EXACT_DTYPE.names}, runs, off
 
+    def exact_paths(self, what=None, x_drop=-1, which=None):
+        """The optimal alignment paths in the batch's own mode, computed on the device (ba_*_exact_paths; no run needed) -> (rec, runs,
+        off). Every batch is served: LOCAL_START / FREE_QUERY_* batches, profile batches, plain ones (where the runs are exact_cigars()'s).
+        rec: dict of arrays score, q_start, r_start, q_end, r_end, rows -- score, (q_end, r_end) and rows are exact(own_mode=True)'s score,
+        end cell and rows, (q_start, r_start) is the cell where the backward walk stopped. runs[off[k]:off[k + 1]] are record k's packed
+        (len << 4 | op) runs over q[q_start:q_end] and r[r_start:r_end]; '=' / 'X' in a CIGAR_EQ sequence batch, 'M' otherwise. what,
+        x_drop and which as in exact(); EXACT_OWN_MODE in what changes nothing."""
+        if what is None:
+            what = EXACT_EXTEND if self.mode & X_DROP else EXACT_GLOBAL
+        w, wp, wn = _which(which)
+        m = self.n if w is None else wn
+        rec, off = np.zeros(m, EXACT_PATH_DTYPE), np.zeros(m + 1, np.uint64)   # the two-call pattern: records and offsets, then the runs
+        self._call("exact_paths", int(what), int(x_drop), wp, wn, rec.ctypes.data, off.ctypes.data, None, 0)
+        runs = np.zeros(int(off[-1]), np.uint32)
+        self._call("exact_paths", int(what), int(x_drop), wp, wn, rec.ctypes.data, off.ctypes.data, runs.ctypes.data, runs.size)
+        return {k: rec[k].copy() for k in EXACT_PATH_DTYPE.names}, runs, off
+
     def accuracy(self, x_drop=-1, which=None, own_mode=False):
         """After a run: the batch's results against exact() of the same pairs (accuracy_summary) -> dict. own_mode as in exact()."""
         ex = self.exact(None, x_drop, which, own_mode)
@@ -699,6 +738,12 @@ class BatchAligner(_Batch):
         """(HIP-event milliseconds, cells) of the last exact_cigars() call that computed: sweep, walk, offsets and gather."""
         ms, cells = C.c_float(), C.c_uint64()
         self._call("exact_cigars_ms", C.byref(ms), C.byref(cells))
+        return ms.value, int(cells.value)
+
+    def exact_paths_ms(self):
+        """(HIP-event milliseconds, cells) of the last exact_paths() call that computed: sweep, walk, offsets and gather."""
+        ms, cells = C.c_float(), C.c_uint64()
+        self._call("exact_paths_ms", C.byref(ms), C.byref(cells))
         return ms.value, int(cells.value)
 
     def text_ms(self) -> float:
@@ -868,6 +913,25 @@ class ExtendBatchAligner(_Batch):
         left, right, score = np.zeros(m, EXACT_DTYPE), np.zeros(m, EXACT_DTYPE), np.zeros(m, np.int32)
         self._call("exact", int(x_drop), wp, wn, left.ctypes.data, right.ctypes.data, score.ctypes.data)
         return dict(left={k: left[k].copy() for k in EXACT_DTYPE.names}, right={k: right[k].copy() for k in EXACT_DTYPE.names}, score=score)
+
+    def exact_paths(self, what=None, x_drop=-1, which=None):
+        """The optimal path of every seed's extension (ba_extend_batch_exact_paths; no run needed) -> (rec, runs, off): the left side's
+        EXACT_EXTEND path turned round + the seed's ungapped columns + the right side's path, merged. rec: score (left + seed + right),
+        q_start, r_start, q_end, r_end (the coordinates of results()), rows (left + right), and the sides' records as exact() gives them
+        in the dicts left / right. what: None or EXACT_EXTEND (extension batches have no other quantity)."""
+        if what is not None and int(what) & ~EXACT_OWN_MODE != EXACT_EXTEND:
+            raise RuntimeError("exact: an extension batch has one quantity, EXACT_EXTEND on both sides of the seed")
+        w, wp, wn = _which(which)
+        m = self.n if w is None else wn
+        rec, off = np.zeros(m, EXACT_PATH_DTYPE), np.zeros(m + 1, np.uint64)
+        left, right = np.zeros(m, EXACT_DTYPE), np.zeros(m, EXACT_DTYPE)
+        self._call("exact_paths", int(x_drop), wp, wn, rec.ctypes.data, left.ctypes.data, right.ctypes.data, off.ctypes.data, None, 0)
+        runs = np.zeros(int(off[-1]), np.uint32)
+        self._call("exact_paths", int(x_drop), wp, wn, rec.ctypes.data, left.ctypes.data, right.ctypes.data, off.ctypes.data, runs.ctypes.data, runs.size)
+        out = {k: rec[k].copy() for k in EXACT_PATH_DTYPE.names}
+        out["left"] = {k: left[k].copy() for k in EXACT_DTYPE.names}
+        out["right"] = {k: right[k].copy() for k in EXACT_DTYPE.names}
+        return out, runs, off
 
     def accuracy(self, x_drop=-1, which=None):
         """After a run: the spliced scores against exact()'s (accuracy_summary without the end comparison) -> dict."""

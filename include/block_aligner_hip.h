@@ -485,7 +485,7 @@ int ba_exact_check_lengths(const uint32_t* q_len, const uint32_t* r_len, uintptr
  *
  * Refused, beside the refusals above that do not concern the mode: BA_EXACT_OWN_MODE on a profile batch that also has BA_LOCAL_START or
  * BA_FREE_QUERY_* (that combination has no definition yet); BA_EXACT_OWN_MODE passed to ba_*_exact_cigars on a profile batch or a batch
- * with one of the mode bits (scores only: the four trace bits per cell have no room for "the path starts here"); a pair of a profile
+ * with one of the mode bits (there the flag gives scores only; ba_*_exact_paths below returns those paths); a pair of a profile
  * batch whose (|q| + |r|) * 384 -- three int8 terms per column -- does not stay above the sentinel -2^30 (the message names the pair).
  * ba_extend_batch_exact has no `what`: extension batches are created without these modes and without profiles. */
 enum { BA_EXACT_OWN_MODE = 1u << 8 };   /* OR-ed into BA_EXACT_GLOBAL / BA_EXACT_EXTEND */
@@ -525,7 +525,8 @@ int ba_exact_check_lengths_profile(const uint32_t* q_len, const uint32_t* r_len,
  * sweep keeps four bits per cell in a trace region per resident wave, sized for the largest requested pair (with the length limit above, below
  * 1.3 GiB); as many waves run at once as free device memory holds regions, one at least, and a request whose single region does not fit is
  * refused with the bytes needed. Every record's runs wait, unmerged with their neighbours' offsets, in 4 * (|q| + |r|) bytes until the offsets
- * are known. The buffers are allocated on the first call, grow, and are freed by destroy. Extension batches have no such call. */
+ * are known. The buffers are allocated on the first call, grow, and are freed by destroy. Extension batches have no such call
+ * (ba_extend_batch_exact_paths below is theirs). */
 #define BA_EXACT_TRACE_MAX_CELLS 2147483648ull   /* 2^31 */
 int ba_batch_exact_cigars(BaBatch* batch, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, struct BaExact* out,
                           uint64_t* run_off, uint32_t* runs, uint64_t capacity);
@@ -538,6 +539,68 @@ int ba_multibatch_exact_cigars(BaMultiBatch* batch, uint32_t what, int32_t x_dro
 int ba_batch_exact_cigars_ms(BaBatch* batch, float* ms, uint64_t* cells);
 /* The length guards of the path calls on their own (host only, no device): ba_exact_check_lengths' and |q| * |r| <= BA_EXACT_TRACE_MAX_CELLS. */
 int ba_exact_trace_check_lengths(const uint32_t* q_len, const uint32_t* r_len, uintptr_t n_pairs);
+/* ---- optimal paths in the batch's own mode ("Optimal paths in the batch's own mode").
+ *
+ * ba_*_exact_cigars serve plain global-start sequence batches and refuse the rest; these calls return the optimal path of every batch a caller
+ * can create: BA_LOCAL_START / BA_FREE_QUERY_* batches, profile batches, plain batches, and (ba_extend_batch_exact_paths) the seeds of an
+ * extension batch. The older calls behave exactly as before.
+ *
+ * what: BA_EXACT_GLOBAL or BA_EXACT_EXTEND. The matrix is always that of the batch's own mode ("exact scores in the batch's own mode"
+ * above); BA_EXACT_OWN_MODE may be OR-ed in and changes nothing. Any other quantity is refused.
+ *
+ * Records (struct BaExactPath): score, (q_end, r_end) and rows are what ba_*_exact(what | BA_EXACT_OWN_MODE) returns as score,
+ * (query_idx, reference_idx) and rows; (q_start, r_start) is the cell where the walk below stopped. The runs (length << 4 | op, alignment
+ * order, adjacent runs of one op merged) align q[q_start .. q_end) against r[r_start .. r_end): clipped ends produce no runs. Match-type
+ * columns are M, or = / X by the image bytes in a BA_CIGAR_EQ sequence batch. A profile batch has no reference letters and emits M
+ * (it cannot be created with BA_CIGAR_EQ: ba_batch_create_profile refuses the flag). Rescoring the runs from the start cell under the mode's rules gives exactly `score`.
+ *
+ * The walk, sequence matrices. H, V, Z are those of the own-mode score definition. The walk starts at the record's end cell in state H;
+ * states V and Z are exactly those of ba_*_exact_cigars (extension preferred). State H at (i, j):
+ *   BA_LOCAL_START            if H[i][j] == 0: stop. This comes before every move, a diagonal that also ties included; row 0 and column 0
+ *                             are zero, so they stop too.
+ *   BA_FREE_QUERY_START_GAPS  at i == 0: stop, emitting nothing. At j == 0: emit I x i and stop (at (0, 0)).
+ *   neither start bit         (only BA_FREE_QUERY_END_GAPS, or a plain batch) at i == 0: emit D x j; at j == 0: emit I x i; stop at (0, 0).
+ *   otherwise                 diagonal (one match-type column, to (i-1, j-1), state H) if H[i][j] == H[i-1][j-1] + s(q_i, r_j);
+ *                             else state V if H[i][j] == V[i][j]; else state Z.
+ * The end rule needs nothing of the walk: in a BA_FREE_QUERY_END_GAPS batch the BA_EXACT_GLOBAL record already ends at (|q|, argmax j).
+ * On a plain batch the result equals ba_batch_exact_cigars run for run, with start (0, 0).
+ *
+ * The walk, profiles. T, Z, V, H are those of the profile recurrence above; row 0 is a row like the others. The walk starts in state H at
+ * the end cell and always stops at (0, 0):
+ *   state H at (i, j):  j == 0: emit I x i and stop. Otherwise go to state T if H[i][j] == T[i][j], else to state V.
+ *   state T at (i, j):  (0, 0): stop. If i, j >= 1 and T[i][j] == H[i-1][j-1] + s(j, q_i): emit M, go to (i-1, j-1), state H.
+ *                       Else go to state Z.
+ *   state Z at (i, j):  emit D. If Z[i][j] == Z[i][j-1] + e stay in state Z, else go to state H; either way to (i, j-1).
+ *   state V at (i, j):  emit I. If V[i][j] == V[i-1][j] + e stay in state V, else go to state T (V opens from T); either way to (i-1, j).
+ * Four bits per cell suffice (H == T, T == diagonal, V extends, Z extends). Rescoring: a D run over positions j .. j+n-1 costs
+ * oC[j] + n e + cC[j+n-1], an I run of n residues after position j costs oR[j] + n e, an M column s(j, q_i).
+ *
+ * Extension batches. Per requested seed the left side is walked over the reversed prefixes the batch holds, the right side over the suffixes,
+ * both as ba_*_exact_cigars walks BA_EXACT_EXTEND. The runs are the left path turned round + the seed's ungapped columns (M, or = / X in a
+ * BA_CIGAR_EQ batch) + the right path, merged across both joints. score = left + seed + right; q_start, r_start, q_end, r_end are in the
+ * coordinates of ba_extend_batch_results (the oriented frame, for strand = 1 seeds too); rows = left.rows + right.rows; an empty side
+ * contributes nothing. left / right (may be NULL) receive the sides' records as ba_extend_batch_exact gives them.
+ *
+ * Protocol and limits: the two-call pattern, the same-arguments cache, `which` and the memory and "in flight" refusals are those of
+ * ba_batch_exact_cigars. BA_EXACT_TRACE_MAX_CELLS applies to |q| * |r|; a profile pair counts (|q| + 1) * |r|, because the profile sweep
+ * owns row 0. The trace keeps four bits per cell (in a BA_LOCAL_START matrix "H == 0" is marked by the two bits the walk never reads
+ * together), so the region size is that of ba_*_exact_cigars. Still refused: a profile batch that also has BA_LOCAL_START or
+ * BA_FREE_QUERY_* -- its scores have no definition either. */
+struct BaExactPath { int32_t score; uint32_t q_start, r_start, q_end, r_end, rows; };   /* 24 bytes */
+int ba_batch_exact_paths(BaBatch* batch, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, struct BaExactPath* out,
+                         uint64_t* run_off, uint32_t* runs, uintptr_t runs_cap);
+/* every part computes its own pairs (a multi-device batch: on its own device) */
+int ba_sized_batch_exact_paths(BaSizedBatch* batch, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, struct BaExactPath* out,
+                               uint64_t* run_off, uint32_t* runs, uintptr_t runs_cap);
+int ba_multibatch_exact_paths(BaMultiBatch* batch, uint32_t what, int32_t x_drop, const uint32_t* which, uintptr_t n_which, struct BaExactPath* out,
+                              uint64_t* run_off, uint32_t* runs, uintptr_t runs_cap);
+int ba_extend_batch_exact_paths(BaExtendBatch* batch, int32_t x_drop, const uint32_t* which, uintptr_t n_which, struct BaExactPath* out,
+                                struct BaExact* left, struct BaExact* right, uint64_t* run_off, uint32_t* runs, uintptr_t runs_cap);
+/* HIP-event time (ms; sweep, walk, offsets and gather) and cells of the last ba_batch_exact_paths call that computed; either may be NULL */
+int ba_batch_exact_paths_ms(BaBatch* batch, float* ms, uint64_t* cells);
+/* The length guards of the path calls on a profile batch on their own (host only, no device): ba_exact_check_lengths_profile's and
+ * (|q| + 1) * |r| <= BA_EXACT_TRACE_MAX_CELLS. For sequence batches ba_exact_trace_check_lengths holds. */
+int ba_exact_paths_check_lengths_profile(const uint32_t* q_len, const uint32_t* r_len, uintptr_t n_pairs);
 /* Host only, no device: the results of a run against exact records of the same pairs. Pairs whose status has an overflow, lost or watchdog
  * bit are skipped; diff = exact - score over the others; wrong counts diff != 0, below diff > 0 (the heuristic missed the optimum), above
  * diff < 0; diff_end counts compared pairs whose end cell differs; mean_rel_error is the mean of diff / |exact| over the wrong pairs with
