@@ -31,7 +31,7 @@ BA_HD constexpr uint64_t exact_row_stride(uint32_t max_r) { return ((uint64_t)ma
 
 // The traced form (ba_*_exact_cigars): four bits per cell, what the backward walk needs to know of it.
 constexpr uint32_t EXACT_TR_DIAG = 1;   // H[i][j] == H[i-1][j-1] + s(q_i, r_j)
-constexpr uint32_t EXACT_TR_HV = 2;     // H[i][j] == V[i][j]
+constexpr uint32_t EXACT_TR_HV = 2;     // H[i][j] == V[i][j]; left clear under DIAG, where no walk reads it
 constexpr uint32_t EXACT_TR_VEXT = 4;   // V[i][j] == V[i-1][j] + extend
 constexpr uint32_t EXACT_TR_ZEXT = 8;   // Z[i][j] == Z[i][j-1] + extend
 // One wave's trace region, in dwords: per band of 64 rows, one dword per lane and eight steps of the skewed sweep (|r| + 63 steps at most).
@@ -67,7 +67,7 @@ struct ExactParams {
     uint32_t eq;
 };
 
-// ------------------------------------------------------------------ the batch's own mode (BA_EXACT_OWN_MODE; ba_exact_modes.hip)
+// ------------------------------------------------------------------ the batch's own mode (BA_EXACT_OWN_MODE)
 constexpr uint32_t EXACT_OWN_MODE = 1u << 8;   // flag bit of `what`, beside EXACT_GLOBAL / EXACT_EXTEND
 // the start rule of a sequence batch: as k_exact's; H[0][j] = 0 (BA_FREE_QUERY_START_GAPS); H[0][j] = H[i][0] = 0 and H floored at 0 (BA_LOCAL_START)
 constexpr uint32_t EXACT_START_GLOBAL = 0, EXACT_START_FREE_ROW0 = 1, EXACT_START_LOCAL = 2;
@@ -83,11 +83,11 @@ struct ExactModeParams {
     uint32_t max_size;           // profiles: the batch's largest block, which sizes the images (profile_positions)
 };
 
-// ------------------------------------------------------------------ optimal paths in the batch's own mode (ba_*_exact_paths; ba_exact_modes.hip,
-// compiled with BA_EXACT_TRACED). The traced fields of ExactParams are used as k_exact uses them; the nibble layout is exact_trace_words'. The
-// kernels take one more argument, start_cell: record k's walk stopped at cell (start_cell[2k], start_cell[2k + 1]).
-// Sequence kinds keep EXACT_TR_*, with one change that costs no memory: the walk never reads HV under DIAG, so the sweep clears HV
-// there, and DIAG | HV together mark "H == 0" in a BA_LOCAL_START matrix: the path starts here.
+// ------------------------------------------------------------------ optimal paths in the batch's own mode (ba_*_exact_paths).
+// The traced fields of ExactParams are used as k_exact uses them; the nibble layout is exact_trace_words'. The kernels take one more
+// argument, start_cell: record k's walk stopped at cell (start_cell[2k], start_cell[2k + 1]).
+// Sequence kinds keep EXACT_TR_*, with one addition that costs no memory: HV is clear under DIAG, so DIAG | HV together mark "H == 0" in
+// a BA_LOCAL_START matrix: the path starts here.
 constexpr uint32_t EXACT_TR_STOP = EXACT_TR_DIAG | EXACT_TR_HV;
 // Profiles: H == T, T == H[i-1][j-1] + s (never set in row 0), and VEXT / ZEXT as above. Row 0 is a swept row: a pair has
 // ceil((|q| + 1) / 64) bands and is traced while (|q| + 1) * |r| <= EXACT_TRACE_MAX_CELLS.

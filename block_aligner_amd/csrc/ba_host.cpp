@@ -1726,36 +1726,20 @@ static_assert(sizeof(BaExact) == sizeof(ba::Exact) && offsetof(BaExact, referenc
               offsetof(BaExact, rows) == offsetof(ba::Exact, rows), "BaExact and ba::Exact differ");
 constexpr uint64_t EXACT_LAUNCH_CELLS = 1ull << 36;
 constexpr uint32_t EXACT_WAVES_PER_CU = 16;
-static int exact_check_lengths(const uint32_t* ql, const uint32_t* rl, size_t n, const uint32_t* name) {
-    for (size_t p = 0; p < n; p++)
-        if ((uint64_t)ql[p] + rl[p] > ba::EXACT_MAX_LEN2)
-            return fail("exact: pair %zu (|q| = %u, |r| = %u) is too long for int32 scores: |q| + |r| may be %llu at most", name ? (size_t)name[p] : p,
-                        ql[p], rl[p], (unsigned long long)ba::EXACT_MAX_LEN2);
-    return 0;
-}
-// profile batches (BA_EXACT_OWN_MODE): three int8 terms per column
-static int exact_check_lengths_profile(const uint32_t* ql, const uint32_t* rl, size_t n, const uint32_t* name) {
-    for (size_t p = 0; p < n; p++)
-        if ((uint64_t)ql[p] + rl[p] > ba::EXACT_MAX_LEN2_PROFILE)
-            return fail("exact: pair %zu (|q| = %u, profile length = %u) is too long for int32 scores: |q| + |r| may be %llu at most for a profile batch",
-                        name ? (size_t)name[p] : p, ql[p], rl[p], (unsigned long long)ba::EXACT_MAX_LEN2_PROFILE);
-    return 0;
-}
 static_assert(ba::EXACT_TRACE_MAX_CELLS == BA_EXACT_TRACE_MAX_CELLS, "BA_EXACT_TRACE_MAX_CELLS and ba::EXACT_TRACE_MAX_CELLS differ");
-static int exact_trace_check_lengths(const uint32_t* ql, const uint32_t* rl, size_t n, const uint32_t* name) {
-    if (exact_check_lengths(ql, rl, n, name)) return 1;
+// The length guards. Every pair must fit int32 scores; a profile column adds three int8 terms. traced: every pair must also fit a trace
+// region; the profile sweep owns row 0, so a pair has |q| + 1 traced rows there.
+static int exact_check_lengths(bool profile, bool traced, const uint32_t* ql, const uint32_t* rl, size_t n, const uint32_t* name) {
+    const uint64_t max_len2 = profile ? ba::EXACT_MAX_LEN2_PROFILE : ba::EXACT_MAX_LEN2;
     for (size_t p = 0; p < n; p++)
-        if ((uint64_t)ql[p] * rl[p] > ba::EXACT_TRACE_MAX_CELLS)
-            return fail("exact: pair %zu (|q| = %u, |r| = %u) is too large for a traced matrix: |q| * |r| may be %llu at most (BA_EXACT_TRACE_MAX_CELLS)",
-                        name ? (size_t)name[p] : p, ql[p], rl[p], (unsigned long long)ba::EXACT_TRACE_MAX_CELLS);
-    return 0;
-}
-// profile batches (ba_*_exact_paths): the profile sweep owns row 0, so a pair has |q| + 1 traced rows
-static int exact_trace_check_lengths_profile(const uint32_t* ql, const uint32_t* rl, size_t n, const uint32_t* name) {
-    if (exact_check_lengths_profile(ql, rl, n, name)) return 1;
-    for (size_t p = 0; p < n; p++)
-        if (((uint64_t)ql[p] + 1) * rl[p] > ba::EXACT_TRACE_MAX_CELLS)
-            return fail("exact: pair %zu (|q| = %u, profile length = %u) is too large for a traced matrix: (|q| + 1) * |r| may be %llu at most (BA_EXACT_TRACE_MAX_CELLS)",
+        if ((uint64_t)ql[p] + rl[p] > max_len2)
+            return fail(profile ? "exact: pair %zu (|q| = %u, profile length = %u) is too long for int32 scores: |q| + |r| may be %llu at most for a profile batch"
+                                : "exact: pair %zu (|q| = %u, |r| = %u) is too long for int32 scores: |q| + |r| may be %llu at most",
+                        name ? (size_t)name[p] : p, ql[p], rl[p], (unsigned long long)max_len2);
+    for (size_t p = 0; traced && p < n; p++)
+        if (((uint64_t)ql[p] + (profile ? 1 : 0)) * rl[p] > ba::EXACT_TRACE_MAX_CELLS)
+            return fail(profile ? "exact: pair %zu (|q| = %u, profile length = %u) is too large for a traced matrix: (|q| + 1) * |r| may be %llu at most (BA_EXACT_TRACE_MAX_CELLS)"
+                                : "exact: pair %zu (|q| = %u, |r| = %u) is too large for a traced matrix: |q| * |r| may be %llu at most (BA_EXACT_TRACE_MAX_CELLS)",
                         name ? (size_t)name[p] : p, ql[p], rl[p], (unsigned long long)ba::EXACT_TRACE_MAX_CELLS);
     return 0;
 }
@@ -1785,7 +1769,7 @@ static int exact_refusals(const BaBatch* b, uint32_t what, const void* out, bool
     return 0;
 }
 // form: scores only; the paths too (ba_batch_exact_cigars) -- the record's runs are left on the device in b->xt_runs at the offsets of
-// b->xt_off; or the paths in the batch's own mode (ba_batch_exact_paths), whatever the batch: the traced kernels of ba_exact_modes.hip, which
+// b->xt_off; or the paths in the batch's own mode (ba_batch_exact_paths), whatever the batch: the traced own-mode kernels of ba_exact.hip, which
 // also leave the start cells in b->xt_start
 enum { EXACT_FORM_SCORES = 0, EXACT_FORM_CIGARS = 1, EXACT_FORM_PATHS = 2 };
 static int batch_exact_device(BaBatch* b, uint32_t what, int32_t x_drop, const uint32_t* devpos, size_t m, BaExact* out, int form = EXACT_FORM_SCORES) {
@@ -1803,13 +1787,13 @@ static int batch_exact_device(BaBatch* b, uint32_t what, int32_t x_drop, const u
     std::vector<uint32_t> ql(b->n), rl(b->n);
     HIP_TRY(hipMemcpy(ql.data(), b->q_len.p, (size_t)b->n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(rl.data(), b->r_len.p, (size_t)b->n * 4, hipMemcpyDeviceToHost));
-    if ((profile ? exact_check_lengths_profile : exact_check_lengths)(ql.data(), rl.data(), b->n, b->h_order.empty() ? nullptr : b->h_order.data())) return 1;
+    if (exact_check_lengths(profile, false, ql.data(), rl.data(), b->n, b->h_order.empty() ? nullptr : b->h_order.data())) return 1;
     if (traced)   // (the requested pairs only: the others need no region)
         for (size_t k = 0; k < m; k++) {
             const uint32_t d = devpos[k];
             if (d == ba::EXACT_NO_PAIR) continue;
             const uint32_t* name = b->h_order.empty() ? &d : &b->h_order[d];
-            if (profile ? exact_trace_check_lengths_profile(&ql[d], &rl[d], 1, name) : exact_trace_check_lengths(&ql[d], &rl[d], 1, name)) return 1;
+            if (exact_check_lengths(profile, true, &ql[d], &rl[d], 1, name)) return 1;
         }
     // (the profile sweep shares this cost model: it also walks row 0, one row in |q| + 1, which neither the order nor the cuts notice)
     auto cost = [&](uint32_t k) { const uint32_t d = devpos[k]; return d == ba::EXACT_NO_PAIR ? 0ull : (uint64_t)ql[d] * rl[d]; };
@@ -2467,19 +2451,19 @@ int ba_batch_exact_paths_ms(BaBatch* b, float* ms, uint64_t* cells) {
 }
 int ba_exact_paths_check_lengths_profile(const uint32_t* q_len, const uint32_t* r_len, uintptr_t n) {
     if (n && (!q_len || !r_len)) return fail("null argument");
-    return exact_trace_check_lengths_profile(q_len, r_len, n, nullptr);
+    return exact_check_lengths(true, true, q_len, r_len, n, nullptr);
 }
 int ba_exact_trace_check_lengths(const uint32_t* q_len, const uint32_t* r_len, uintptr_t n) {
     if (n && (!q_len || !r_len)) return fail("null argument");
-    return exact_trace_check_lengths(q_len, r_len, n, nullptr);
+    return exact_check_lengths(false, true, q_len, r_len, n, nullptr);
 }
 int ba_exact_check_lengths_profile(const uint32_t* q_len, const uint32_t* r_len, uintptr_t n) {
     if (n && (!q_len || !r_len)) return fail("null argument");
-    return exact_check_lengths_profile(q_len, r_len, n, nullptr);
+    return exact_check_lengths(true, false, q_len, r_len, n, nullptr);
 }
 int ba_exact_check_lengths(const uint32_t* q_len, const uint32_t* r_len, uintptr_t n) {
     if (n && (!q_len || !r_len)) return fail("null argument");
-    return exact_check_lengths(q_len, r_len, n, nullptr);
+    return exact_check_lengths(false, false, q_len, r_len, n, nullptr);
 }
 int ba_accuracy_summary(const int32_t* score, const uint32_t* qidx, const uint32_t* ridx, const uint32_t* status, const BaExact* exact, uintptr_t n,
                         BaAccuracy* out) {

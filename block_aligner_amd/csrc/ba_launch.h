@@ -68,15 +68,15 @@ hipError_t ba_launch_extend_gather(hipStream_t s, const ba::ExtendParams* ep);
 // ba_stats.hip
 hipError_t ba_launch_stats(hipStream_t s, const ba::StatsParams* sp);
 hipError_t ba_launch_stats_extend(hipStream_t s, const ba::ExtendParams* ep, const ba::AlignStats* side, ba::AlignStats* out);
-// ba_exact.hip
+// ba_exact.hip, BA_EXACT_UNIT 0 (ba_launch_exact, ba_launch_exact_seed) and 1 (ba_launch_exact_trace, ba_launch_exact_runs)
 hipError_t ba_launch_exact(hipStream_t s, const ba::ExactParams* xp, uint32_t wgs);
 hipError_t ba_launch_exact_trace(hipStream_t s, const ba::ExactParams* xp, uint32_t waves);
 hipError_t ba_launch_exact_runs(hipStream_t s, const uint32_t* rev, const uint64_t* rev_off, const uint32_t* nrun, const uint64_t* off, uint32_t* runs,
                                 uint32_t m);
 hipError_t ba_launch_exact_seed(hipStream_t s, const ba::ExtendParams* ep, const uint32_t* which, uint32_t m, int32_t* out);
-// ba_exact_modes.hip
+// ba_exact.hip, BA_EXACT_UNIT 2 (ba_launch_exact_modes) and 3 (the other two)
 hipError_t ba_launch_exact_modes(hipStream_t s, const ba::ExactModeParams* mp, uint32_t wgs);
-hipError_t ba_launch_exact_modes_trace(hipStream_t s, const ba::ExactModeParams* mp, uint32_t* start_cell, uint32_t waves);   // (the BA_EXACT_TRACED unit)
+hipError_t ba_launch_exact_modes_trace(hipStream_t s, const ba::ExactModeParams* mp, uint32_t* start_cell, uint32_t waves);
 hipError_t ba_launch_exact_join(hipStream_t s, const ba::ExactJoinParams* jp);
 // ba_text.hip
 hipError_t ba_launch_text_len(hipStream_t s, const ba::TextParams* tp);

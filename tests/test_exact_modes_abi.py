@@ -65,4 +65,4 @@ def test_profile_length_guard_names_the_pair(hip):
 
 def test_kernel_hash_lists_the_new_sources():
     from tools import kernel_hash
-    assert "ba_exact_modes.hip" in kernel_hash.FILES and "ba_exact_dev.hpp" in kernel_hash.FILES
+    assert "ba_exact.hip" in kernel_hash.FILES and "ba_exact.h" in kernel_hash.FILES   # the one source of the own-mode kernels and its header

@@ -42,7 +42,7 @@ def step(name: str, n: int, runs: int) -> dict:
     b.close()
     fill_cells = int(res["cells"].sum())
     return dict(workload=w.name, pairs=len(p), block=list(w.size), x_drop=w.x_drop if mode else None, what="EXTEND" if mode else "GLOBAL",
-                exact_cells=cells, exact_ms=ms, exact_ms_min=float(min(times)), exact_gcups=cells / ms / 1e6,
+                exact_cells=cells, exact_ms=ms, exact_ms_min=float(min(times)), exact_ms_max=float(max(times)), exact_gcups=cells / ms / 1e6,
                 fill_kernel=info["kernel"], fill_ms=fill_ms, fill_cells=fill_cells, fill_gcups=fill_cells / fill_ms / 1e6,
                 fill_full_matrix_gcups=w.full_matrix_cells() / fill_ms / 1e6, accuracy=acc)
 
