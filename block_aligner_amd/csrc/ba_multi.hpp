@@ -152,6 +152,7 @@ __device__ __forceinline__ void apply_halves(int (&r)[4], int r3, int cs, int ge
 }
 
 typedef int lds_v4i __attribute__((ext_vector_type(4)));   // (16 bytes through a pointer into LDS: the HIP vector classes assign only through generic pointers)
+typedef int vec_v4i __attribute__((ext_vector_type(4)));   // (... and through a pointer into global memory)
 struct MultiOut { int mx, act_max8, pas_max8, corner_new; };
 
 // One 8-column shift step for the four slots of a wave, 8 cells per lane (scan_block.rs:147-246 with place_block 1083-1228 and
@@ -682,7 +683,10 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
 #define BA_R(k) (live ? mq_load(rec + 4 * (k)) : 0)
             const uint32_t pair = (uint32_t)BA_R(MR_PAIR), tslot = (uint32_t)BA_R(MR_TSLOT);
             uint32_t si = (uint32_t)BA_R(MR_SI), sj = (uint32_t)BA_R(MR_SJ), y_drop = (uint32_t)BA_R(MR_Y_DROP);
-            uint32_t trace_top = (uint32_t)BA_R(MR_TRACE_TOP), nblocks = (uint32_t)BA_R(MR_NBLOCKS), sel = (uint32_t)BA_R(MR_SEL);
+            uint32_t nblocks = (uint32_t)BA_R(MR_NBLOCKS), sel = (uint32_t)BA_R(MR_SEL);
+            // every plain step adds one record and MQ_TW words: the top of the trace stack is tt0 + nblocks * MQ_TW while the slot runs, and only
+            // nblocks is carried from step to step
+            const uint32_t tt_in = (uint32_t)BA_R(MR_TRACE_TOP), tt0 = tt_in - nblocks * MQ_TW;
             int dir = BA_R(MR_DIR), prev_dir = BA_R(MR_PREV_DIR), off = BA_R(MR_OFF), off_max = BA_R(MR_OFF_MAX), best_max = BA_R(MR_BEST_MAX);
             int x_iter = BA_R(MR_X_ITER), D_corner = BA_R(MR_D_CORNER);
 #undef BA_R
@@ -700,19 +704,26 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
             // (buffer `sel`) comes from the arena now and goes back after the loop; the other one is rewritten before every step. Both hold a
             // lane's cells in the registers' order.
             char* const lbuf = base + (uint32_t)g * (2u * BUFL);                 // this slot's buffers: + which * BUFL
-            constexpr uint32_t MQ_LSC_STATE = 9u, MQ_LSC_PAIR = 20u;   // ints: a buffer's scalars (see above: [0] .. [8]); where the eight constants of the slot's pair start
-            static_assert(2u * MQ_LSC_STATE <= MQ_LSC_PAIR && MQ_LSC_PAIR + 8u <= MQ_LSC_INTS && (4u * MQ_LSC_PAIR) % 16u == 0 && (4u * MQ_LSC_INTS) % 16u == 0, "a slot's scalars in LDS");
-            int* const lsc = (int*)(base + MQ_LDS_SCALARS) + (uint32_t)g * MQ_LSC_INTS;   // their scalars: + which * MQ_LSC_STATE; + MQ_LSC_PAIR: eight constants of the slot's pair
+            constexpr uint32_t MQ_LSC_STATE = 9u, MQ_LSC_PAIR = 20u;   // ints: a buffer's scalars (see above: [0] .. [8]); where the twelve constants of the slot's pair start
+            static_assert(2u * MQ_LSC_STATE <= MQ_LSC_PAIR && MQ_LSC_PAIR + 12u <= MQ_LSC_INTS && (4u * MQ_LSC_PAIR) % 16u == 0 && (4u * MQ_LSC_INTS) % 16u == 0, "a slot's scalars in LDS");
+            int* const lsc = (int*)(base + MQ_LDS_SCALARS) + (uint32_t)g * MQ_LSC_INTS;   // their scalars: + which * MQ_LSC_STATE; + MQ_LSC_PAIR: twelve constants of the slot's pair
             lds_sync();
             // (score-only kernels have the registers: there the values stay where they were -- 119.8 against 125.5 ms at config 3 without traceback)
             const unsigned long long qa_r = TRACE ? 0ull : (unsigned long long)(bp.pool + (live ? bp.q_off[pair] : 0ull)), ra_r = TRACE ? 0ull : (unsigned long long)(bp.pool + (live ? bp.r_off[pair] : 0ull));
             const uint32_t qlen_r = (!TRACE && live) ? bp.q_len[pair] : 0u, rlen_r = (!TRACE && live) ? bp.r_len[pair] : 0u;
             if (TRACE && l == 0) {
-                // what a step needs of its pair only at its start -- the two sequence images and their lengths, the trace slot -- is read from
-                // LDS in every step instead of living in seven registers through the columns
+                // what a step needs of its pair only at its start -- the two sequence images and their lengths, where the trace slot's words and
+                // records start, how many records the slot has room for -- is read from LDS in every step instead of living in registers through
+                // the columns (the two addresses were a 64-bit multiply each in every step: they change only with the pair)
                 const unsigned long long qa = (unsigned long long)(bp.pool + (live ? bp.q_off[pair] : 0ull)), ra = (unsigned long long)(bp.pool + (live ? bp.r_off[pair] : 0ull));
                 *(int4*)(lsc + MQ_LSC_PAIR) = int4{(int)(uint32_t)qa, (int)(uint32_t)(qa >> 32), (int)(uint32_t)ra, (int)(uint32_t)(ra >> 32)};
-                *(int4*)(lsc + MQ_LSC_PAIR + 4) = int4{live ? (int)bp.q_len[pair] : 0, live ? (int)bp.r_len[pair] : 0, (int)tslot, 0};
+                // (nblocks < bcap && top + MQ_TW + 64 <= tcap as one compare of nblocks: the first count that fails either)
+                const long long room = (long long)tcap - (long long)(MQ_TW + 64u) - (long long)tt_in;
+                const unsigned long long nb_room = room < 0 ? 0ull : (unsigned long long)nblocks + (unsigned long long)room / MQ_TW + 1ull;
+                const uint32_t nb_lim = (uint32_t)(nb_room < (unsigned long long)bcap ? nb_room : (unsigned long long)bcap);
+                *(int4*)(lsc + MQ_LSC_PAIR + 4) = int4{live ? (int)bp.q_len[pair] : 0, live ? (int)bp.r_len[pair] : 0, (int)nb_lim, 0};
+                const unsigned long long ta = (unsigned long long)(bp.trace_arena + (uint64_t)tslot * bp.trace_stride), ba = (unsigned long long)(bp.blocks + (uint64_t)tslot * bp.blocks_stride);
+                *(int4*)(lsc + MQ_LSC_PAIR + 8) = int4{(int)(uint32_t)ta, (int)(uint32_t)(ta >> 32), (int)(uint32_t)ba, (int)(uint32_t)(ba >> 32)};
             }
             if (live) {
                 const char* cb = slot_mem + sel * BUFA;
@@ -752,11 +763,12 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
                 const uint32_t l8 = (lid & (uint32_t)(SL - 1)) * 8u;
                 const uint32_t lbuf_s = base32 + (lid / (uint32_t)SL) * (2u * BUFL) + 2u * l8;
                 const uint32_t lsc_s = base32 + (uint32_t)MQ_LDS_SCALARS + (lid / (uint32_t)SL) * (4u * (uint32_t)MQ_LSC_INTS);
-                int4 cA = {0, 0, 0, 0}, cB = {0, 0, 0, 0};
+                int4 cA = {0, 0, 0, 0}, cB = {0, 0, 0, 0}, cC = {0, 0, 0, 0};
                 if (TRACE) {
                     typedef const __attribute__((address_space(3))) lds_v4i* lds_cint4_ptr;
-                    const lds_v4i a4 = *(lds_cint4_ptr)(uintptr_t)(lsc_s + 4u * MQ_LSC_PAIR), b4 = *(lds_cint4_ptr)(uintptr_t)(lsc_s + 4u * (MQ_LSC_PAIR + 4u));
-                    cA = int4{a4.x, a4.y, a4.z, a4.w}; cB = int4{b4.x, b4.y, b4.z, b4.w};
+                    const lds_v4i a4 = *(lds_cint4_ptr)(uintptr_t)(lsc_s + 4u * MQ_LSC_PAIR), b4 = *(lds_cint4_ptr)(uintptr_t)(lsc_s + 4u * (MQ_LSC_PAIR + 4u)),
+                                  c4 = *(lds_cint4_ptr)(uintptr_t)(lsc_s + 4u * (MQ_LSC_PAIR + 8u));
+                    cA = int4{a4.x, a4.y, a4.z, a4.w}; cB = int4{b4.x, b4.y, b4.z, b4.w}; cC = int4{c4.x, c4.y, c4.z, c4.w};
                 }
                 const uint8_t* const qp = TRACE ? (const uint8_t*)((unsigned long long)(uint32_t)cA.x | ((unsigned long long)(uint32_t)cA.y << 32)) : (const uint8_t*)qa_r;
                 const uint8_t* const rp = TRACE ? (const uint8_t*)((unsigned long long)(uint32_t)cA.z | ((unsigned long long)(uint32_t)cA.w << 32)) : (const uint8_t*)ra_r;
@@ -766,7 +778,8 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
                 const bool q_out = si + MB > qlen, r_out = sj + MB > rlen;
                 // a step that could break early at the matrix edge (never with X-drop) or that the trace slot has no room for is not a slot's
                 bool elig = XDROP || ri + MB <= lenV || rj + STEP <= lenC;
-                if (TRACE) elig = elig && nblocks < bcap && trace_top + MQ_TW + 64 <= tcap;
+                const uint32_t trace_top = tt0 + nblocks * MQ_TW;
+                if (TRACE) elig = elig && nblocks < (uint32_t)cB.z;   // (room for the step's record and trace words: the limit set when the slot took its pair)
                 leave = live && !elig;
                 const bool run = live && !leave;
                 const int off_n = off_max;
@@ -802,16 +815,18 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
                 }
                 uint32_t* tw = nullptr;
                 if (TRACE) {
-                    // (the slot's base address is derived again in every step -- two multiply-adds -- instead of living in a register pair across
-                    // the loop: with the pair the allocator spilled it and reloaded it before the stores, behind every outstanding memory operation)
-                    uint32_t ts = (uint32_t)cB.z; asm volatile("" : "+v"(ts));
-                    tw = bp.trace_arena + (uint64_t)ts * bp.trace_stride + (trace_top + l8);
+                    // (the slot's base address comes from LDS in every step instead of living in a register pair across the loop: with the pair
+                    // the allocator spilled it and reloaded it before the stores, behind every outstanding memory operation)
+                    // (as pointers to global memory: an address that comes out of LDS would otherwise be stored through as a flat one)
+                    typedef __attribute__((address_space(1))) uint32_t* glb_u32_ptr;
+                    tw = (uint32_t*)(glb_u32_ptr)((unsigned long long)(uint32_t)cC.x | ((unsigned long long)(uint32_t)cC.y << 32)) + (trace_top + l8);
                     if (run && l == 0) {   // add_block(i, j, width, height, right) in matrix orientation (scan_block.rs:154,204)
-                        BlockRec br;
-                        br.i = (right ? ri : rj) | 0x80000000u;   // (bit 31: words of 4 cells x 2 columns, see multi_rect)
-                        br.j = right ? rj : ri; br.h = (uint16_t)(right ? MB : STEP); br.w = (uint16_t)(right ? STEP : MB);
-                        br.trace_base = trace_top | (right ? 0x80000000u : 0u);
-                        bp.blocks[(uint64_t)(uint32_t)cB.z * bp.blocks_stride + nblocks] = br;
+                        // (the record's 16 bytes as one store; rows and columns are one select between two constants)
+                        static_assert(sizeof(BlockRec) == 16, "a record as four words");
+                        const uint32_t hw = right ? ((uint32_t)MB | ((uint32_t)STEP << 16)) : ((uint32_t)STEP | ((uint32_t)MB << 16));   // h = rows, w = columns
+                        typedef __attribute__((address_space(1))) vec_v4i* glb_rec_ptr;
+                        ((glb_rec_ptr)((unsigned long long)(uint32_t)cC.z | ((unsigned long long)(uint32_t)cC.w << 32)))[nblocks] =
+                            vec_v4i{(int)((right ? ri : rj) | 0x80000000u) /* bit 31: words of 4 cells x 2 columns, see multi_rect */, (int)(right ? rj : ri), (int)hw, (int)(trace_top | (right ? 0x80000000u : 0u))};
                     }
                 }
                 MultiOut o;
@@ -838,7 +853,7 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
                     best_max = imp ? new_off_max : best_max;
                     off = commit ? off_n : off; off_max = commit ? new_off_max : off_max; y_drop = commit ? new_y : y_drop;
                     prev_dir = commit ? dir : prev_dir; D_corner = commit ? o.corner_new : D_corner;
-                    if (TRACE) { trace_top += commit ? MQ_TW : 0u; nblocks += commit ? 1u : 0u; }
+                    if (TRACE) nblocks += commit ? 1u : 0u;
                     if (XDROP) x_iter = commit ? ((new_off_max < best_max - x_drop) ? x_iter + 1 : 0) : x_iter;
                     const bool go_down = r_out || (!q_out && down_max > right_max);   // forced at the matrix edge, else greedy (ties -> right)
                     si += (commit && go_down) ? (uint32_t)STEP : 0u; sj += (commit && !go_down) ? (uint32_t)STEP : 0u;
@@ -860,6 +875,7 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
             } while (!__any(leave));
             // ---- every slot's state at the top of the loop to memory: the registers of the slots that took the step (the others'
             // was staged before it)
+            const uint32_t trace_top = tt0 + nblocks * MQ_TW;
             if (live && !leave) stage((uint32_t)(uintptr_t)(lbuf + l * 16), (uint32_t)(uintptr_t)lsc, sel ^ 1u, si, sj, 0, trace_top, nblocks, dir, 0, 0);
             lds_sync();
             if (live) {   // both buffers back to the arena (solo mode needs the LDS region, and reads a pair's state from the arena)

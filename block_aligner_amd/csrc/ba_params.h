@@ -125,7 +125,7 @@ constexpr uint32_t MQ_B_HOST = 128;   // k_multi: block size of a slot (ba_drive
 constexpr uint32_t MQ_BUF_BYTES = 4 * 256 + 64, MQ_SLOT_BYTES = 2 * MQ_BUF_BYTES + 128, MQ_WAVE_BYTES = 4 * MQ_SLOT_BYTES;
 // k_multi: while the slots run, the same buffers live in the wave's LDS region (the solo borders' space, which the slots do not need):
 // 4 slots x 2 buffers x 1 KB of borders, then 8 x 9 scalars
-constexpr uint32_t MQ_LDS_SCALARS = 8192, MQ_LSC_INTS = 28, MQ_LDS_BYTES = 8192 + 4 * MQ_LSC_INTS * 4;   // per slot: 2 x 9 scalars, 2 free, 8 constants of the slot's pair (sequence addresses and lengths, trace slot)
+constexpr uint32_t MQ_LDS_SCALARS = 8192, MQ_LSC_INTS = 32, MQ_LDS_BYTES = 8192 + 4 * MQ_LSC_INTS * 4;   // per slot: 2 x 9 scalars, 2 free, 12 constants of the slot's pair (sequence addresses and lengths, the record limit, where the trace slot's words and records start)
 // k_small (ba_small.hpp): sixteen pairs per wave while the block is 32 cells -- slots of 4 lanes x 8 cells. Per wave and slot in the `big`
 // arena: two state buffers (4 border arrays x 4 lanes x 16 bytes + 8 scalars) and a 128-byte record; while the slots run the buffers live in
 // the wave's LDS region (16 slots x 2 buffers x 256 bytes of borders, then 16 x 2 x 8 scalars)
