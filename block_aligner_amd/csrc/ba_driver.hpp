@@ -103,8 +103,18 @@ __device__ __forceinline__ uint32_t tb_next(bool right_blk, uint32_t next, uint3
     return (next == TB_PENDING && v == 0) ? (right_blk ? 2u : 1u) : next;
 }
 
+// Trace words of a slot's rectangle (bit 31 of BlockRec::i: ba_small.hpp small_rect, ba_multi.hpp multi_rect): a lane's 8 cells x 2 columns are
+// the 8 bytes of words (column >> 1) * 2 and (column >> 1) * 2 + 1 of the lane's eight; this is the byte of cell c = 0 .. 7 among them.
+//   RO = false, the cell order (k_small): byte c -- word c >> 2 holds cells 0 .. 3 or 4 .. 7.
+//   RO = true, the order of k_multi's registers (round 9): word p2 holds cells (2 p2, 2 p2 + 1, 2 p2 + 4, 2 p2 + 5) in bytes 0 .. 3, so for
+//   c = (b2 b1 b0) the byte is b1 * 4 + b2 * 2 + b0: 0 1 4 5 2 3 6 7 for c = 0 .. 7.
+// The order belongs to the kernel that wrote the batch, not to the record: every walker takes it as a compile-time parameter (RO).
+template <bool RO>
+__host__ __device__ constexpr uint32_t slot_cell_byte(uint32_t c) { return RO ? (((c & 2u) << 1) | ((c & 4u) >> 1) | (c & 1u)) : c; }
+
 // Walk back from (i, j); emit run-length ops right-aligned into [out_lo, out_hi). Returns run count, or
 // sets *status on failure. Executed by lane 0 only. (scan_block.rs:1482-1672)
+template <bool RO = false>
 __device__ __forceinline__ uint32_t traceback(const BlockRec* __restrict__ blocks, uint32_t nblocks, const uint32_t* __restrict__ trace,
                                      uint32_t i, uint32_t j, const uint8_t* __restrict__ q, const uint8_t* __restrict__ r, uint32_t flags,
                                      uint32_t* __restrict__ out, uint64_t out_lo, uint64_t out_hi, uint32_t* status) {
@@ -136,8 +146,9 @@ __device__ __forceinline__ uint32_t traceback(const BlockRec* __restrict__ block
             if (right_blk && fqs && i == 0) { stop = true; break; }                     // scan_block.rs:1597-1599
             uint32_t nib;
             if (l2) {
-                const uint32_t word = trace[tbase + (v >> 3) * 8 + (w >> 1) * 2 + ((v >> 2) & 1)];
-                nib = ((word >> ((v & 3) * 8 + (w & 1) * 4)) ^ 15u) & 15u;
+                const uint32_t cb = slot_cell_byte<RO>(v & 7u);
+                const uint32_t word = trace[tbase + (v >> 3) * 8 + (w >> 1) * 2 + (cb >> 2)];
+                nib = ((word >> ((cb & 3) * 8 + (w & 1) * 4)) ^ 15u) & 15u;
             } else {
                 // (LOCAL_START batches: a trace word is followed by its cells' zero-mask word, place_rect)
                 const uint32_t word = trace[tbase + (((w >> 2) * nch + chunk) * nl + lane) * (local ? 2u : 1u)];
@@ -194,7 +205,7 @@ __device__ __forceinline__ uint32_t wave_excl_sum(uint32_t x, uint32_t lane) {
     }
     return s - x;
 }
-template <bool L2OK>
+template <bool L2OK, bool RO = false>
 __device__ __forceinline__ uint32_t walk_wave(const BlockRec* __restrict__ blocks, uint32_t nblocks_in, const uint32_t* __restrict__ trace,
                                               uint32_t i_in, uint32_t j_in, const uint8_t* __restrict__ q, const uint8_t* __restrict__ r, bool eq,
                                               uint32_t* __restrict__ out, uint64_t out_lo, uint64_t out_hi, uint32_t* status,
@@ -274,7 +285,7 @@ __device__ __forceinline__ uint32_t walk_wave(const BlockRec* __restrict__ block
                 const uint32_t ci = i - bi, cj = j - bj;
                 const uint32_t v = right ? ci : cj, w = right ? cj : ci;
                 uint32_t widx, sh;
-                if (l2) { widx = (v >> 3) * 8u + (w >> 1) * 2u + ((v >> 2) & 1u); sh = (v & 3u) * 8u + (w & 1u) * 4u; }
+                if (l2) { const uint32_t cb = slot_cell_byte<RO>(v & 7u); widx = (v >> 3) * 8u + (w >> 1) * 2u + (cb >> 2); sh = (cb & 3u) * 8u + (w & 1u) * 4u; }
                 else { widx = ((w >> 2) * nch + (v >> 7)) * nl + ((v & 127u) >> 1); sh = (v & 1u) * 16u + (w & 3u) * 4u; }
                 uint32_t word;
                 // ---- round 5: a run of diagonal moves at once. In state D a cell whose C and R flags both say "differs" is a match / mismatch and
@@ -287,7 +298,7 @@ __device__ __forceinline__ uint32_t walk_wave(const BlockRec* __restrict__ block
                     const bool valid = lane <= lim;
                     const uint32_t vv = v - lane, ww = w - lane;
                     uint32_t widx_k, sh_k;
-                    if (l2) { widx_k = (vv >> 3) * 8u + (ww >> 1) * 2u + ((vv >> 2) & 1u); sh_k = (vv & 3u) * 8u + (ww & 1u) * 4u; }
+                    if (l2) { const uint32_t cb = slot_cell_byte<RO>(vv & 7u); widx_k = (vv >> 3) * 8u + (ww >> 1) * 2u + (cb >> 2); sh_k = (cb & 3u) * 8u + (ww & 1u) * 4u; }
                     else { widx_k = ((ww >> 2) * nch + (vv >> 7)) * nl + ((vv & 127u) >> 1); sh_k = (vv & 1u) * 16u + (ww & 3u) * 4u; }
                     uint32_t word_k = 0;
                     if (valid) { if constexpr (DIRECT) word_k = trace[off + widx_k]; else word_k = lds[off + widx_k]; }
@@ -413,7 +424,8 @@ constexpr int TB_CELLS_PER_STEP = 4;
 // call -- one memory round trip of its wave -- on each.
 // LB: bytes of a lane's LDS record. TB_LANE_BYTES: 10 trace words + the two sequence windows. TB_LANE_BYTES_L2 (k_multi): 16 trace words, so
 // that a window also holds the words of a slot's rectangles (4 cells x 2 columns each: two 8-cell lanes x two column groups = 64 bytes).
-template <int CELLS = TB_CELLS_PER_STEP, int DEPTH = 1, int LB = (int)TB_LANE_BYTES>
+// RO: the byte order of a slot rectangle's trace words (slot_cell_byte)
+template <int CELLS = TB_CELLS_PER_STEP, int DEPTH = 1, int LB = (int)TB_LANE_BYTES, bool RO = false>
 __device__ __forceinline__ void tb_step(TbLane& t, uint32_t flags, uint32_t* __restrict__ out, unsigned char* lrec,
                                         const unsigned char* lut, unsigned long long* tacc = nullptr) {
     constexpr bool LOCREC = LB == (int)TB_LANE_BYTES_LOC;   // records with room for the zero-mask bits: the only ones LOCAL_START walks use
@@ -559,7 +571,7 @@ __device__ __forceinline__ void tb_step(TbLane& t, uint32_t flags, uint32_t* __r
             if (L2OK && t.l2) {
                 const uint32_t k8 = (v >> 3) - t.tw_lane0;
                 alive = alive && t.tw_chunk == 0xffffu && k8 <= 1u;
-                baddr = k8 * 32 + (w >> 1) * 8 + ((v >> 2) & 1) * 4 + (v & 3);
+                baddr = k8 * 32 + (w >> 1) * 8 + slot_cell_byte<RO>(v & 7u);
                 zaddr = 64 + k8 * 8 + ((v >> 2) & 1) * 4 + (v & 3); zbit = w;
             } else {
                 const uint32_t k = lc - t.tw_lane0;
@@ -649,11 +661,13 @@ __device__ __forceinline__ void tb_prefetch2(TbLane& t) {
     t.nq = min(2u, t.bidx);
 }
 // Tables of tb_diag behind the lanes' records (8-byte aligned): per (position, k) the byte offset of the cell k steps up the diagonal.
-//   slot rectangles (records of TB_LANE_BYTES_L2: a window of 16 rows x 8 columns, byte = (row >> 3) * 32 + (column >> 1) * 8 + (row & 7)):
-//     F[u][k], u = row in the window (16 x 8 bytes), then G[w][k], w = column (8 x 8 bytes)
+//   slot rectangles (records of TB_LANE_BYTES_L2: a window of 16 rows x 8 columns, byte = (row >> 3) * 32 + (column >> 1) * 8 +
+//   slot_cell_byte<RO>(row & 7) -- RO: the words' byte order, k_small's cell order or the order of k_multi's registers):
+//     F[u][k] = (x >> 3) * 32 + slot_cell_byte<RO>(x & 7) with x = (u - k) & 15, u = row in the window (16 x 8 bytes), then
+//     G[w][k] = (((w - k) & 7) >> 1) * 8, w = column (8 x 8 bytes)
 //   per-pair rectangles (records of TB_LANE_BYTES: 5 lanes x 2 column groups, byte = (newer group ? 0 : 20) + row * 2 + ((column & 3) >> 1)):
 //     C[x][k], x = column in the window's 8 columns (8 x 8 bytes); the row term is arithmetic
-template <bool L2W>
+template <bool L2W, bool RO = false>
 __device__ __forceinline__ void tb_diag_lut_fill(unsigned char* dlut) {
     if constexpr (L2W) {
 #pragma unroll
@@ -661,7 +675,7 @@ __device__ __forceinline__ void tb_diag_lut_fill(unsigned char* dlut) {
             const uint32_t idx = (uint32_t)lane_id() + 64u * e;   // 0 .. 191
             const uint32_t k = idx & 7u, p = idx >> 3;              // p < 16: F, else G
             const uint32_t x = (p - k) & 15u, c = ((p - 16u) - k) & 7u;
-            dlut[idx] = (unsigned char)(p < 16u ? (((x & 8u) << 2) | (x & 7u)) : ((c >> 1) << 3));
+            dlut[idx] = (unsigned char)(p < 16u ? (((x & 8u) << 2) | slot_cell_byte<RO>(x & 7u)) : ((c >> 1) << 3));
         }
     }
     {   // C: alone (records of TB_LANE_BYTES) or behind F and G (a kernel of slot rectangles also walks the rectangles its solo driver wrote)
@@ -759,7 +773,7 @@ __device__ __forceinline__ void tb_diag(TbLane& t, const bool eq, const unsigned
 
 // One call of a lane's walk (CIGAR_EQ is the only mode bit: LOCAL_START / FREE_QUERY_START_GAPS walks keep tb_step). LB: TB_LANE_BYTES
 // (per-pair rectangles only) or TB_LANE_BYTES_L2 (slot rectangles too; tb_diag then takes only those).
-template <int DEPTH, int LB>
+template <int DEPTH, int LB, bool RO = false>
 __device__ __forceinline__ void tb_step_fast(TbLane& t, const bool eq, uint32_t* __restrict__ out, unsigned char* lrec, const unsigned char* lut, const unsigned char* dlut) {
     static_assert(DEPTH >= 2 && DEPTH <= 4 && (BA_TB_FCELLS) >= 1 && (BA_TB_FCELLS) <= 2, "");
     constexpr bool L2OK = LB == (int)TB_LANE_BYTES_L2;
@@ -866,7 +880,7 @@ __device__ __forceinline__ void tb_step_fast(TbLane& t, const bool eq, uint32_t*
             if (L2OK && t.l2) {
                 const uint32_t k8 = (v >> 3) - t.tw_lane0;
                 alive = alive && t.tw_chunk == 0xffffu && k8 <= 1u;
-                baddr = k8 * 32 + (w >> 1) * 8 + ((v >> 2) & 1) * 4 + (v & 3);
+                baddr = k8 * 32 + (w >> 1) * 8 + slot_cell_byte<RO>(v & 7u);
             } else {
                 const uint32_t k = lc - t.tw_lane0;
                 alive = alive && (v >> 7) == t.tw_chunk && gi <= 1u && k <= 4u;             // else: left the window, the next call reloads it
@@ -902,7 +916,7 @@ __device__ __forceinline__ void tb_step_fast(TbLane& t, const bool eq, uint32_t*
 // dependent iterations whose length grows with the number of lanes walking in lockstep, so the last `tb_reserve`
 // hand-offs are left to these late helpers, one lane per wave on a SIMD that has nothing else left to do (the
 // dedicated waves stop claiming tickets once the ticket counter reaches that reserve).
-template <int LB = (int)TB_LANE_BYTES, int CELLS = TB_CELLS_PER_STEP, int DEPTH = BA_RING_DEPTH>
+template <int LB = (int)TB_LANE_BYTES, int CELLS = TB_CELLS_PER_STEP, int DEPTH = BA_RING_DEPTH, bool RO = false>
 __device__ __forceinline__ void traceback_consumer(const BatchParams& bp, uint32_t flag_mask, unsigned char* tb_lds, uint32_t nlanes, bool dedicated, int prio = -1) {
     enum { IDLE = 0, WAIT = 1, WALK = 2, RETIRED = 3 };
     int phase = (uint32_t)lane_id() < nlanes ? IDLE : RETIRED;
@@ -923,7 +937,7 @@ __device__ __forceinline__ void traceback_consumer(const BatchParams& bp, uint32
         const Move mv = tb_lut(idx >> 6, idx & 3, (idx >> 2) & 1, (idx >> 4) & 3);   // (bit 3 of the cell's nibble is resolved before the lookup)
         lut[idx] = (unsigned char)(mv.op | (mv.di << 3) | (mv.dj << 4) | (mv.next << 5));
     }
-    if constexpr (FASTP) tb_diag_lut_fill<LB == (int)TB_LANE_BYTES_L2>(dlut);
+    if constexpr (FASTP) tb_diag_lut_fill<LB == (int)TB_LANE_BYTES_L2, RO>(dlut);
     lds_sync();
     // A walk is a long dependent chain of short instructions sharing its SIMD with VALU-saturating fill waves; without
     // priority it gets a quarter of the issue slots and every pending walk pins a whole trace slot meanwhile.
@@ -986,18 +1000,18 @@ __device__ __forceinline__ void traceback_consumer(const BatchParams& bp, uint32
 #ifdef BA_TIMING
             const unsigned long long tq0 = __builtin_amdgcn_s_memtime();
             if (t.i > 0 || t.j > 0) {
-                if constexpr (FASTP) tb_step_fast<BA_TB_FDEPTH, LB>(t, eq != 0u, bp.cig_ops, lrec, lut, dlut);
-                else tb_step<CELLS, DEPTH, LB>(t, eq, bp.cig_ops, lrec, lut, c_sec);
+                if constexpr (FASTP) tb_step_fast<BA_TB_FDEPTH, LB, RO>(t, eq != 0u, bp.cig_ops, lrec, lut, dlut);
+                else tb_step<CELLS, DEPTH, LB, RO>(t, eq, bp.cig_ops, lrec, lut, c_sec);
             }
             c_sec[2] += __builtin_amdgcn_s_memtime() - tq0;
 #else
             // (an emptied fill wave's few lanes -- the batch's last walks, each a chain of memory round trips that ends the launch --
             // take more cells per call and look further ahead; dedicated waves share their SIMD with fill waves: see tb_step)
             if (t.i > 0 || t.j > 0) {
-                if constexpr (FASTP) tb_step_fast<BA_TB_FDEPTH, LB>(t, eq != 0u, bp.cig_ops, lrec, lut, dlut);
+                if constexpr (FASTP) tb_step_fast<BA_TB_FDEPTH, LB, RO>(t, eq != 0u, bp.cig_ops, lrec, lut, dlut);
                 else
-                if (BA_HELPER_CELLS != CELLS && !dedicated) tb_step<BA_HELPER_CELLS, BA_WALK_DEPTH, LB>(t, eq, bp.cig_ops, lrec, lut);
-                else tb_step<CELLS, DEPTH, LB>(t, eq, bp.cig_ops, lrec, lut);
+                if (BA_HELPER_CELLS != CELLS && !dedicated) tb_step<BA_HELPER_CELLS, BA_WALK_DEPTH, LB, RO>(t, eq, bp.cig_ops, lrec, lut);
+                else tb_step<CELLS, DEPTH, LB, RO>(t, eq, bp.cig_ops, lrec, lut);
             }
 #endif
             if (!(t.i > 0 || t.j > 0)) {
@@ -1030,7 +1044,7 @@ __device__ __forceinline__ void traceback_consumer(const BatchParams& bp, uint32
 // that is only partly resident) walks a pending traceback itself instead of giving up: it takes the ring's head entry -- only if the
 // entry is there: compare-and-swap on the head counter after seeing it, so nothing is ever claimed that might not come -- and walks it
 // with lane 0 out of its own LDS region. Returns true if a walk was done (one of this wave's slots may be free now).
-template <int LB = (int)TB_LANE_BYTES>
+template <int LB = (int)TB_LANE_BYTES, bool RO = false>
 __device__ __forceinline__ bool traceback_help_one(const BatchParams& bp, uint32_t flag_mask, unsigned char* tb_lds) {
     uint32_t entry = 0;
     if (is_lane(0)) {
@@ -1073,7 +1087,7 @@ __device__ __forceinline__ bool traceback_help_one(const BatchParams& bp, uint32
         t.lo = bp.cig_off[t.pair]; t.wp = bp.cig_off[t.pair + 1];
         t.status = bp.status[t.pair];
         if (t.status || (bp.flags & 0x200u)) t.i = t.j = 0;
-        while (t.i > 0 || t.j > 0) tb_step<TB_CELLS_PER_STEP, BA_RING_DEPTH, LB>(t, eq, bp.cig_ops, lrec, lut);
+        while (t.i > 0 || t.j > 0) tb_step<TB_CELLS_PER_STEP, BA_RING_DEPTH, LB, RO>(t, eq, bp.cig_ops, lrec, lut);
         tb_emit(t, bp.cig_ops);
         bp.cig_len[t.pair] = t.status ? 0u : (uint32_t)(bp.cig_off[t.pair + 1] - t.wp);
         if (t.status) bp.status[t.pair] = t.status;
@@ -1085,7 +1099,7 @@ __device__ __forceinline__ bool traceback_help_one(const BatchParams& bp, uint32
 
 // An emptied fill wave at the end of a batch: it serves hand-offs like a traceback lane (a ticket, then the entry), but with all of
 // its lanes on one path at a time (walk_wave) -- the batch ends one walk after its last fill, and this walk is the short one.
-template <bool L2OK>
+template <bool L2OK, bool RO = false>
 __device__ __forceinline__ void traceback_helper_wave(const BatchParams& bp, uint32_t* lds, uint32_t budget) {
     uint32_t* head = bp.tb_ctrl + 32;
     for (;;) {
@@ -1109,7 +1123,7 @@ __device__ __forceinline__ void traceback_helper_wave(const BatchParams& bp, uin
         uint32_t st = bp.status[pair], ncig = 0;
         lds_sync();
         if (!st && !(bp.flags & 0x200u))
-            ncig = walk_wave<L2OK>(bp.blocks + (uint64_t)slot * bp.blocks_stride, si.nblocks, bp.trace_arena + (uint64_t)slot * bp.trace_stride, si.end_i, si.end_j,
+            ncig = walk_wave<L2OK, RO>(bp.blocks + (uint64_t)slot * bp.blocks_stride, si.nblocks, bp.trace_arena + (uint64_t)slot * bp.trace_stride, si.end_i, si.end_j,
                                    bp.pool + bp.q_off[pair], bp.pool + bp.r_off[pair], (bp.flags & F_CIGAR_EQ) != 0, bp.cig_ops, bp.cig_off[pair], bp.cig_off[pair + 1],
                                    &st, lds, budget);
         lds_sync();
@@ -1263,6 +1277,7 @@ struct NoState { int exited; };
 template <int PMAX, int KIND, bool TRACE, bool XDROP, bool SPECIAL, bool MULTI = false, int SLOT_B_ = 128>
 struct Aligner {
     static constexpr uint32_t SLOT_B = (uint32_t)SLOT_B_;
+    static constexpr bool SLOT_RO = MULTI && SLOT_B_ >= 128;   // the slot rectangles on this driver's stacks are k_multi's (words in its registers' order: slot_cell_byte), not k_small's
     typedef std::conditional_t<MULTI, PairState, NoState> RunOut;
     // The batch descriptor lives in device memory. Only the scalars the step loop needs are copied into registers;
     // everything else (a couple of dozen per-pair output pointers) is re-read where it is used, once per pair, so it
@@ -2074,14 +2089,14 @@ struct Aligner {
             if constexpr (SPECIAL) {
                 if (is_lane(0)) {
                     uint32_t st = 0;
-                    ncig = traceback(blocks, nblocks, trace, ri, rj, q, r, h_flags, coldp()->cig_ops, coldp()->cig_off[pair], coldp()->cig_off[pair + 1], &st);
+                    ncig = traceback<SLOT_RO>(blocks, nblocks, trace, ri, rj, q, r, h_flags, coldp()->cig_ops, coldp()->cig_off[pair], coldp()->cig_off[pair + 1], &st);
                     status |= st;
                 }
             } else {
                 // the whole wave on this one path, out of the border arrays' LDS space (the pair is finished: nothing in it is live)
                 uint32_t st = 0;
                 lds_sync();
-                ncig = walk_wave<MULTI>(blocks, nblocks, trace, ri, rj, q, r, (h_flags & F_CIGAR_EQ) != 0, coldp()->cig_ops, coldp()->cig_off[pair],
+                ncig = walk_wave<MULTI, SLOT_RO>(blocks, nblocks, trace, ri, rj, q, r, (h_flags & F_CIGAR_EQ) != 0, coldp()->cig_ops, coldp()->cig_off[pair],
                                         coldp()->cig_off[pair + 1], &st, (uint32_t*)L.D_col, lds_array_bytes_h(kBig ? 128u : (uint32_t)PMAX * 128u));
                 lds_sync();
                 status |= st;

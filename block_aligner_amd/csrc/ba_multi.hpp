@@ -74,7 +74,7 @@ template <int SL> __device__ __forceinline__ int slot_shl1_keep(int last, int sr
 // in-lane gap scan is ONE packed chain of three links that scans cells 0 .. 3 and 4 .. 7 side by side, joined by a single carry across the halves
 // (scan_halves / apply_halves: 20 instructions per column where the chain over consecutive pairs took 32). Only the registers of the loop of steps
 // and its two LDS buffers are in this order: the arena, the trace words and everything the per-pair driver and the traceback read keep the cells
-// consecutive (cells_split / cells_join at the loop's edges; the trace bytes are put in order once per two columns).
+// consecutive (cells_split / cells_join at the loop's edges; round 9: the slots' trace words keep the registers' order too, see multi_rect).
 __device__ __forceinline__ void cells_split(int (&v)[4]) {   // (c0 c1)(c2 c3)(c4 c5)(c6 c7) -> (c0 c4)(c1 c5)(c2 c6)(c3 c7)
     const int a = v[0], b = v[1], c = v[2], d = v[3];
     v[0] = __builtin_amdgcn_perm(c, a, 0x05040100); v[1] = __builtin_amdgcn_perm(c, a, 0x07060302);
@@ -157,7 +157,8 @@ struct MultiOut { int mx, act_max8, pas_max8, corner_new; };
 
 // One 8-column shift step for the four slots of a wave, 8 cells per lane (scan_block.rs:147-246 with place_block 1083-1228 and
 // the border moves 1003-1061 folded in). (Ad, Ac): the border pair along the step's vector axis, (Pd, Pr) the orthogonal pair.
-// tout: this lane's eight trace words of the step.
+// tout: this lane's eight trace words of the step: word (column >> 1) * 2 + p2 holds cells (2 p2, 2 p2 + 1, 2 p2 + 4, 2 p2 + 5) x 2 columns, the registers'
+// order (round 9) -- cell c is byte slot_cell_byte<true>(c) of its column pair's eight (ba_driver.hpp), which every walker of this kernel uses.
 // SPM (round 5): the special alignment modes a slot takes, as in small_rect (ba_small.hpp) -- 1 = LOCAL_START (every cell's D is at least the relative
 // zero rz2; TRACE: a zero mask of one bit per cell, two words per lane -- cells 0 .. 3 / 4 .. 7, byte = cell, bit = column --, stored by the caller behind
 // the rectangle's 128 trace words), 2 = FREE_QUERY_START_GAPS (fqs_row0: row 0 of a right step starts from the relative zero in every column).
@@ -238,11 +239,14 @@ __device__ __forceinline__ void multi_rect(const char* table, const FillConsts& 
             }
         }
         if (TRACE) {
-            // Trace words of a slot's rectangle: 4 consecutive cells x 2 columns, a byte per cell, the even
-            // column in its low nibble; a lane's eight words -- its 8 cells x the step's 8 columns -- are contiguous in memory (word
-            // lane * 8 + (column >> 1) * 2 + (cell >> 2)), so that the traceback finds everything around a path cell in one cache line.
-            // A pair of registers holds cells 2 p2, 2 p2 + 1 and the two four further down: its bytes are gathered as (2 p2, 2 p2 + 1, 2 p2 + 4,
-            // 2 p2 + 5), and once two columns are complete two v_perm exchange the middle halves of the two words.
+            // Trace words of a slot's rectangle: 4 cells x 2 columns, a byte per cell, the even column in its low nibble; a lane's eight
+            // words -- its 8 cells x the step's 8 columns -- are contiguous in memory (word lane * 8 + (column >> 1) * 2 + p2), so that the
+            // traceback finds everything around a path cell in one cache line.
+            // Round 9: the words stay in the registers' order. A pair of registers holds cells 2 p2, 2 p2 + 1 and the two four further down, and
+            // word p2 of a column pair holds exactly those, (2 p2, 2 p2 + 1, 2 p2 + 4, 2 p2 + 5) in bytes 0 .. 3: cell c of the lane's eight is
+            // byte slot_cell_byte<true>(c) = (c & 2) * 2 + (c & 4) / 2 + (c & 1) of the column pair's 8 bytes (ba_driver.hpp; until round 9 two
+            // v_perm per column pair put the bytes in cell order here -- 2.6 M cells filled per pair against ~11 k walked). Only the walkers
+            // of this kernel read them (SLOT_RO); k_small's small_rect keeps the cell order under the same record bit.
             // The sign bytes of two registers' differences are gathered by one v_perm each, so that the three bit-field inserts that build a
             // nibble {nRo, nCo, nR, nC} (see fast_rect) serve four cells instead of two.
 #pragma unroll
@@ -255,10 +259,6 @@ __device__ __forceinline__ void multi_rect(const char* table, const FillConsts& 
                 const uint32_t nib = bfi(0x33333333u, lo2, hi2);
                 if (j & 1) tacc[2 * (j >> 1) + p2] = (int)bfi(0xF0F0F0F0u, nib, (uint32_t)tacc[2 * (j >> 1) + p2]);
                 else tacc[2 * (j >> 1) + p2] = (int)nib;   // (the high nibbles are the odd column's, written next)
-            }
-            if (j & 1) {
-                const int wa = tacc[j - 1], wb = tacc[j];
-                tacc[j - 1] = __builtin_amdgcn_perm(wb, wa, 0x05040100); tacc[j] = __builtin_amdgcn_perm(wb, wa, 0x07060302);
             }
         }
         // the last cell of the column feeds the orthogonal border (scan_block.rs:1213-1214): two columns to a register
@@ -367,7 +367,7 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
 #endif
     if (batch_traceback && wave == 0 && blockIdx.x % stride == 0) {
         if (!(bp.flags & 0x800u))   // (development switch: as if the traceback waves were never resident)
-        traceback_consumer<TB_LB, 8, 3>(bp, TB_MASK, (unsigned char*)base, 64u, true, 1);   // (8 cells per call: the window of a slot's rectangle is 16 rows x 8 columns; 4: -0.8 %, 12: -2 %. Three records fetched ahead: +0.8 % over two)   // (records in this wave's own region)
+        traceback_consumer<TB_LB, 8, 3, true>(bp, TB_MASK, (unsigned char*)base, 64u, true, 1);   // (8 cells per call: the window of a slot's rectangle is 16 rows x 8 columns; 4: -0.8 %, 12: -2 %. Three records fetched ahead: +0.8 % over two)   // (records in this wave's own region)
 #if defined(BA_TIMING) || defined(BA_ENDHIST)
         if (bp.prof && is_lane(0)) atomicMax(bp.prof + 42, (unsigned long long)__builtin_amdgcn_s_memrealtime());
 #endif
@@ -558,7 +558,7 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
                         if (head != seen) { seen = head; idle_n = 0; }
                         // nobody has taken a traceback for a few milliseconds: walk one here (see traceback_help_one; the wave's LDS region
                         // is free: the slots' buffers are in the arena while the wave is in solo mode)
-                        else if ((++idle_n & 2047u) == 0 && traceback_help_one<TB_LB>(bp, TB_MASK, (unsigned char*)base)) idle_n = 0;
+                        else if ((++idle_n & 2047u) == 0 && traceback_help_one<TB_LB, true>(bp, TB_MASK, (unsigned char*)base)) idle_n = 0;
                         __builtin_amdgcn_s_sleep(64);
                     }
 #ifdef BA_TIMING
@@ -715,8 +715,10 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
                 // what a step needs of its pair only at its start -- the two sequence images and their lengths, where the trace slot's words and
                 // records start, how many records the slot has room for -- is read from LDS in every step instead of living in registers through
                 // the columns (the two addresses were a 64-bit multiply each in every step: they change only with the pair)
-                const unsigned long long qa = (unsigned long long)(bp.pool + (live ? bp.q_off[pair] : 0ull)), ra = (unsigned long long)(bp.pool + (live ? bp.r_off[pair] : 0ull));
-                *(int4*)(lsc + MQ_LSC_PAIR) = int4{(int)(uint32_t)qa, (int)(uint32_t)(qa >> 32), (int)(uint32_t)ra, (int)(uint32_t)(ra >> 32)};
+                // (round 9: the images' OFFSETS from bp.pool, words 0 and 2. The step's prefetch adds them to the pool's base as 32-bit values, see there;
+                // words 1 and 3, the offsets' high halves, are read only where a slot has no prefetched bytes -- and are zero unless F_POOL64 is set)
+                const unsigned long long qo = live ? bp.q_off[pair] : 0ull, ro = live ? bp.r_off[pair] : 0ull;
+                *(int4*)(lsc + MQ_LSC_PAIR) = int4{(int)(uint32_t)qo, (int)(uint32_t)(qo >> 32), (int)(uint32_t)ro, (int)(uint32_t)(ro >> 32)};
                 // (nblocks < bcap && top + MQ_TW + 64 <= tcap as one compare of nblocks: the first count that fails either)
                 const long long room = (long long)tcap - (long long)(MQ_TW + 64u) - (long long)tt_in;
                 const unsigned long long nb_room = room < 0 ? 0ull : (unsigned long long)nblocks + (unsigned long long)room / MQ_TW + 1ull;
@@ -753,6 +755,13 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
                 }
             };
             const uint32_t base32 = (uint32_t)(uintptr_t)base;   // (the low word of a generic pointer into LDS is the LDS address)
+            // Round 9, traced kernels: the sequence bytes are fetched at bp.pool + a 32-bit offset -- one v_add per address and a load with the
+            // pool's base in scalar registers, where a 64-bit address per lane took ten vector instructions a step and, coming out of LDS as
+            // integers, made the loads flat ones (counted in lgkmcnt too: the first column's wait for its scores also waited for them). The host
+            // sets F_POOL64 where an offset could pass 32 bits (pool + two blocks + 8 bytes, ba_host.cpp params()): those batches fetch nothing
+            // ahead -- every step reads its bytes where a slot that has just taken its pair does, by 64-bit offset.
+            typedef const __attribute__((address_space(1))) uint8_t* glb_cu8_ptr;
+            typedef const __attribute__((address_space(1))) uint32_t* glb_cu32_ptr;
             do {
                 // ---- the step every live slot is about to take (scan_block.rs:147-246)
                 const bool right = dir == DIR_RIGHT;
@@ -763,6 +772,12 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
                 const uint32_t l8 = (lid & (uint32_t)(SL - 1)) * 8u;
                 const uint32_t lbuf_s = base32 + (lid / (uint32_t)SL) * (2u * BUFL) + 2u * l8;
                 const uint32_t lsc_s = base32 + (uint32_t)MQ_LDS_SCALARS + (lid / (uint32_t)SL) * (4u * (uint32_t)MQ_LSC_INTS);
+                // (the pool's base and the flags: scalar loads from the kernel's arguments, issued here with the slot's constants -- kept across the loop
+                // they would cost scalar registers the driver has none of to spare, and left to the compiler they are loaded right in front of their use)
+                const __attribute__((address_space(4))) BatchParams* kargs = (const __attribute__((address_space(4))) BatchParams*)__builtin_amdgcn_kernarg_segment_ptr();
+                asm volatile("" : "+s"(kargs));
+                const glb_cu8_ptr pool_g = (glb_cu8_ptr)kargs->pool;
+                const bool pool64 = TRACE && (kargs->flags & (uint32_t)F_POOL64);
                 int4 cA = {0, 0, 0, 0}, cB = {0, 0, 0, 0}, cC = {0, 0, 0, 0};
                 if (TRACE) {
                     typedef const __attribute__((address_space(3))) lds_v4i* lds_cint4_ptr;
@@ -770,8 +785,8 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
                                   c4 = *(lds_cint4_ptr)(uintptr_t)(lsc_s + 4u * (MQ_LSC_PAIR + 8u));
                     cA = int4{a4.x, a4.y, a4.z, a4.w}; cB = int4{b4.x, b4.y, b4.z, b4.w}; cC = int4{c4.x, c4.y, c4.z, c4.w};
                 }
-                const uint8_t* const qp = TRACE ? (const uint8_t*)((unsigned long long)(uint32_t)cA.x | ((unsigned long long)(uint32_t)cA.y << 32)) : (const uint8_t*)qa_r;
-                const uint8_t* const rp = TRACE ? (const uint8_t*)((unsigned long long)(uint32_t)cA.z | ((unsigned long long)(uint32_t)cA.w << 32)) : (const uint8_t*)ra_r;
+                const uint8_t* const qp = (const uint8_t*)qa_r; const uint8_t* const rp = (const uint8_t*)ra_r;   // (score-only kernels: the pointers stay in registers)
+                const uint32_t qo32 = (uint32_t)cA.x, ro32 = (uint32_t)cA.z;                                      // (traced kernels: offsets from bp.pool)
                 const uint32_t qlen = TRACE ? (uint32_t)cB.x : qlen_r, rlen = TRACE ? (uint32_t)cB.y : rlen_r;
                 const uint32_t ri = right ? si : sj, rj = (right ? sj : si) + (MB - STEP);
                 const uint32_t lenV = right ? qlen : rlen, lenC = right ? rlen : qlen;
@@ -796,20 +811,34 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
                 {
                     const uint8_t* Vp = right ? qp : rp; const uint8_t* Cp = right ? rp : qp;
                     vb = right ? pf_qv : pf_rv; cbv = right ? pf_rc : pf_qc;
-                    if (__any(run && !pf_ok)) {   // a slot that has just taken its pair (back)
+                    if (__any(run && !pf_ok)) {   // a slot that has just taken its pair (back) (F_POOL64: every slot, in every step)
                         if (run && !pf_ok) {
+                            if constexpr (TRACE) {   // (by 64-bit offset: right whatever the pool's size)
+                                const unsigned long long vo = right ? ((unsigned long long)(uint32_t)cA.x | ((unsigned long long)(uint32_t)cA.y << 32)) : ((unsigned long long)(uint32_t)cA.z | ((unsigned long long)(uint32_t)cA.w << 32));
+                                const unsigned long long co = right ? ((unsigned long long)(uint32_t)cA.z | ((unsigned long long)(uint32_t)cA.w << 32)) : ((unsigned long long)(uint32_t)cA.x | ((unsigned long long)(uint32_t)cA.y << 32));
+                                const glb_cu32_ptr vp = (glb_cu32_ptr)(pool_g + (vo + (ri + l8))), cp = (glb_cu32_ptr)(pool_g + (co + rj));
+                                vb.x = vp[0]; vb.y = vp[1]; cbv.x = cp[0]; cbv.y = cp[1];
+                            } else {
                             const uint32_t* vp = (const uint32_t*)(Vp + (ri + l8));   // (images are 4-byte aligned, positions multiples of 8)
                             vb.x = vp[0]; vb.y = vp[1];
                             const uint32_t* cp = (const uint32_t*)(Cp + rj);
                             cbv.x = cp[0]; cbv.y = cp[1];
+                            }
                         }
                     }
                     asm volatile("" : "+v"(vb.x), "+v"(vb.y));   // (consume the old prefetch before the next one is issued: the memory counter is in-order)
-                    if (run) {                                    // for the step after this one, whichever way it goes
+                    if (!pool64) if (run) {                       // for the step after this one, whichever way it goes (pool64: wave-uniform)
+                        if constexpr (TRACE) {   // (32-bit offsets from the pool's base: see above)
+                            const glb_cu32_ptr a = (glb_cu32_ptr)(pool_g + (unsigned long long)(qo32 + (si + l8))), b = (glb_cu32_ptr)(pool_g + (unsigned long long)(ro32 + (sj + l8)));
+                            const glb_cu32_ptr cq = (glb_cu32_ptr)(pool_g + (unsigned long long)(qo32 + si) + MB), cr = (glb_cu32_ptr)(pool_g + (unsigned long long)(ro32 + sj) + MB);
+                            pf_qv.x = a[0]; pf_qv.y = a[1]; pf_rv.x = b[0]; pf_rv.y = b[1];
+                            pf_qc.x = cq[0]; pf_qc.y = cq[1]; pf_rc.x = cr[0]; pf_rc.y = cr[1];
+                        } else {
                         const uint32_t* a = (const uint32_t*)(qp + (si + l8)); const uint32_t* b = (const uint32_t*)(rp + (sj + l8));
                         const uint32_t* cq = (const uint32_t*)(qp + si + MB); const uint32_t* cr = (const uint32_t*)(rp + sj + MB);
                         pf_qv.x = a[0]; pf_qv.y = a[1]; pf_rv.x = b[0]; pf_rv.y = b[1];
                         pf_qc.x = cq[0]; pf_qc.y = cq[1]; pf_rc.x = cr[0]; pf_rc.y = cr[1];
+                        }
                         pf_ok = true;
                     }
                 }
@@ -926,12 +955,12 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
 #ifndef MQ_HELPER_LANES
 #define MQ_HELPER_LANES 0u   // 0: the emptied wave walks one path at a time with all its lanes (walk_wave); k > 0: k paths, one per lane (1 -> 4 lanes: +1.5 % at config 3; 4 lanes -> the whole wave: +3 %)
 #endif
-        if constexpr (SPM != 0) traceback_consumer<TB_LB>(bp, TB_MASK, (unsigned char*)base, 4u, false);   // (the whole-wave walk takes no mode bits: four lanes' walks instead)
+        if constexpr (SPM != 0) traceback_consumer<TB_LB, TB_CELLS_PER_STEP, BA_RING_DEPTH, true>(bp, TB_MASK, (unsigned char*)base, 4u, false);   // (the whole-wave walk takes no mode bits: four lanes' walks instead)
         else {
 #if MQ_HELPER_LANES == 0
-        traceback_helper_wave<true>(bp, (uint32_t*)base, 2048u);
+        traceback_helper_wave<true, true>(bp, (uint32_t*)base, 2048u);
 #else
-        traceback_consumer<(int)TB_LANE_BYTES_L2>(bp, (uint32_t)F_CIGAR_EQ, (unsigned char*)base, MQ_HELPER_LANES, false);
+        traceback_consumer<(int)TB_LANE_BYTES_L2, TB_CELLS_PER_STEP, BA_RING_DEPTH, true>(bp, (uint32_t)F_CIGAR_EQ, (unsigned char*)base, MQ_HELPER_LANES, false);
 #endif
         }
 #if defined(BA_TIMING) || defined(BA_ENDHIST)

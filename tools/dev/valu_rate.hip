@@ -117,6 +117,11 @@
 #define L_MAXI16_PAIR(r) "v_max_i16 " r ", " r ", %9\n v_max_i16_sdwa " r ", " r ", %9 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_1 src1_sel:WORD_1\n"
 #define L_PERM(r) "v_perm_b32 " r ", " r ", %9, %9\n"
 #define L_SHL16_OR(r) "v_lshlrev_b16 " r ", 8, " r "\n v_or_b32 " r ", " r ", %9\n"
+// ---- round 9: v_swap_b32 (the exchange of k_multi's border roles when a slot turns: eight swaps under the slots' lane mask against sixteen v_cndmask_b32).
+// Four independent pairs of accumulators, twice: 8 instructions where the other cases have ALL8; the group is a swap and three packed adds on its pair.
+#define M_SWAP4 "v_swap_b32 %0, %1\n v_swap_b32 %2, %3\n v_swap_b32 %4, %5\n v_swap_b32 %6, %7\n"
+#define M_SWAPMIX(a, b) "v_swap_b32 " a ", " b "\n v_pk_add_i16 " a ", " a ", %9 clamp\n v_pk_add_i16 " b ", " b ", %9 clamp\n v_pk_add_i16 " a ", " a ", %9 clamp\n"
+#define M_SWAPMIX4 M_SWAPMIX("%0", "%1") M_SWAPMIX("%2", "%3") M_SWAPMIX("%4", "%5") M_SWAPMIX("%6", "%7")
 struct Case { const char* name; int id; int per_group; };   // per_group: VALU instructions counted per accumulator visit
 
 template <int KIND>
@@ -142,6 +147,8 @@ __global__ void __launch_bounds__(256) k(int* out, unsigned long long* ticks, in
         CASE(88, K_CNDE64) CASE(89, K_CNDMIX) CASE(90, K_CND0) CASE(91, K_CNDEXEC)
         CASE(92, L_3PK_AND) CASE(93, L_3PK_BFI) CASE(94, L_4PK) CASE(95, L_SHR_BFI) CASE(96, L_SHR_AND_AND_OR) CASE(97, L_PK_FAST_PK_FAST) CASE(98, L_2PK_2FAST)
         CASE(99, L_MAXI16_PAIR) CASE(100, L_PERM) CASE(101, L_SHL16_OR)
+        if (KIND == 102) { REP8(asm volatile(M_SWAP4 M_SWAP4 : ACC : "s"(s), "v"(vb));) }
+        if (KIND == 103) { REP8(asm volatile(M_SWAPMIX4 M_SWAPMIX4 : ACC : "s"(s), "v"(vb));) }
         CASE(81, J_MAXI16S) CASE(82, J_SUBREV) CASE(83, J_LSHLADD) CASE(84, J_ADDLSHL) CASE(85, J_SADU16) CASE(86, J_MIX2) CASE(87, J_MIX3)
     }
     const unsigned long long t1 = __builtin_amdgcn_s_memtime();
@@ -192,6 +199,11 @@ int main(int argc, char** argv) {
         RUN(95, "group: v_lshrrev_b32 + v_bfi_b32 (one insert of the trace packing)") RUN(96, "group: v_lshrrev_b32 + 2 v_and_b32 + v_or_b32 (the same insert in VOP2 forms)")
         RUN(1, "v_pk_max_i16") RUN(99, "group: v_max_i16 + v_max_i16_sdwa WORD_1 (the same maximum in two halves)")
         RUN(100, "v_perm_b32") RUN(101, "group: v_lshlrev_b16 + v_or_b32")
+        fclose(md); return 0;
+    }
+    if (first == 3) {   // round 9 (profiles/r09_valu_rate.md): v_swap_b32 beside the select it would replace
+        RUN(102, "v_swap_b32") RUN(103, "group: v_swap_b32 + 3 v_pk_add_i16") RUN(88, "v_cndmask_b32_e64 sgpr pair") RUN(89, "group: v_cndmask vcc + 3 v_pk_add_i16")
+        RUN(0, "v_pk_add_i16 clamp") RUN(62, "v_mov_b32")
         fclose(md); return 0;
     }
     if (first) { RUN(24, "v_cndmask_b32 vcc") RUN(88, "v_cndmask_b32_e64 sgpr pair") RUN(89, "group: v_cndmask vcc + 3 v_pk_add_i16") RUN(90, "v_cndmask_b32_e64 sgpr pair = 0") RUN(91, "v_cndmask_b32_e64 exec") RUN(16, "v_bfi_b32") fclose(md); return 0; }
