@@ -270,13 +270,16 @@ struct BaBatch {
     bool pad_negative = false;  // every matrix entry of the padding byte's row and column is negative (pad_negative() at creation): the kernels may clip an X-drop alignment's last block (F_PAD_NEG)
     bool handle_mode = false;   // the device state of one Block handle: one pair per launch, CIGARs only on request (k_traceback)
     DevBuf hblk, rblk;          // handle mode: everything uploaded per align / everything read back, one buffer each
+    // a sequence offset of k_multi's prefetch (pool + two blocks + 8 bytes) could pass 32 bits, or BA_POOL64 in the development library: traced
+    // k_multi batches run the kernels that fetch by 64-bit offset (kernel_fn)
+    bool pool64() const { return (uint64_t)pool.bytes + 2ull * max_size + 8ull > 0xffffffffull || dev_env("BA_POOL64"); }
     BatchParams params() const {
         BatchParams bp{};
         bp.pool = pool.as<uint8_t>();
         bp.q_off = q_off.as<uint64_t>(); bp.q_len = q_len.as<uint32_t>();
         bp.r_off = r_off.as<uint64_t>(); bp.r_len = r_len.as<uint32_t>();
         bp.n = n; bp.gap_open = gap_open; bp.gap_extend = gap_extend;
-        bp.min_size = min_size; bp.max_size = max_size; bp.x_drop = x_drop; bp.flags = mode | (dev_env("BA_NO_FAST") ? 0x100u : 0u) | ((dev_env("BA_SKIP_WALK") || dev_env("BA_NO_TRACEBACK")) ? 0x200u : 0u) | ((handle_mode || dev_env("BA_NO_SPEC")) ? 0x400u : 0u) | (dev_env("BA_NO_TB_WAVES") ? 0x800u : 0u) | (dev_env("BA_NO_REFILL") ? 0x1000u : 0u) | (dev_env("BA_NO_STEAL") ? 0x2000u : 0u) | ((pad_negative && !dev_env("BA_NO_END_CLIP")) ? (uint32_t)ba::F_PAD_NEG : 0u) | (((uint64_t)pool.bytes + 2ull * max_size + 8ull > 0xffffffffull || dev_env("BA_POOL64")) ? (uint32_t)ba::F_POOL64 : 0u);   // (0x400: no speculative grows -- a handle's trace may be walked from any cell)
+        bp.min_size = min_size; bp.max_size = max_size; bp.x_drop = x_drop; bp.flags = mode | (dev_env("BA_NO_FAST") ? 0x100u : 0u) | ((dev_env("BA_SKIP_WALK") || dev_env("BA_NO_TRACEBACK")) ? 0x200u : 0u) | ((handle_mode || dev_env("BA_NO_SPEC")) ? 0x400u : 0u) | (dev_env("BA_NO_TB_WAVES") ? 0x800u : 0u) | (dev_env("BA_NO_REFILL") ? 0x1000u : 0u) | (dev_env("BA_NO_STEAL") ? 0x2000u : 0u) | ((pad_negative && !dev_env("BA_NO_END_CLIP")) ? (uint32_t)ba::F_PAD_NEG : 0u) | (pool64() ? (uint32_t)ba::F_POOL64 : 0u) | (dev_env("BA_COUNT_STEPS") ? (uint32_t)ba::F_COUNT_STEPS : 0u);   // (0x400: no speculative grows -- a handle's trace may be walked from any cell)
         bp.matrix = matrix.as<int8_t>();
         bp.score = score.as<int32_t>(); bp.query_idx = qidx.as<uint32_t>(); bp.reference_idx = ridx.as<uint32_t>();
         bp.cig_ops = ((mode & BA_TRACE) && !handle_mode && !dev_env("BA_NO_TRACEBACK")) ? cig_ops.as<uint32_t>() : nullptr;   // env: development switch
@@ -607,7 +610,11 @@ static size_t kernel_wave_arena_bytes(const BaBatch* b) {
     }
 }
 // The kernel of the entry for the batch's X_DROP bit, with / without traceback; bp's flags choose the form where the family has two.
-static const void* kernel_fn(const BaBatch* b, const ba::KernelEntry* k, bool trace, int form) { return k->fn[form][trace][(b->mode & BA_X_DROP) != 0]; }
+static const void* kernel_fn(const BaBatch* b, const ba::KernelEntry* k, bool trace, int form) {
+    const int xd = (b->mode & BA_X_DROP) != 0;
+    if (trace && k->fn64[form][xd] && b->pool64()) return k->fn64[form][xd];   // (k_multi: the large-pool form is a kernel of its own)
+    return k->fn[form][trace][xd];
+}
 static hipError_t kernel_lds_opt_in(const void* fn, unsigned lds) {   // more than the default dynamic-LDS limit: opt in (160 KB per CU on gfx950)
     return lds > 64 * 1024 ? hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
 }

@@ -39,28 +39,38 @@
 #define K_SMALL_S1(T, X) ba::k_small<BA_PMAX, BA_KIND, T, X, 1>
 #define K_SMALL_S2(T, X) ba::k_small<BA_PMAX, BA_KIND, T, X, 2>
 #define K_QUAD(T, X) ba::k_quad<BA_KIND, T, X>
+// k_multi's traced kernels for pools beyond 32 bits: P(X) is a family's instantiation of k_multi_p64 with / without X-drop
+#define P_MULTI(X) ba::k_multi_p64<BA_PMAX, BA_KIND, X>
+#define P_MULTI_256(X) ba::k_multi_p64<BA_PMAX, BA_KIND, X, 0, 256>
+#define P_MULTI_512(X) ba::k_multi_p64<BA_PMAX, BA_KIND, X, 0, 512>
+#define P_MULTI_G2(X) ba::k_multi_p64<BA_PMAX, BA_KIND, X, 0, 128, ba::MQ_GEOM_WPW, 2>
+#define P_MULTI_G3(X) ba::k_multi_p64<BA_PMAX, BA_KIND, X, 0, 128, ba::MQ_GEOM_WPW, 3>
+#define P_MULTI_S1(X) ba::k_multi_p64<BA_PMAX, BA_KIND, X, 1>
+#define P_MULTI_S2(X) ba::k_multi_p64<BA_PMAX, BA_KIND, X, 2>
 #define BA_TX(K) {{(const void*)K(false, false), (const void*)K(false, true)}, {(const void*)K(true, false), (const void*)K(true, true)}}
-#define BA_ENTRY(FAM, WPW, K) {FAM, WPW, 0u, {BA_TX(K), {}}}
-#define BA_ENTRY_SPM(FAM, WPW, K1, K2) {FAM, WPW, 0u, {BA_TX(K1), BA_TX(K2)}}   // (the batch's flags choose: spm 1 LOCAL_START, spm 2 FREE_QUERY_START_GAPS)
+#define BA_PX(P) {(const void*)P(false), (const void*)P(true)}
+#define BA_ENTRY(FAM, WPW, K) {FAM, WPW, 0u, {BA_TX(K), {}}, {}}
+#define BA_ENTRY_P64(FAM, WPW, K, P) {FAM, WPW, 0u, {BA_TX(K), {}}, {BA_PX(P), {}}}
+#define BA_ENTRY_SPM(FAM, WPW, K1, K2, P1, P2) {FAM, WPW, 0u, {BA_TX(K1), BA_TX(K2)}, {BA_PX(P1), BA_PX(P2)}}   // (the batch's flags choose: spm 1 LOCAL_START, spm 2 FREE_QUERY_START_GAPS)
 
 static const ba::KernelEntry g_entries[] = {
     BA_ENTRY(BA_BIG ? ba::FAM_TILED : ba::FAM_PAIR, ba::WAVES_PER_WG, K_ALIGN),
 #if BA_KIND != 3 && !BA_SPECIAL && !BA_BIG
     // four pairs per wave while the block is 128 cells, everything else by the same wave on all its lanes (ba_multi.hpp): one kernel per
     // kind and block class
-    BA_ENTRY(ba::FAM_MULTI, ba::WAVES_PER_WG, K_MULTI),
+    BA_ENTRY_P64(ba::FAM_MULTI, ba::WAVES_PER_WG, K_MULTI, P_MULTI),
 #if BA_KIND == 1 && BA_PMAX >= 4
     // ... with two slots of 256 cells per wave (round 6: DNA batches that start at 256 cells, block classes 512 .. 2048)
-    BA_ENTRY(ba::FAM_MULTI_256, ba::WAVES_PER_WG, K_MULTI_256),
+    BA_ENTRY_P64(ba::FAM_MULTI_256, ba::WAVES_PER_WG, K_MULTI_256, P_MULTI_256),
 #endif
 #if BA_KIND == 1 && BA_PMAX >= 8
     // ... with one slot of 512 cells per wave (round 6: DNA batches that start at 512 cells -- percent_len 1 % of reads above 25.6 kbp --, block classes 1024 and 2048)
-    BA_ENTRY(ba::FAM_MULTI_512, ba::WAVES_PER_WG, K_MULTI_512),
+    BA_ENTRY_P64(ba::FAM_MULTI_512, ba::WAVES_PER_WG, K_MULTI_512, P_MULTI_512),
 #endif
 #if BA_KIND == 1 && (BA_PMAX == 4 || BA_PMAX == 8)
     // ... in workgroups of four waves at three / two waves per SIMD (round 6: DNA batches whose pairs fill that many waves' slots about once -- ba_host.cpp batch_build)
-    BA_ENTRY(ba::FAM_MULTI_G3, ba::MQ_GEOM_WPW, K_MULTI_G3),
-    BA_ENTRY(ba::FAM_MULTI_G2, ba::MQ_GEOM_WPW, K_MULTI_G2),
+    BA_ENTRY_P64(ba::FAM_MULTI_G3, ba::MQ_GEOM_WPW, K_MULTI_G3, P_MULTI_G3),
+    BA_ENTRY_P64(ba::FAM_MULTI_G2, ba::MQ_GEOM_WPW, K_MULTI_G2, P_MULTI_G2),
 #endif
 #endif
 #if !BA_SPECIAL && !BA_BIG && BA_PMAX <= 8
@@ -71,15 +81,15 @@ static const ba::KernelEntry g_entries[] = {
 #if BA_SPECIAL && !BA_BIG && BA_KIND != 3
     // k_multi for LOCAL_START / FREE_QUERY_START_GAPS batches of the sequence kinds: the slots take these modes' plain steps too
     // (FREE_QUERY_END_GAPS batches stay with the per-pair kernel: the mode's running column maxima are not a slot's)
-    BA_ENTRY_SPM(ba::FAM_MULTI, ba::WAVES_PER_WG, K_MULTI_S1, K_MULTI_S2),
+    BA_ENTRY_SPM(ba::FAM_MULTI, ba::WAVES_PER_WG, K_MULTI_S1, K_MULTI_S2, P_MULTI_S1, P_MULTI_S2),
 #endif
 #if BA_SPECIAL && !BA_BIG && BA_PMAX <= 8 && BA_KIND != 3
     // ... and k_small for the same two modes
-    BA_ENTRY_SPM(ba::FAM_SMALL, ba::WAVES_PER_WG, K_SMALL_S1, K_SMALL_S2),
+    {ba::FAM_SMALL, ba::WAVES_PER_WG, 0u, {BA_TX(K_SMALL_S1), BA_TX(K_SMALL_S2)}, {}},
 #endif
 #if BA_PMAX == 1 && !BA_SPECIAL && !BA_BIG
     // four pairs per wave while the block is 32 cells (ba_quad.hpp): one kernel per kind, its LDS fixed
-    {ba::FAM_QUAD, ba::WAVES_PER_WG, ba::lds_table_bytes_h(BA_KIND) + ba::WAVES_PER_WG * 4 * ba::QUAD_SLOT_BYTES, {BA_TX(K_QUAD), {}}},
+    {ba::FAM_QUAD, ba::WAVES_PER_WG, ba::lds_table_bytes_h(BA_KIND) + ba::WAVES_PER_WG * 4 * ba::QUAD_SLOT_BYTES, {BA_TX(K_QUAD), {}}, {}},
 #endif
 };
 [[maybe_unused]] static const int g_registered = ba::register_kernels(BA_KIND, BA_PMAX, BA_SPECIAL != 0, g_entries, (int)(sizeof g_entries / sizeof g_entries[0]));

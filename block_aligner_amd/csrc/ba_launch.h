@@ -28,12 +28,14 @@ constexpr int N_KINDS = 4, N_CLASSES = 6;   // block classes: 128 << c cells for
 
 // One family as one translation unit instantiates it. fn[form][trace][xdrop] are the kernels' host addresses, each taking one
 // BatchParams by value. A family has one form -- except k_multi and k_small in a special-mode unit: form 0 is for LOCAL_START
-// batches, form 1 for FREE_QUERY_START_GAPS batches.
+// batches, form 1 for FREE_QUERY_START_GAPS batches. fn64[form][xdrop]: k_multi's traced kernels for batches whose sequence pool does not
+// fit in 32 bits (F_POOL64, k_multi_p64 of ba_multi.hpp); null in every other family, whose kernels take any pool.
 struct KernelEntry {
     KernelFamily family;
     unsigned wpw;   // waves per workgroup the kernels are launched with
     unsigned lds;   // bytes of LDS per workgroup where the kernel fixes them (k_quad); 0: the host sizes them by the block class
     const void* fn[2][2][2];
+    const void* fn64[2][2];
 };
 
 // A kernel translation unit (ba_kernels.hip, compiled per matrix kind, packed registers per lane = 1 .. 16 or 32 for the

@@ -49,15 +49,17 @@ __device__ __forceinline__ int sel_mask(unsigned long long m, int a, int b) {
 // row operations; a 32-lane slot spans two DPP rows, so its shifts are whole-wave shifts with the slot's own edge lane patched, and its broadcasts
 // go through the LDS crossbar (ds_bpermute: three per step). l = the lane inside its slot.
 // (SL = 64, round 6: one slot of 512 cells -- the whole wave: the edges are the wave's, the broadcasts scalar reads of lane 0 / 63)
-template <int SL> __device__ __forceinline__ int slot_first(int v) {   // the slot's first lane's value, to all its lanes
+// (wl: the lane in its wave, read by the 32-lane forms only. k_multi's loop of steps passes the number it derives in every step: a source address
+// computed once would be one more value the allocator reloads from scratch memory in front of the loop, outstanding at the loop's top)
+template <int SL> __device__ __forceinline__ int slot_first(int v, int wl) {   // the slot's first lane's value, to all its lanes
     if constexpr (SL == 16) return row_bcast<0>(v);
     else if constexpr (SL == 64) return __builtin_amdgcn_readfirstlane(v);
-    else return __builtin_amdgcn_ds_bpermute((lane_id() & 32) << 2, v);
+    else return __builtin_amdgcn_ds_bpermute((wl & 32) << 2, v);
 }
-template <int SL> __device__ __forceinline__ int slot_last(int v) {    // the slot's last lane's value, to all its lanes
+template <int SL> __device__ __forceinline__ int slot_last(int v, int wl) {    // the slot's last lane's value, to all its lanes
     if constexpr (SL == 16) return row_bcast<15>(v);
     else if constexpr (SL == 64) return __builtin_amdgcn_readlane(v, 63);
-    else return __builtin_amdgcn_ds_bpermute(((lane_id() & 32) + 31) << 2, v);
+    else return __builtin_amdgcn_ds_bpermute(((wl & 32) + 31) << 2, v);
 }
 template <int SL> __device__ __forceinline__ int slot_shr1_z(int v, int l) {   // lane l <- l - 1 inside the slot; its first lane <- 0
     if constexpr (SL == 16) return row_shr1_z(v);
@@ -157,7 +159,7 @@ struct MultiOut { int mx, act_max8, pas_max8, corner_new; };
 
 // One 8-column shift step for the four slots of a wave, 8 cells per lane (scan_block.rs:147-246 with place_block 1083-1228 and
 // the border moves 1003-1061 folded in). (Ad, Ac): the border pair along the step's vector axis, (Pd, Pr) the orthogonal pair.
-// tout: this lane's eight trace words of the step: word (column >> 1) * 2 + p2 holds cells (2 p2, 2 p2 + 1, 2 p2 + 4, 2 p2 + 5) x 2 columns, the registers'
+// tout: this lane's eight trace words of the step, returned in registers (round 10: the caller stores them): word (column >> 1) * 2 + p2 holds cells (2 p2, 2 p2 + 1, 2 p2 + 4, 2 p2 + 5) x 2 columns, the registers'
 // order (round 9) -- cell c is byte slot_cell_byte<true>(c) of its column pair's eight (ba_driver.hpp), which every walker of this kernel uses.
 // SPM (round 5): the special alignment modes a slot takes, as in small_rect (ba_small.hpp) -- 1 = LOCAL_START (every cell's D is at least the relative
 // zero rz2; TRACE: a zero mask of one bit per cell, two words per lane -- cells 0 .. 3 / 4 .. 7, byte = cell, bit = column --, stored by the caller behind
@@ -165,7 +167,7 @@ struct MultiOut { int mx, act_max8, pas_max8, corner_new; };
 template <int KIND, bool TRACE, int SPM = 0, int SL = 16>
 __device__ __forceinline__ void multi_rect(const char* table, const FillConsts& fc, const MultiConsts& mc, int l, int (&Ad)[4], int (&Ac)[4],
                                            int (&Pd)[4], int (&Pr)[4], uint2 vb, uint32_t cb_lo, uint32_t cb_hi, int corner, int off_add,
-                                           uint32_t* __restrict__ tout, bool store, MultiOut& o, int rz2 = 0, bool fqs_row0 = false, int* zout = nullptr) {
+                                           int (&tout)[8], MultiOut& o, int wl, int rz2 = 0, bool fqs_row0 = false, int* zout = nullptr) {
     uint32_t zacc[2] = {0, 0};   // LOCAL_START + TRACE: "D differs from the relative zero", inverted at the end
     const int offa = splat(off_add);
     int d[4], c[4], pd[4], pr[4];
@@ -173,7 +175,7 @@ __device__ __forceinline__ void multi_rect(const char* table, const FillConsts& 
     for (int k = 0; k < 4; k++) {   // just_offset (scan_block.rs:1003-1012)
         d[k] = adds(Ad[k], offa); c[k] = adds(Ac[k], offa); pd[k] = adds(Pd[k], offa); pr[k] = adds(Pr[k], offa);
     }
-    o.corner_new = slot_first<SL>(pd[3]) >> 16;   // D_corner for a following orthogonal step: the orthogonal border's entry 7, re-based
+    o.corner_new = slot_first<SL>(pd[3], wl) >> 16;   // D_corner for a following orthogonal step: the orthogonal border's entry 7, re-based
     ScoreKey<KIND> key[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) key[k] = make_key<KIND>((int)((vb.x >> (8 * k)) & 0xffu), (int)((vb.y >> (8 * k)) & 0xffu));   // cells k, k + 4
@@ -266,11 +268,8 @@ __device__ __forceinline__ void multi_rect(const char* table, const FillConsts& 
         else { holdD[j] = dn[3]; holdR[j] = r[3]; }
     }
     if (TRACE) {
-#ifndef MQ_X_NOTRSTORE
-        if (store) { *(int4*)tout = int4{tacc[0], tacc[1], tacc[2], tacc[3]}; *(int4*)(tout + 4) = int4{tacc[4], tacc[5], tacc[6], tacc[7]}; }
-#else
-        asm volatile("" :: "v"(tacc[0]), "v"(tacc[1]), "v"(tacc[2]), "v"(tacc[3]), "v"(tacc[4]), "v"(tacc[5]), "v"(tacc[6]), "v"(tacc[7]));
-#endif
+#pragma unroll
+        for (int k = 0; k < 8; k++) tout[k] = tacc[k];   // (stored by the caller: round 10, see k_multi's loop of steps)
     }
 #pragma unroll
     for (int k = 0; k < 4; k++) {   // shift_and_offset (scan_block.rs:1040-1061): 8 entries = one lane
@@ -281,12 +280,12 @@ __device__ __forceinline__ void multi_rect(const char* table, const FillConsts& 
         const int ma = vmax(vmax(d[0], d[1]), vmax(d[2], d[3])), mb = vmax(vmax(Pd[0], Pd[1]), vmax(Pd[2], Pd[3]));
         const s16x2 sa = as_s(ma), sb = as_s(mb);
         const int xa = vmax(ma, as_i(s16x2{sa.y, sa.x})), xb = vmax(mb, as_i(s16x2{sb.y, sb.x}));
-        const s16x2 rr = as_s(slot_first<SL>(__builtin_amdgcn_perm(xb, xa, 0x05040100)));
+        const s16x2 rr = as_s(slot_first<SL>(__builtin_amdgcn_perm(xb, xa, 0x05040100), wl));
         o.act_max8 = rr.x; o.pas_max8 = rr.y;
     }
     const int mm = vmax(vmax(dmax[0], dmax[1]), vmax(dmax[2], dmax[3]));
     const int m32 = max(mm & 0xffff, (int)((uint32_t)mm >> 16));   // halves are >= 0 (D_max starts at MIN = 0)
-    o.mx = slot_last<SL>(SL == 16 ? wave_prefix_max16(m32) : (SL == 64 ? wave_prefix_max(m32) : wave_prefix_max32(m32)));
+    o.mx = slot_last<SL>(SL == 16 ? wave_prefix_max16(m32) : (SL == 64 ? wave_prefix_max(m32) : wave_prefix_max32(m32)), wl);
     if constexpr (TRACE && SPM == 1) { zout[0] = ~__builtin_amdgcn_perm((int)zacc[1], (int)zacc[0], 0x05040100); zout[1] = ~__builtin_amdgcn_perm((int)zacc[1], (int)zacc[0], 0x07060302); }
 }
 
@@ -319,8 +318,10 @@ __device__ __forceinline__ int mq_load(const char* p) { return __hip_atomic_load
 // WPW / EU (round 6): waves per workgroup and waves per SIMD the instantiation is compiled and launched for. The batch geometry is the host's choice
 // (ba_host.cpp batch_build): eight-wave workgroups at four waves per SIMD for batches of many rounds; four-wave workgroups -- one wave per SIMD,
 // EU of them per CU -- at three or two waves per SIMD (168 / 256 registers) for batches whose pairs fill the slots of that many waves about once.
-template <int PMAX, int KIND, bool TRACE, bool XDROP, int SPM = 0, int MBP = 128, int WPW = WAVES_PER_WG, int EU = MQ_WAVES_EU>
-__global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const BatchParams bp) {
+// P64 (round 10): the form for batches whose sequence pool does not fit in 32 bits (F_POOL64) -- the slots' prefetch adds 64-bit offsets to the pool's
+// base. The body of two kernels, k_multi and k_multi_p64 (below): the form is the host's choice at the launch, never a branch in the loop of steps.
+template <int PMAX, int KIND, bool TRACE, bool XDROP, int SPM, int MBP, int WPW, int EU, bool P64>
+__device__ __forceinline__ void multi_body(const BatchParams& bp) {
     // a slot rectangle's words on the trace stack (LOCAL_START: the zero mask takes 32 words behind the 128 trace words; the stack advances as the
     // per-pair kernel's does -- a mask word per trace word, Aligner::add_block); the walkers' records and mode bits (the special modes: room for the
     // zero-mask bits, the early stops of scan_block.rs:1597-1611)
@@ -716,7 +717,7 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
                 // records start, how many records the slot has room for -- is read from LDS in every step instead of living in registers through
                 // the columns (the two addresses were a 64-bit multiply each in every step: they change only with the pair)
                 // (round 9: the images' OFFSETS from bp.pool, words 0 and 2. The step's prefetch adds them to the pool's base as 32-bit values, see there;
-                // words 1 and 3, the offsets' high halves, are read only where a slot has no prefetched bytes -- and are zero unless F_POOL64 is set)
+                // words 1 and 3, the offsets' high halves, are read by the fetch before the loop and by the P64 form's prefetch -- and are zero unless F_POOL64 is set)
                 const unsigned long long qo = live ? bp.q_off[pair] : 0ull, ro = live ? bp.r_off[pair] : 0ull;
                 *(int4*)(lsc + MQ_LSC_PAIR) = int4{(int)(uint32_t)qo, (int)(uint32_t)(qo >> 32), (int)(uint32_t)ro, (int)(uint32_t)(ro >> 32)};
                 // (nblocks < bcap && top + MQ_TW + 64 <= tcap as one compare of nblocks: the first count that fails either)
@@ -724,7 +725,11 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
                 const unsigned long long nb_room = room < 0 ? 0ull : (unsigned long long)nblocks + (unsigned long long)room / MQ_TW + 1ull;
                 const uint32_t nb_lim = (uint32_t)(nb_room < (unsigned long long)bcap ? nb_room : (unsigned long long)bcap);
                 *(int4*)(lsc + MQ_LSC_PAIR + 4) = int4{live ? (int)bp.q_len[pair] : 0, live ? (int)bp.r_len[pair] : 0, (int)nb_lim, 0};
-                const unsigned long long ta = (unsigned long long)(bp.trace_arena + (uint64_t)tslot * bp.trace_stride), ba = (unsigned long long)(bp.blocks + (uint64_t)tslot * bp.blocks_stride);
+                // (round 10: a dead slot issues the loads and stores of a step as the live ones do. It reads at the pool's start -- offsets 0 above -- and
+                // writes its trace words and its record, always at count 0, into its own unused buffers in the arena: words into buffer 0, the record into buffer 1)
+                static_assert(4u * MB + (SPM == 1 ? MB : 0u) <= BUFA && sizeof(BlockRec) <= BUFA, "a dead slot's stores stay inside its own buffers");
+                const unsigned long long ta = live ? (unsigned long long)(bp.trace_arena + (uint64_t)tslot * bp.trace_stride) : (unsigned long long)slot_mem;
+                const unsigned long long ba = live ? (unsigned long long)(bp.blocks + (uint64_t)tslot * bp.blocks_stride) : (unsigned long long)(slot_mem + BUFA);
                 *(int4*)(lsc + MQ_LSC_PAIR + 8) = int4{(int)(uint32_t)ta, (int)(uint32_t)(ta >> 32), (int)(uint32_t)ba, (int)(uint32_t)(ba >> 32)};
             }
             if (live) {
@@ -739,8 +744,9 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
             }
             lds_sync();
             // sequence bytes of the next step, fetched one step ahead for both possible directions
-            uint2 pf_qv = {0, 0}, pf_rv = {0, 0}, pf_qc = {0, 0}, pf_rc = {0, 0}; bool pf_ok = false;
-            bool leave = false;
+            uint2 pf_qv = {0, 0}, pf_rv = {0, 0}, pf_qc = {0, 0}, pf_rc = {0, 0};
+            // leave: the slot goes through solo mode next; rolled: ... because its last step was rolled back (its registers are garbage, its state is what was staged)
+            bool leave = false, rolled = false;
             // the slot's registers and the scalars of the step at the top into the buffer `which` (see above)
             // (lb: the LDS address of this lane's 16 bytes of the slot's first array in buffer 0, ls: of the slot's scalars)
             auto stage = [&](uint32_t lb, uint32_t ls, uint32_t which, uint32_t s_i, uint32_t s_j, int s_off, uint32_t s_tt, uint32_t s_nb, int s_dir, int s_offadd, int s_corner) {
@@ -749,7 +755,8 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
                 const lds_int4_ptr b = (lds_int4_ptr)(uintptr_t)(lb + which * BUFL);
                 b[0] = lds_v4i{A_d[0], A_d[1], A_d[2], A_d[3]}; b[ARR / 16] = lds_v4i{A_c[0], A_c[1], A_c[2], A_c[3]};
                 b[2 * ARR / 16] = lds_v4i{P_d[0], P_d[1], P_d[2], P_d[3]}; b[3 * ARR / 16] = lds_v4i{P_r[0], P_r[1], P_r[2], P_r[3]};
-                if (l == 0) {
+                {   // (by every lane of the slot, the same values to the same address: a branch on the lane inside the loop of steps would have the
+                    // compiler restructure the loop's exit -- and with it what it knows of the memory counter at the loop's top)
                     const lds_int_ptr sc = (lds_int_ptr)(uintptr_t)ls + which * MQ_LSC_STATE;
                     sc[0] = 1; sc[1] = (int)s_i; sc[2] = (int)s_j; sc[3] = s_off; sc[4] = (int)s_tt; sc[5] = (int)s_nb; sc[6] = s_dir; sc[7] = s_offadd; sc[8] = s_corner;
                 }
@@ -758,11 +765,81 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
             // Round 9, traced kernels: the sequence bytes are fetched at bp.pool + a 32-bit offset -- one v_add per address and a load with the
             // pool's base in scalar registers, where a 64-bit address per lane took ten vector instructions a step and, coming out of LDS as
             // integers, made the loads flat ones (counted in lgkmcnt too: the first column's wait for its scores also waited for them). The host
-            // sets F_POOL64 where an offset could pass 32 bits (pool + two blocks + 8 bytes, ba_host.cpp params()): those batches fetch nothing
-            // ahead -- every step reads its bytes where a slot that has just taken its pair does, by 64-bit offset.
+            // launches the P64 form where an offset could pass 32 bits (F_POOL64: pool + two blocks + 8 bytes, ba_host.cpp BaBatch::pool64()): its
+            // prefetch adds the 64-bit offsets.
+            //
+            // Round 10: every vector-memory instruction of the loop is issued in every step, by every slot, in one order -- the trace words (the zero
+            // mask) of the step before, the four prefetch loads, the record --, so that the compiler can count them: the only wait on the memory counter inside the loop
+            // is the one in front of the prefetched bytes' first use, and it leaves the step's stores outstanding (vmcnt(3)). A memory instruction
+            // that some slots or some steps skip makes every later wait a draining one (the counter is in order; behind a join the compiler
+            // must assume the worst). What made them conditional, and where it went:
+            //   - a slot that has just taken its pair (back) had no prefetched bytes: its first fetch is issued here, before the loop;
+            //   - a slot that may not take the step (no room in its trace slot, the matrix edge without X-drop) ended the loop after the step of
+            //     the others: whether a slot may take its NEXT step is decided at the end of a step now, with the step's outcome, and ends the loop
+            //     there (before the first step: the loop is not entered) -- inside a step every live slot runs. The loop keeps its single exit;
+            //   - a dead slot reads and writes harmless addresses of its own (see where the slot's constants are written);
+            //   - the record is stored by every lane of its slot (the same 16 bytes to the same address) instead of by the first one;
+            //   - the trace words of a step are stored at the top of the NEXT step, when all slots are known to have committed it (behind the loop: by
+            //     the slots that committed the last one). The first step of a visit has none to store: it writes zeros into the slot's own state
+            //     buffer 0 in the arena, which is stale while the slots run (both buffers are written back behind the loop);
+            //   - the large-pool form is a kernel of its own (P64).
             typedef const __attribute__((address_space(1))) uint8_t* glb_cu8_ptr;
             typedef const __attribute__((address_space(1))) uint32_t* glb_cu32_ptr;
+            // A step that could break early at the matrix edge (never with X-drop) or that the trace slot has no room for is not a slot's: such a slot
+            // goes through solo mode, and the other slots take their steps when they come back (a slot's sequence of steps does not depend on its
+            // neighbours'). s_len: {query length, reference length, the record count that has no room}
+            auto eligible = [&](uint32_t s_i, uint32_t s_j, int s_dir, uint32_t s_nb, uint32_t qlen, uint32_t rlen, uint32_t nb_lim) {
+                const bool rt = s_dir == DIR_RIGHT;
+                bool e = XDROP || (rt ? s_i : s_j) + MB <= (rt ? qlen : rlen) || (rt ? s_j : s_i) + MB <= (rt ? rlen : qlen);
+                if (TRACE) e = e && s_nb < nb_lim;   // (room for the step's record and trace words: the limit set when the slot took its pair)
+                return e;
+            };
+            {
+                uint32_t qlen = qlen_r, rlen = rlen_r, nb_lim = 0;
+                if constexpr (TRACE) { const int4 b4 = *(const int4*)(lsc + MQ_LSC_PAIR + 4); qlen = (uint32_t)b4.x; rlen = (uint32_t)b4.y; nb_lim = (uint32_t)b4.z; }
+                leave = live && !eligible(si, sj, dir, nblocks, qlen, rlen, nb_lim);
+            }
+            // (a step's words are stored at the top of the next step, the last step's behind the loop; before the first step: see above)
+            static_assert(4u * MB + (SPM == 1 ? MB : 0u) <= BUFL, "the first step's stores stay inside the slot's buffer 0");
+            // (as a pointer to global memory: through a generic one the stores would be flat ones, counted with the LDS operations too)
+            typedef __attribute__((address_space(1))) uint32_t* glb_u32_ptr;
+            typedef __attribute__((address_space(1))) vec_v4i* glb_v4i_ptr;
+            typedef int vec_v2i __attribute__((ext_vector_type(2)));
+            typedef __attribute__((address_space(1))) vec_v2i* glb_v2i_ptr;
+            glb_u32_ptr tw = (glb_u32_ptr)(uintptr_t)slot_mem + 8 * l;
+            int zw[2] = {0, 0}, tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            bool commit = false;
+            // the step's trace words, and the rectangle's zero mask behind its 128 trace words
+            auto store_words = [&]() {
+                if constexpr (TRACE) {
+#ifndef MQ_X_NOTRSTORE
+                    *(glb_v4i_ptr)tw = vec_v4i{tacc[0], tacc[1], tacc[2], tacc[3]}; *(glb_v4i_ptr)(tw + 4) = vec_v4i{tacc[4], tacc[5], tacc[6], tacc[7]};
+#else
+                    asm volatile("" :: "v"(tacc[0]), "v"(tacc[1]), "v"(tacc[2]), "v"(tacc[3]), "v"(tacc[4]), "v"(tacc[5]), "v"(tacc[6]), "v"(tacc[7]));
+#endif
+                    if constexpr (SPM == 1) *(glb_v2i_ptr)(tw - 8 * l + 128 + 2 * l) = vec_v2i{zw[0], zw[1]};
+                }
+            };
+            if (!__any(leave)) {
+            {   // the first step's bytes: what the prefetch of a step before it would have read (the columns: the block's last STEP), by 64-bit offset
+                unsigned long long qa = qa_r, ra = ra_r;
+                if constexpr (TRACE) {
+                    const int4 a4 = *(const int4*)(lsc + MQ_LSC_PAIR);
+                    qa = (unsigned long long)bp.pool + ((unsigned long long)(uint32_t)a4.x | ((unsigned long long)(uint32_t)a4.y << 32));
+                    ra = (unsigned long long)bp.pool + ((unsigned long long)(uint32_t)a4.z | ((unsigned long long)(uint32_t)a4.w << 32));
+                }
+                const uint32_t* a = (const uint32_t*)((const uint8_t*)qa + (si + 8u * (uint32_t)l)); const uint32_t* b = (const uint32_t*)((const uint8_t*)ra + (sj + 8u * (uint32_t)l));
+                const uint32_t* cq = (const uint32_t*)((const uint8_t*)qa + si + (MB - STEP)); const uint32_t* cr = (const uint32_t*)((const uint8_t*)ra + sj + (MB - STEP));
+                pf_qv.x = a[0]; pf_qv.y = a[1]; pf_rv.x = b[0]; pf_rv.y = b[1];
+                pf_qc.x = cq[0]; pf_qc.y = cq[1]; pf_rc.x = cr[0]; pf_rc.y = cr[1];
+                // (waited for here, once per visit: the loop is entered with nothing outstanding, so the wait at its top is the back edge's)
+                // (... and what the allocator may have kept in scratch memory over the solo driver: reloaded before this point, not in the loop's
+                // preheader behind it, where a reload would be one more thing outstanding at the loop's top)
+                asm volatile("" : "+v"(pf_qv.x), "+v"(pf_qv.y), "+v"(pf_rv.x), "+v"(pf_rv.y), "+v"(pf_qc.x), "+v"(pf_qc.y), "+v"(pf_rc.x), "+v"(pf_rc.y),
+                                  "+v"(mc.laneKG), "+v"(mc.lanem1KG), "+v"(mc.w0), "+v"(tw));
+            }
             do {
+                store_words();   // the step before this one: every live slot has committed it (a dead one writes into its own buffer)
                 // ---- the step every live slot is about to take (scan_block.rs:147-246)
                 const bool right = dir == DIR_RIGHT;
                 // (the lane's number, and with it the slot's two addresses in LDS: from the hardware's lane count in every step, not from kernel-wide
@@ -772,12 +849,11 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
                 const uint32_t l8 = (lid & (uint32_t)(SL - 1)) * 8u;
                 const uint32_t lbuf_s = base32 + (lid / (uint32_t)SL) * (2u * BUFL) + 2u * l8;
                 const uint32_t lsc_s = base32 + (uint32_t)MQ_LDS_SCALARS + (lid / (uint32_t)SL) * (4u * (uint32_t)MQ_LSC_INTS);
-                // (the pool's base and the flags: scalar loads from the kernel's arguments, issued here with the slot's constants -- kept across the loop
-                // they would cost scalar registers the driver has none of to spare, and left to the compiler they are loaded right in front of their use)
+                // (the pool's base: a scalar load from the kernel's arguments, issued here with the slot's constants -- kept across the loop
+                // it would cost scalar registers the driver has none of to spare, and left to the compiler it is loaded right in front of its use)
                 const __attribute__((address_space(4))) BatchParams* kargs = (const __attribute__((address_space(4))) BatchParams*)__builtin_amdgcn_kernarg_segment_ptr();
                 asm volatile("" : "+s"(kargs));
                 const glb_cu8_ptr pool_g = (glb_cu8_ptr)kargs->pool;
-                const bool pool64 = TRACE && (kargs->flags & (uint32_t)F_POOL64);
                 int4 cA = {0, 0, 0, 0}, cB = {0, 0, 0, 0}, cC = {0, 0, 0, 0};
                 if (TRACE) {
                     typedef const __attribute__((address_space(3))) lds_v4i* lds_cint4_ptr;
@@ -789,67 +865,54 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
                 const uint32_t qo32 = (uint32_t)cA.x, ro32 = (uint32_t)cA.z;                                      // (traced kernels: offsets from bp.pool)
                 const uint32_t qlen = TRACE ? (uint32_t)cB.x : qlen_r, rlen = TRACE ? (uint32_t)cB.y : rlen_r;
                 const uint32_t ri = right ? si : sj, rj = (right ? sj : si) + (MB - STEP);
-                const uint32_t lenV = right ? qlen : rlen, lenC = right ? rlen : qlen;
                 const bool q_out = si + MB > qlen, r_out = sj + MB > rlen;
-                // a step that could break early at the matrix edge (never with X-drop) or that the trace slot has no room for is not a slot's
-                bool elig = XDROP || ri + MB <= lenV || rj + STEP <= lenC;
                 const uint32_t trace_top = tt0 + nblocks * MQ_TW;
-                if (TRACE) elig = elig && nblocks < (uint32_t)cB.z;   // (room for the step's record and trace words: the limit set when the slot took its pair)
-                leave = live && !elig;
-                const bool run = live && !leave;
                 const int off_n = off_max;
                 const int off_add = sat16(off - off_n);
                 const int corner = (prev_dir != dir && prev_dir != DIR_GROW) ? sat16(D_corner + off_add) : 0;
-                // the state before the step: for a slot that leaves (its registers do not survive the step) and for the checkpoint
+                // the state before the step: for a slot whose step is rolled back (its registers do not survive the step) and for the checkpoint
+                // (a dead slot's goes into its own, unused buffers)
 #ifndef MQ_X_NOSTAGE
-                if (live) stage(lbuf_s, lsc_s, sel ^ 1u, si, sj, off_n, trace_top, nblocks, dir, off_add, corner);
+                stage(lbuf_s, lsc_s, sel ^ 1u, si, sj, off_n, trace_top, nblocks, dir, off_add, corner);
 #endif
                 // (should the allocator keep the column code's per-lane constants in scratch memory after all: reloaded here, before the prefetch
                 // is issued, a reload waits for nothing but the previous step's stores)
                 asm volatile("" : "+v"(mc.laneKG), "+v"(mc.lanem1KG), "+v"(mc.w0));
-                uint2 vb, cbv;
-                {
-                    const uint8_t* Vp = right ? qp : rp; const uint8_t* Cp = right ? rp : qp;
-                    vb = right ? pf_qv : pf_rv; cbv = right ? pf_rc : pf_qc;
-                    if (__any(run && !pf_ok)) {   // a slot that has just taken its pair (back) (F_POOL64: every slot, in every step)
-                        if (run && !pf_ok) {
-                            if constexpr (TRACE) {   // (by 64-bit offset: right whatever the pool's size)
-                                const unsigned long long vo = right ? ((unsigned long long)(uint32_t)cA.x | ((unsigned long long)(uint32_t)cA.y << 32)) : ((unsigned long long)(uint32_t)cA.z | ((unsigned long long)(uint32_t)cA.w << 32));
-                                const unsigned long long co = right ? ((unsigned long long)(uint32_t)cA.z | ((unsigned long long)(uint32_t)cA.w << 32)) : ((unsigned long long)(uint32_t)cA.x | ((unsigned long long)(uint32_t)cA.y << 32));
-                                const glb_cu32_ptr vp = (glb_cu32_ptr)(pool_g + (vo + (ri + l8))), cp = (glb_cu32_ptr)(pool_g + (co + rj));
-                                vb.x = vp[0]; vb.y = vp[1]; cbv.x = cp[0]; cbv.y = cp[1];
-                            } else {
-                            const uint32_t* vp = (const uint32_t*)(Vp + (ri + l8));   // (images are 4-byte aligned, positions multiples of 8)
-                            vb.x = vp[0]; vb.y = vp[1];
-                            const uint32_t* cp = (const uint32_t*)(Cp + rj);
-                            cbv.x = cp[0]; cbv.y = cp[1];
-                            }
-                        }
-                    }
-                    asm volatile("" : "+v"(vb.x), "+v"(vb.y));   // (consume the old prefetch before the next one is issued: the memory counter is in-order)
-                    if (!pool64) if (run) {                       // for the step after this one, whichever way it goes (pool64: wave-uniform)
-                        if constexpr (TRACE) {   // (32-bit offsets from the pool's base: see above)
-                            const glb_cu32_ptr a = (glb_cu32_ptr)(pool_g + (unsigned long long)(qo32 + (si + l8))), b = (glb_cu32_ptr)(pool_g + (unsigned long long)(ro32 + (sj + l8)));
-                            const glb_cu32_ptr cq = (glb_cu32_ptr)(pool_g + (unsigned long long)(qo32 + si) + MB), cr = (glb_cu32_ptr)(pool_g + (unsigned long long)(ro32 + sj) + MB);
-                            pf_qv.x = a[0]; pf_qv.y = a[1]; pf_rv.x = b[0]; pf_rv.y = b[1];
-                            pf_qc.x = cq[0]; pf_qc.y = cq[1]; pf_rc.x = cr[0]; pf_rc.y = cr[1];
-                        } else {
+                uint2 vb = right ? pf_qv : pf_rv, cbv = {0, 0};
+                if constexpr (TRACE) cbv = right ? pf_rc : pf_qc;   // (score only: behind the first pair of loads, see there)
+                asm volatile("" : "+v"(vb.x), "+v"(vb.y));   // (consume the old prefetch before the next one is issued: the memory counter is in-order)
+                {   // for the step after this one, whichever way it goes
+                    if constexpr (TRACE && P64) {   // (64-bit offsets: right whatever the pool's size)
+                        const unsigned long long qo = (unsigned long long)(uint32_t)cA.x | ((unsigned long long)(uint32_t)cA.y << 32), ro = (unsigned long long)(uint32_t)cA.z | ((unsigned long long)(uint32_t)cA.w << 32);
+                        const glb_cu32_ptr a = (glb_cu32_ptr)(pool_g + (qo + (si + l8))), b = (glb_cu32_ptr)(pool_g + (ro + (sj + l8)));
+                        const glb_cu32_ptr cq = (glb_cu32_ptr)(pool_g + (qo + si) + MB), cr = (glb_cu32_ptr)(pool_g + (ro + sj) + MB);
+                        pf_qv.x = a[0]; pf_qv.y = a[1]; pf_rv.x = b[0]; pf_rv.y = b[1];
+                        pf_qc.x = cq[0]; pf_qc.y = cq[1]; pf_rc.x = cr[0]; pf_rc.y = cr[1];
+                    } else if constexpr (TRACE) {   // (32-bit offsets from the pool's base: see above)
+                        const glb_cu32_ptr a = (glb_cu32_ptr)(pool_g + (unsigned long long)(qo32 + (si + l8))), b = (glb_cu32_ptr)(pool_g + (unsigned long long)(ro32 + (sj + l8)));
+                        const glb_cu32_ptr cq = (glb_cu32_ptr)(pool_g + (unsigned long long)(qo32 + si) + MB), cr = (glb_cu32_ptr)(pool_g + (unsigned long long)(ro32 + sj) + MB);
+                        pf_qv.x = a[0]; pf_qv.y = a[1]; pf_rv.x = b[0]; pf_rv.y = b[1];
+                        pf_qc.x = cq[0]; pf_qc.y = cq[1]; pf_rc.x = cr[0]; pf_rc.y = cr[1];
+                    } else {
+                        // (score only: a step stores nothing, so behind its four loads nothing else is outstanding and a wait for the last of them
+                        // would be a draining one. The loads go out as two pairs, each behind the wait for its own registers' bytes of the step
+                        // before: either wait leaves the other pair -- issued a whole step or a few instructions ago -- in flight, vmcnt(2))
                         const uint32_t* a = (const uint32_t*)(qp + (si + l8)); const uint32_t* b = (const uint32_t*)(rp + (sj + l8));
                         const uint32_t* cq = (const uint32_t*)(qp + si + MB); const uint32_t* cr = (const uint32_t*)(rp + sj + MB);
                         pf_qv.x = a[0]; pf_qv.y = a[1]; pf_rv.x = b[0]; pf_rv.y = b[1];
+                        // (the columns' old bytes are consumed behind the first pair's issue and in front of the second's: no memory operation
+                        // moves across this statement)
+                        asm volatile("" : "+v"(pf_qc.x), "+v"(pf_qc.y), "+v"(pf_rc.x), "+v"(pf_rc.y) :: "memory");
+                        cbv = right ? pf_rc : pf_qc;
                         pf_qc.x = cq[0]; pf_qc.y = cq[1]; pf_rc.x = cr[0]; pf_rc.y = cr[1];
-                        }
-                        pf_ok = true;
                     }
                 }
-                uint32_t* tw = nullptr;
                 if (TRACE) {
                     // (the slot's base address comes from LDS in every step instead of living in a register pair across the loop: with the pair
                     // the allocator spilled it and reloaded it before the stores, behind every outstanding memory operation)
                     // (as pointers to global memory: an address that comes out of LDS would otherwise be stored through as a flat one)
-                    typedef __attribute__((address_space(1))) uint32_t* glb_u32_ptr;
-                    tw = (uint32_t*)(glb_u32_ptr)((unsigned long long)(uint32_t)cC.x | ((unsigned long long)(uint32_t)cC.y << 32)) + (trace_top + l8);
-                    if (run && l == 0) {   // add_block(i, j, width, height, right) in matrix orientation (scan_block.rs:154,204)
+                    tw = (glb_u32_ptr)((unsigned long long)(uint32_t)cC.x | ((unsigned long long)(uint32_t)cC.y << 32)) + (trace_top + l8);
+                    {   // add_block(i, j, width, height, right) in matrix orientation (scan_block.rs:154,204): by every lane of the slot, the same bytes
                         // (the record's 16 bytes as one store; rows and columns are one select between two constants)
                         static_assert(sizeof(BlockRec) == 16, "a record as four words");
                         const uint32_t hw = right ? ((uint32_t)MB | ((uint32_t)STEP << 16)) : ((uint32_t)STEP | ((uint32_t)MB << 16));   // h = rows, w = columns
@@ -859,11 +922,8 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
                     }
                 }
                 MultiOut o;
-                int zw[2] = {0, 0};
-                multi_rect<KIND, TRACE, SPM, SL>(smem, fq, mc, l, A_d, A_c, P_d, P_r, vb, cbv.x, cbv.y, corner, off_add, tw, run, o, SPM ? splat(sat16(ZERO - off_n)) : 0,
+                multi_rect<KIND, TRACE, SPM, SL>(smem, fq, mc, l, A_d, A_c, P_d, P_r, vb, cbv.x, cbv.y, corner, off_add, tacc, o, (int)lid, SPM ? splat(sat16(ZERO - off_n)) : 0,
                                              SPM == 2 && right && ri == 0u && l == 0, zw);
-                if (TRACE && SPM == 1 && run) *(int2*)(tw - 8 * l + 128 + 2 * l) = int2{zw[0], zw[1]};   // the rectangle's zero mask behind its 128 trace words
-
                 // ---- what does the step call for? (scan_block.rs:332-558; nothing is committed yet)
                 const int right_max = right ? o.act_max8 : o.pas_max8, down_max = right ? o.pas_max8 : o.act_max8;
                 const int new_off_max = off_n + o.mx - ZERO;
@@ -872,8 +932,8 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
                 bool stop = q_out && r_out;                                                                   // end of the matrix
                 if (XDROP) stop = stop || (!improve && new_off_max < best_max - x_drop && x_iter >= 1);      // X-drop termination
                 stop = stop || (!q_out && !r_out && 2 * MB <= max_size && new_y > MB / STEP - 1);        // grow
-                const bool commit = run && !stop;
-                leave = leave || (run && stop);   // rolled back: the pair's state is what was staged before this step
+                commit = live && !stop;   // (a dead slot commits nothing: its counts stay 0, and with them its addresses)
+                rolled = live && stop;    // rolled back: the pair's state is what was staged before this step
                 {
                     // Straight-line selects, no branch (round 4): as nested conditionals the compiler copied the sixteen border registers three
                     // times per step (before the commit branch, inside it, and for the exchange: ~64 moves of 1156 instructions).
@@ -901,11 +961,15 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
 #ifdef BA_TIMING
                 n_quad++;
 #endif
+                // may the slot take its next step? (a slot that was rolled back stands where it was eligible)
+                leave = rolled || (live && !eligible(si, sj, dir, nblocks, qlen, rlen, (uint32_t)cB.z));
             } while (!__any(leave));
-            // ---- every slot's state at the top of the loop to memory: the registers of the slots that took the step (the others'
-            // was staged before it)
+            if (commit) store_words();   // the last step of this visit: the words of the slots that took it
+            }
+            // ---- every slot's state at the top of the loop to memory: the registers of the slots that took the last step, or -- the loop ended at its
+            // top -- of every slot (a slot whose step was rolled back: its state was staged before the step)
             const uint32_t trace_top = tt0 + nblocks * MQ_TW;
-            if (live && !leave) stage((uint32_t)(uintptr_t)(lbuf + l * 16), (uint32_t)(uintptr_t)lsc, sel ^ 1u, si, sj, 0, trace_top, nblocks, dir, 0, 0);
+            if (live && !rolled) stage((uint32_t)(uintptr_t)(lbuf + l * 16), (uint32_t)(uintptr_t)lsc, sel ^ 1u, si, sj, 0, trace_top, nblocks, dir, 0, 0);
             lds_sync();
             if (live) {   // both buffers back to the arena (solo mode needs the LDS region, and reads a pair's state from the arena)
 #pragma unroll
@@ -921,10 +985,13 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
             if (live && l == 0) {
                 int* rc = (int*)(slot_mem + 2 * BUFA);
                 // (the steps taken here are not counted in a register: every one moved the block by STEP in one direction)
-                const uint32_t nsteps = (uint32_t)mq_load((const char*)(rc + MR_NSTEPS)) + ((si + sj) - (uint32_t)mq_load((const char*)(rc + MR_SI)) - (uint32_t)mq_load((const char*)(rc + MR_SJ))) / (uint32_t)STEP;
+                const uint32_t taken = ((si + sj) - (uint32_t)mq_load((const char*)(rc + MR_SI)) - (uint32_t)mq_load((const char*)(rc + MR_SJ))) / (uint32_t)STEP;
+                const uint32_t nsteps = (uint32_t)mq_load((const char*)(rc + MR_NSTEPS)) + taken;
                 rc[MR_SI] = (int)si; rc[MR_SJ] = (int)sj; rc[MR_DIR] = dir; rc[MR_PREV_DIR] = prev_dir; rc[MR_OFF] = off; rc[MR_OFF_MAX] = off_max; rc[MR_BEST_MAX] = best_max;
                 rc[MR_Y_DROP] = (int)y_drop; rc[MR_X_ITER] = x_iter; rc[MR_D_CORNER] = D_corner; rc[MR_NSTEPS] = (int)nsteps; rc[MR_TRACE_TOP] = (int)trace_top;
                 rc[MR_NBLOCKS] = (int)nblocks; rc[MR_SEL] = (int)sel;
+                // development (F_COUNT_STEPS, the tests of the loop of steps): the steps this slot took in the loop, by the kernel form that took them
+                if (bp.flags & F_COUNT_STEPS) atomicAdd(bp.prof + (P64 ? 49 : 48), (unsigned long long)taken);
             }
             const unsigned long long lm = __ballot(leave && l == 0);
             pend_m = 0;
@@ -967,6 +1034,16 @@ __global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const
         if (bp.prof && is_lane(0)) atomicMax(bp.prof + 41, (unsigned long long)__builtin_amdgcn_s_memrealtime());
 #endif
     }
+}
+
+template <int PMAX, int KIND, bool TRACE, bool XDROP, int SPM = 0, int MBP = 128, int WPW = WAVES_PER_WG, int EU = MQ_WAVES_EU>
+__global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi(const BatchParams bp) {
+    multi_body<PMAX, KIND, TRACE, XDROP, SPM, MBP, WPW, EU, false>(bp);
+}
+// ... for batches with F_POOL64 (traced batches only: the score-only kernels keep 64-bit pointers in registers)
+template <int PMAX, int KIND, bool XDROP, int SPM = 0, int MBP = 128, int WPW = WAVES_PER_WG, int EU = MQ_WAVES_EU>
+__global__ void __launch_bounds__(WPW * 64, (PMAX >= 16 ? 2 : EU)) k_multi_p64(const BatchParams bp) {
+    multi_body<PMAX, KIND, true, XDROP, SPM, MBP, WPW, EU, true>(bp);
 }
 
 #undef don_final

@@ -11,7 +11,8 @@ constexpr int DIR_RIGHT = 0, DIR_DOWN = 1, DIR_GROW = 2;
 
 enum : uint32_t {
     F_TRACE = 1u << 0, F_XDROP = 1u << 1, F_LOCAL = 1u << 2, F_FQS = 1u << 3, F_FQE = 1u << 4, F_CIGAR_EQ = 1u << 5,
-    F_POOL64 = 1u << 15,   // the sequence pool (+ two blocks + 8 bytes) does not fit in 32 bits, or BA_POOL64 in the development library: k_multi's traced slots fetch their sequence bytes by 64-bit offset (ba_multi.hpp)
+    F_POOL64 = 1u << 15,   // the sequence pool (+ two blocks + 8 bytes) does not fit in 32 bits, or BA_POOL64 in the development library: the host launches k_multi's traced batches as k_multi_p64, whose slots prefetch their sequence bytes by 64-bit offset (ba_multi.hpp; the kernels do not read the flag)
+    F_COUNT_STEPS = 1u << 16,   // development library, BA_COUNT_STEPS: k_multi adds the steps its slots take in the loop of steps to prof[48] (k_multi_p64: prof[49]), once per visit of the loop (tests/test_gpu_step_loop_waits.py)
     F_PAD_NEG = 1u << 14   // every matrix entry of the padding byte's row and column is negative (set by the host, ba_host.cpp pad_negative): the end clip of ba_driver.hpp run()
 };
 enum : uint32_t { ST_OK = 0, ST_TRACE_OVERFLOW = 1, ST_BLOCKS_OVERFLOW = 2, ST_CIGAR_OVERFLOW = 4, ST_TRACEBACK_LOST = 8, ST_WATCHDOG = 16, ST_SLOT_TIMEOUT = 32, ST_MODE = 64,

@@ -21,19 +21,26 @@ def loop_of(text, pat):
         elif cur and l.strip().startswith('v_'):
             cur[2] += 1
     big = max(blocks, key=lambda b: b[2])
-    hdr = re.search(r'Header=(BB\d+_\d+)', big[3]).group(1)
+    m = re.search(r'Header=(BB\d+_\d+)', big[3])
+    hdr = m.group(1) if m else big[0][2:]   # (no Header= in its comment: the block is its loop's header itself)
     start = next(i for i, l in enumerate(L) if re.match(r'^\.L%s:' % hdr, l))
-    ins = []
+    ins = []; inner = []   # inner: where the loop's labelled blocks behind the header start, as indices into ins
     for i in range(start, len(L)):
         l = L[i]
         m = re.match(r'^(\.LBB\d+_\d+):(.*)', l)
         if m and ('Header=%s' % hdr) not in m.group(2) and i > start:
             break
+        if m and i > start:
+            inner.append(len(ins))
         t2 = l.strip()
         if not t2 or t2.startswith(';') or t2.startswith('.'):
             continue
         ins.append(t2)
-    return ins, hdr, big[:3]
+    # (the loop ends at its last branch back to the header: a block that follows it without a label of its own is not the loop's)
+    last = max((k for k, t2 in enumerate(ins) if re.match(r'^s_c?branch\S*\s+\.L%s$' % hdr, t2)), default=len(ins) - 1)
+    # (... and a block of the loop laid out behind that branch would be cut off with it: there is none)
+    assert all(k <= last for k in inner), ('a block of the loop at %s lies behind its last branch back' % hdr, inner, last)
+    return ins[:last + 1], hdr, big[:3]
 
 
 def main():
