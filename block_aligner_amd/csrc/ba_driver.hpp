@@ -211,6 +211,9 @@ __device__ __forceinline__ uint32_t walk_wave(const BlockRec* __restrict__ block
                                               uint32_t* __restrict__ out, uint64_t out_lo, uint64_t out_hi, uint32_t* status,
                                               uint32_t* __restrict__ lds, uint32_t budget) {
     const uint32_t lane = (uint32_t)lane_id();
+    // the last 64 words of the region: the owner table of the diagonal pass (round 11); the trace words are staged in front of it
+    const uint32_t tbudget = budget - 64u;
+    uint32_t* const own = lds + tbudget;
     uint32_t lutv0, lutv1;
     {
         const Move a = tb_lut(false, lane & 3, (lane >> 2) & 1, (lane >> 4) & 3), b = tb_lut(true, lane & 3, (lane >> 2) & 1, (lane >> 4) & 3);
@@ -244,9 +247,9 @@ __device__ __forceinline__ uint32_t walk_wave(const BlockRec* __restrict__ block
         if (lane < nvalid) rec = *(const uint4*)(blocks + (bidx - 1u - lane));
         const bool untr = rec.w & 0x40000000u;
         const uint32_t words = untr ? 0u : (rec.z & 0xffffu) * (rec.z >> 16) / 8u;
-        const uint32_t tb = rec.w & 0x3fffffffu;
+        const uint32_t tb = rec.w & 0x3fffffffu, rbi = rec.x & 0x7fffffffu;
         uint32_t toff = wave_excl_sum(lane < nvalid ? words : 0u, lane);
-        const uint32_t nfit = (uint32_t)__popcll(__ballot(lane < nvalid && toff + words <= budget));
+        const uint32_t nfit = (uint32_t)__popcll(__ballot(lane < nvalid && toff + words <= tbudget));
         // (a stack's rectangles are stacked: record k's words end where record k - 1's begin -- then one flat copy)
         const uint32_t tb_up = (uint32_t)__shfl_up((int)tb, 1, 64);
         const bool flat = nfit > 1 && !__any(lane > 0 && lane < nfit && tb + words != tb_up);
@@ -269,7 +272,7 @@ __device__ __forceinline__ uint32_t walk_wave(const BlockRec* __restrict__ block
         const uint32_t ntake = direct ? 1u : nfit;
         auto walk_rects = [&](auto direct_c) {
         constexpr bool DIRECT = decltype(direct_c)::value;
-        uint32_t cur = 0;
+        uint32_t cur = 0, skip = 0;   // skip: the next cells are known not to start a run (the pass that ended in front of them saw them)
         while (cur < ntake && ok && (i > 0 || j > 0)) {
             const uint32_t rx = (uint32_t)__builtin_amdgcn_readlane((int)rec.x, (int)cur), bj = (uint32_t)__builtin_amdgcn_readlane((int)rec.y, (int)cur);
             const uint32_t bi = rx & 0x7fffffffu;
@@ -293,22 +296,59 @@ __device__ __forceinline__ uint32_t walk_wave(const BlockRec* __restrict__ block
                 // lanes that agree is the length of the run; with CIGAR_EQ the lanes also compare their cells' bytes and the run is cut into = / X
                 // runs from the two masks. (A cell on wave-uniform values costs ~700 cycles -- ~75 scalar instructions at one issue per ~5 cycles and
                 // their branches --, the pass about as much as one cell.)
-                if (table == 0u && i > 0u && j > 0u && min(v, w) >= 1u) {
-                    const uint32_t lim = min(min(v, w), min(i, j) - 1u);   // cells 0 .. lim: inside the rectangle, and a diagonal move from them stays inside the matrix
-                    const bool valid = lane <= lim;
-                    const uint32_t vv = v - lane, ww = w - lane;
-                    uint32_t widx_k, sh_k;
-                    if (l2) { const uint32_t cb = slot_cell_byte<RO>(vv & 7u); widx_k = (vv >> 3) * 8u + (ww >> 1) * 2u + (cb >> 2); sh_k = (cb & 3u) * 8u + (ww & 1u) * 4u; }
-                    else { widx_k = ((ww >> 2) * nch + (vv >> 7)) * nl + ((vv & 127u) >> 1); sh_k = (vv & 1u) * 16u + (ww & 3u) * 4u; }
-                    uint32_t word_k = 0;
-                    if (valid) { if constexpr (DIRECT) word_k = trace[off + widx_k]; else word_k = lds[off + widx_k]; }
-                    const unsigned long long cm = __ballot(valid && ((word_k >> sh_k) & 3u) == 3u);
+                if (table == 0u && skip == 0u && i > 0u && j > 0u && (!DIRECT || min(v, w) >= 1u)) {
+                    uint32_t word_k = 0, own_k = cur;
+                    unsigned long long cm, vm;
+                    if constexpr (DIRECT) {   // a rectangle walked out of global memory: the run stays inside it
+                        const uint32_t lim = min(min(v, w), min(i, j) - 1u);   // cells 0 .. lim: inside the rectangle, and a diagonal move from them stays inside the matrix
+                        const bool valid = lane <= lim;
+                        const uint32_t vv = v - lane, ww = w - lane;
+                        uint32_t widx_k, sh_k;
+                        if (l2) { const uint32_t cb = slot_cell_byte<RO>(vv & 7u); widx_k = (vv >> 3) * 8u + (ww >> 1) * 2u + (cb >> 2); sh_k = (cb & 3u) * 8u + (ww & 1u) * 4u; }
+                        else { widx_k = ((ww >> 2) * nch + (vv >> 7)) * nl + ((vv & 127u) >> 1); sh_k = (vv & 1u) * 16u + (ww & 3u) * 4u; }
+                        if (valid) word_k = trace[off + widx_k];
+                        vm = __ballot(valid); cm = __ballot(valid && ((word_k >> sh_k) & 3u) == 3u);
+                    } else {
+                        // ---- round 11: the run goes on across the staged rectangles. The owner of lane k's cell is the walk's own choice, the first
+                        // record a >= cur that holds it: K_a = min(i - bi_a, j - bj_a) >= k (a record that does not hold cell k - 1 does not hold cell k,
+                        // and cur only advances). Lane a holds record a: a running maximum of K from cur on says which k record a is the first to reach,
+                        // and lane a writes its index there (own[]; cells 0 .. K_cur are cur's and need no entry). Lane k then takes its owner's
+                        // record by ds_bpermute and reads its cell in that rectangle's layout. An untraced owner, a cell that no staged record holds and
+                        // the matrix edge end the run: the code below meets such a cell as it always did.
+                        const uint32_t kcur = min(min(v, w), 63u);
+                        const int K = lane > cur && lane < ntake ? min(min((int)(i - rbi), (int)(j - rec.y)), 63) : (lane == cur ? (int)kcur : -1);
+                        const int pm = wave_prefix_max(K);
+                        const int prev = __builtin_amdgcn_update_dpp(-1, pm, 0x138, 0xf, 0xf, false);   // wave_shr:1 (lane 0 keeps -1)
+                        const uint32_t kmax = (uint32_t)__builtin_amdgcn_readlane(pm, 63);
+                        for (int kk = lane == cur ? pm + 1 : prev + 1; __any(kk <= pm); kk++)
+                            if (kk <= pm) own[kk] = lane;
+                        asm volatile("" ::: "memory");
+                        const bool mine = lane <= min(kmax, min(i, j) - 1u);   // (a diagonal move from these cells stays inside the matrix)
+                        if (mine && lane > kcur) own_k = own[lane];
+                        const int oa = (int)(own_k << 2);
+                        const uint32_t ox = (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)rec.x), oy = (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)rec.y);
+                        const uint32_t oz = (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)rec.z), ow = (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)rec.w);
+                        const uint32_t ot = (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)toff);
+                        const bool valid = mine && !(ow & 0x40000000u);
+                        const bool oright = ow >> 31, ol2 = L2OK && (ox >> 31);
+                        const uint32_t oci = i - lane - (ox & 0x7fffffffu), ocj = j - lane - oy;
+                        const uint32_t vv = oright ? oci : ocj, ww = oright ? ocj : oci;
+                        const uint32_t oHv = oright ? (oz & 0xffffu) : (oz >> 16);
+                        const uint32_t onch = oHv > 128u ? oHv / 128u : 1u, onl = oHv > 128u ? 64u : oHv / 2u;
+                        uint32_t widx_k, sh_k;
+                        if (ol2) { const uint32_t cb = slot_cell_byte<RO>(vv & 7u); widx_k = (vv >> 3) * 8u + (ww >> 1) * 2u + (cb >> 2); sh_k = (cb & 3u) * 8u + (ww & 1u) * 4u; }
+                        else { widx_k = ((ww >> 2) * onch + (vv >> 7)) * onl + ((vv & 127u) >> 1); sh_k = (vv & 1u) * 16u + (ww & 3u) * 4u; }
+                        if (valid) word_k = lds[ot + widx_k];
+                        vm = __ballot(valid); cm = __ballot(valid && ((word_k >> sh_k) & 3u) == 3u);
+                    }
                     uint32_t n = cm == ~0ull ? 64u : (uint32_t)__builtin_ctzll(~cm);
                     if (eq && n >= 2u) {   // the cells' bytes out of the sequence windows (256 bytes each, four per lane)
                         if (i < qw0) load_q();
                         if (j < rw0) load_r();
                         n = min(n, min(i - qw0, j - rw0) + 1u);
                     }
+                    // (the cell behind the run, when a lane looked at it and it is no plain diagonal move, goes to the code below without another pass)
+                    const uint32_t known = n < 64u ? (uint32_t)(((vm & ~cm) >> n) & 1ull) : 0u;
                     if (n >= 2u) {
                         bool fits = true;
                         if (!eq) {
@@ -330,13 +370,19 @@ __device__ __forceinline__ uint32_t walk_wave(const BlockRec* __restrict__ block
                             }
                         }
                         if (!fits) { st = ST_CIGAR_OVERFLOW; ok = false; break; }
-                        i -= n; j -= n;   // (the state stays D)
+                        i -= n; j -= n; skip = known;   // (the state stays D)
+                        if constexpr (!DIRECT) {   // the owner of the run's last cell is the current rectangle now
+                            const uint32_t last = (uint32_t)__builtin_amdgcn_readlane((int)own_k, (int)(n - 1u));
+                            if (last != cur) { cur = last; break; }
+                        }
                         continue;
                     }
                     word = (uint32_t)__builtin_amdgcn_readlane((int)word_k, 0);   // (lane 0 looked at the current cell)
+                    skip = n + known;
                 } else {
                 if constexpr (DIRECT) word = (uint32_t)uni((int)trace[off + widx]); else word = (uint32_t)uni((int)lds[off + widx]);
                 }
+                if (skip) skip--;
                 const uint32_t nib = ((word >> sh) ^ 15u) & 15u;                                // all four bits are stored as "differs"
                 table = tb_resolve(right, table, nib);
                 const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)lutr, (int)((table << 4) | nib));

@@ -789,6 +789,8 @@ static int batch_plan(BaBatch* b, size_t n, uint64_t fixed_bytes, uint64_t maxle
         // least 2 n_fill_waves hand-offs pending, more than the n_fill_waves reserved ones: some of them are the dedicated lanes', which are
         // resident and walking; and a wave that waits long walks a pending hand-off itself, traceback_help_one. Enforced below: spw >= 6.)
         // (round 6, the cheaper lane walk: one per fill wave at every batch size -- 12.5 k pairs 34.2 -> 33.6 ms, 25 k 49.4 -> 49.2, 100 k 158.3 -> 157.9)
+        // (round 11, the whole-wave walk's runs cross rectangles: one per fill wave stays best -- same box, BA_TB_RESERVE at 1x / 1.5x / 2x the fill
+        // waves: 100 k pairs 131.7 / 132.5 / 134.3 ms, 25 k pairs 41.1 .. 41.7 / 42.2 / 43.0 ms; profiles/r11_walk_runs.md)
         if (b->multi && (n >= 5ull * b->n_fill_waves || !special_of(mode)) && spw >= mslots + 2) b->tb_reserve = b->n_fill_waves;
         // with fewer than three trace slots per wave a fill wave soon waits for the walk of its previous pair: leave
         // less of the batch to walkers that only exist once the first wave has run out of pairs
