@@ -376,6 +376,7 @@ struct ExtImages {
     const uint8_t* flags = nullptr;
     const uint32_t* seed_of = nullptr;
     float* pack_ms = nullptr;   // (optional) device time of the packer
+    const char* what = "seed";  // what seed_of counts, for the message about a byte outside the alphabet (chain batches: "chain")
 };
 struct Packed {   // host-side packing of a set of pairs: padded images + the per-pair arrays the kernels read
     std::vector<uint64_t> qo, ro, cig_off;
@@ -849,7 +850,7 @@ static int upload_images(BaBatch* b, const Packed& P, size_t n) {
         if (P.ext->pack_ms) HIP_TRY(hipEventElapsedTime(P.ext->pack_ms, b->ev0, b->ev1));
         unsigned long long e = 0;
         HIP_TRY(hipMemcpy(&e, err.p, 8, hipMemcpyDeviceToHost));
-        if (e != ~0ull) return fail("seed %u: byte 0x%02x is outside the matrix alphabet", P.ext->seed_of[P.who((size_t)(e >> 8))], (unsigned)(e & 0xff));
+        if (e != ~0ull) return fail("%s %u: byte 0x%02x is outside the matrix alphabet", P.ext->what, P.ext->seed_of[P.who((size_t)(e >> 8))], (unsigned)(e & 0xff));
         return 0;
     }
     DevBuf raw, raw_q, raw_r, err;
@@ -1685,6 +1686,249 @@ static int ext_load(BaExtendBatch* e, const ExtSet& S, size_t n, const void* mat
     e->n = (uint32_t)n; e->n_sides = (uint32_t)n_sides;
     e->h_t_raw_q = S.t_raw_q; e->h_t_raw_r = S.t_raw_r; e->h_t_ql = S.t_ql; e->h_t_rl = S.t_rl; e->h_t_strand = S.t_strand;
     e->t_uploaded = false;
+    return 0;
+}
+
+// ------------------------------------------------------------------ anchor-chain batches (ba_chain_batch_*)
+// One chain of colinear anchors = one result: X-drop extension leftwards from the first anchor and rightwards from the last one, as for a
+// seed; a global alignment of the slices between consecutive anchors; the anchors themselves ungapped. The ends of every chain are the pairs
+// of ONE X-drop batch, the gaps with two non-empty slices the pairs of ONE global batch (batch_build over device-cut images, as the sides of
+// an extension batch: the caller's bytes are uploaded once); the segmented splice (ba_chain.hip) scores the anchors, makes the runs of the
+// gaps with one empty slice and joins everything per chain on the device, in the caller's order.
+struct ChainPieceSet {   // the pairs of one inner batch (host addresses into the caller's pool; nothing is copied)
+    std::vector<const uint8_t*> src;   // 2 per piece (query, reference): first byte of the slice
+    std::vector<uint32_t> len;         // 2 per piece
+    std::vector<uint8_t> flags;        // 2 per piece: ba::IMG_*
+    std::vector<uint32_t> chain_of;    // per piece
+    size_t size() const { return chain_of.size(); }
+    uint32_t add(size_t c, const uint8_t* qs, uint64_t ql, uint8_t qf, const uint8_t* rs, uint64_t rl, uint8_t rf) {
+        chain_of.push_back((uint32_t)c);
+        src.push_back(qs); len.push_back((uint32_t)ql); flags.push_back(qf);
+        src.push_back(rs); len.push_back((uint32_t)rl); flags.push_back(rf);
+        return (uint32_t)chain_of.size() - 1;
+    }
+};
+struct ChainSet {   // a set of chains cut into pieces
+    const uint8_t* lo = nullptr; uint64_t bytes = 0;   // extent of the chains' sequences in the caller's pool
+    ChainPieceSet ends, gaps;
+    std::vector<uint32_t> end_side;                    // 2 per chain (left, right): index of the end in `ends`, or ba::CHAIN_NO_PIECE
+    std::vector<uint32_t> gap_side;                    // per anchor: index in `gaps` of the gap behind it, or ba::CHAIN_NO_PIECE
+    std::vector<uint64_t> a_raw_q, a_raw_r, a_img_q, a_img_r;   // the anchors' own images: source offsets in the upload, offsets in the anchor pool
+    std::vector<uint8_t> a_flags;                      // 2 per anchor
+    uint64_t anchor_bytes = 0, n_anchors = 0;
+};
+static int chain_check_params(int kind, Gaps gaps, SizeRange size, int32_t x_drop, uint32_t mode) {   // ba_chain_batch_create's own arguments
+    if (kind == BA_KIND_PROFILE_) return fail("chain batches take a sequence matrix: profile batches cannot be chained");
+    if (kind < 0 || kind > 2) return fail("unknown matrix kind %d", kind);
+    if (!(mode & BA_X_DROP)) return fail("chain batches need BA_X_DROP: the ends of a chain end where their score drops");
+    if (mode & (BA_LOCAL_START | BA_FREE_QUERY_START_GAPS | BA_FREE_QUERY_END_GAPS))
+        return fail("chain batches take BA_X_DROP, BA_TRACE and BA_CIGAR_EQ only: LOCAL_START and FREE_QUERY_* are rejected");
+    const size_t min_size = size.min < 16 ? 16 : size.min, max_size = size.max < 16 ? 16 : size.max;   // (as batch_build)
+    std::string why;
+    if (check_align_params(false, gaps, min_size, max_size, x_drop, mode, &why)) return fail("%s", why.c_str());
+    if (min_size > max_size) return fail("min block size exceeds max block size");
+    return 0;
+}
+// Check a set of chains (the mode and the matrix kind are checked already) and cut it into ends, gaps and anchors.
+static int chain_plan(int kind, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len,
+                      const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor, const uint32_t* anchor_len, const uint8_t* strand,
+                      size_t n, ChainSet& S) {
+    if (!pool || !q_off || !q_len || !r_off || !r_len || !anchor_first || !q_anchor || !r_anchor || !anchor_len) return fail("null argument");
+    if (n == 0 || n > (1u << 28)) return fail("a chain batch must hold between 1 and 2^28 chains");
+    if (anchor_first[0] != 0) return fail("anchor_first must start at 0 (chain 0 starts at %llu)", (unsigned long long)anchor_first[0]);
+    for (size_t c = 0; c < n; c++) {
+        if (anchor_first[c + 1] < anchor_first[c])
+            return fail("chain %zu: anchor_first must not decrease (%llu after %llu)", c, (unsigned long long)anchor_first[c + 1], (unsigned long long)anchor_first[c]);
+        if (anchor_first[c + 1] == anchor_first[c]) return fail("chain %zu: a chain must hold at least one anchor", c);
+    }
+    const uint64_t na = anchor_first[n];
+    if (na > (1u << 28)) return fail("a chain batch must hold at most 2^28 anchors");   // (k_pack_images: two workgroups per anchor)
+    S = ChainSet();
+    S.n_anchors = na;
+    S.end_side.resize(2 * n); S.gap_side.assign(na, ba::CHAIN_NO_PIECE);
+    S.a_raw_q.resize(na); S.a_raw_r.resize(na); S.a_img_q.resize(na); S.a_img_r.resize(na); S.a_flags.resize(2 * na);
+    const uint8_t* hi = nullptr;
+    for (size_t c = 0; c < n; c++) {
+        const uint64_t Q = q_len[c], R = r_len[c];
+        const uint8_t st = strand ? strand[c] : 0;
+        if (st > 1) return fail("chain %zu: strand must be 0 or 1", c);
+        if (st && kind != BA_KIND_NUC) return fail("chain %zu: strand needs a NucMatrix batch (reverse complement is nucleotide-only)", c);
+        const uint8_t* q = pool + q_off[c]; const uint8_t* r = pool + r_off[c];
+        for (const uint8_t* x : {q, r}) if (!S.lo || x < S.lo) S.lo = x;
+        if (!hi || q + Q > hi) hi = q + Q;
+        if (r + R > hi) hi = r + R;
+        // (minus strand: q is the reverse complement of the caller's bytes, and a slice [a, b) of it the reversed, complemented slice
+        // [Q - b, Q - a) of those bytes)
+        const uint8_t fwd = st ? (ba::IMG_REVERSE | ba::IMG_COMPLEMENT) : 0;
+        auto q_slice = [&](uint64_t a, uint64_t b) { return st ? q + (Q - b) : q + a; };
+        const uint64_t a0 = anchor_first[c], K = anchor_first[c + 1] - a0;
+        for (uint64_t k = 0; k < K; k++) {
+            const uint64_t a = a0 + k, s = q_anchor[a], t = r_anchor[a], L = anchor_len[a];
+            if (L == 0) return fail("chain %zu, anchor %llu: anchor_len must be at least 1", c, (unsigned long long)k);
+            if (s + L > Q || t + L > R)
+                return fail("chain %zu, anchor %llu: the anchor (query %llu + %llu, reference %llu + %llu) runs past the end of its sequences (%llu, %llu)", c,
+                            (unsigned long long)k, (unsigned long long)s, (unsigned long long)L, (unsigned long long)t, (unsigned long long)L,
+                            (unsigned long long)Q, (unsigned long long)R);
+            if (k) {
+                const uint64_t ps = (uint64_t)q_anchor[a - 1] + anchor_len[a - 1], pt = (uint64_t)r_anchor[a - 1] + anchor_len[a - 1];
+                if (s < ps || t < pt)
+                    return fail("chain %zu, anchor %llu: the anchor overlaps or precedes anchor %llu on the %s (it starts at %llu, anchor %llu ends at %llu)", c,
+                                (unsigned long long)k, (unsigned long long)(k - 1), s < ps ? "query" : "reference", (unsigned long long)(s < ps ? s : t),
+                                (unsigned long long)(k - 1), (unsigned long long)(s < ps ? ps : pt));
+                if (s > ps && t > pt)   // both slices non-empty: a pair of the global batch (one empty: a single I or D run, made by the splice)
+                    S.gap_side[a - 1] = S.gaps.add(c, q_slice(ps, s), s - ps, fwd, r + pt, t - pt, 0);
+            }
+            S.a_raw_q[a] = (uint64_t)(q_slice(s, s + L) - pool); S.a_raw_r[a] = (uint64_t)(r + t - pool);   // (made relative to lo below)
+            S.a_flags[2 * a] = fwd; S.a_flags[2 * a + 1] = 0;
+            S.a_img_q[a] = S.anchor_bytes; S.anchor_bytes += (1 + L + 3) & ~(uint64_t)3;
+            S.a_img_r[a] = S.anchor_bytes; S.anchor_bytes += (1 + L + 3) & ~(uint64_t)3;
+        }
+        // the ends: the two sides of a seed (ext_plan), left of the first anchor and right of the last one
+        const uint64_t s = q_anchor[a0], t = r_anchor[a0], al = a0 + K - 1, eq = (uint64_t)q_anchor[al] + anchor_len[al], er = (uint64_t)r_anchor[al] + anchor_len[al];
+        S.end_side[2 * c] = (s && t) ? S.ends.add(c, st ? q + (Q - s) : q, s, st ? ba::IMG_COMPLEMENT : ba::IMG_REVERSE, r, t, ba::IMG_REVERSE) : ba::CHAIN_NO_PIECE;
+        S.end_side[2 * c + 1] = (Q - eq && R - er) ? S.ends.add(c, q_slice(eq, Q), Q - eq, fwd, r + er, R - er, 0) : ba::CHAIN_NO_PIECE;
+    }
+    const uint64_t base = (uint64_t)(S.lo - pool);
+    for (uint64_t a = 0; a < na; a++) { S.a_raw_q[a] -= base; S.a_raw_r[a] -= base; }
+    S.bytes = (uint64_t)(hi - S.lo);
+    if (S.ends.size() > 0x7fffffffu || S.gaps.size() > 0x7fffffffu) return fail("too many pieces");
+    return 0;
+}
+struct BaChainBatch {
+    int device = 0, kind = 0; uint32_t mode = 0;
+    int gap_open = 0, gap_extend = 0;
+    std::unique_ptr<BaBatch> ends, gaps;   // the X-drop batch of the ends, the global batch of the gaps; null if the batch was created without such pieces
+    uint32_t n = 0, n_anchors = 0, n_ends = 0, n_gaps = 0;
+    uint64_t cap_n = 0, cap_anchors = 0, cap_raw = 0, cap_anchor_bytes = 0, runs_cap = 0, total_runs = 0;
+    hipStream_t stream = nullptr; hipEvent_t ev[4] = {};
+    DevBuf raw, anchor_pool, anchor_q, anchor_r, anchor_raw_q, anchor_raw_r, anchor_flags, anchor_len, q_anchor, r_anchor, anchor_first, end_side, gap_side,
+           matrix, err;
+    DevBuf a_score, a_nrun, a_ops, a_flen, a_llen;
+    DevBuf score, left_score, right_score, q_start, r_start, q_end, r_end, cells, status, cigar_len, out_off, runs;
+    float ends_ms = 0, gaps_ms = 0, pack_ms = 0, splice_ms = 0;
+    bool ran = false;
+    static ba::ChainPieces pieces(const BaBatch* b) {
+        ba::ChainPieces pc{};
+        if (!b) return pc;
+        pc.score = b->score.as<int32_t>(); pc.qidx = b->qidx.as<uint32_t>(); pc.ridx = b->ridx.as<uint32_t>();
+        pc.cells = b->cells.as<unsigned long long>(); pc.status = b->status.as<uint32_t>(); pc.cig_len = b->cig_len.as<uint32_t>();
+        pc.cig_off = b->cig_off.as<uint64_t>(); pc.cig_ops = b->cig_ops.as<uint32_t>();
+        return pc;
+    }
+    ba::ChainParams params() const {
+        ba::ChainParams cp{};
+        cp.n = n; cp.n_anchors = n_anchors; cp.kind = seq_kind(kind); cp.flags = mode; cp.gap_open = gap_open; cp.gap_extend = gap_extend;
+        cp.matrix = matrix.as<int8_t>(); cp.anchor_first = anchor_first.as<uint64_t>();
+        cp.q_anchor = q_anchor.as<uint32_t>(); cp.r_anchor = r_anchor.as<uint32_t>(); cp.anchor_len = anchor_len.as<uint32_t>();
+        cp.anchor_pool = anchor_pool.as<uint8_t>(); cp.anchor_q = anchor_q.as<uint64_t>(); cp.anchor_r = anchor_r.as<uint64_t>();
+        cp.end_side = end_side.as<uint32_t>(); cp.gap_side = gap_side.as<uint32_t>();
+        cp.ends = pieces(n_ends ? ends.get() : nullptr); cp.gaps = pieces(n_gaps ? gaps.get() : nullptr);
+        cp.a_score = a_score.as<int32_t>(); cp.a_nrun = a_nrun.as<uint32_t>(); cp.a_ops = a_ops.as<uint32_t>();
+        cp.a_flen = a_flen.as<uint32_t>(); cp.a_llen = a_llen.as<uint32_t>();
+        cp.score = score.as<int32_t>(); cp.left_score = left_score.as<int32_t>(); cp.right_score = right_score.as<int32_t>();
+        cp.q_start = q_start.as<uint32_t>(); cp.r_start = r_start.as<uint32_t>(); cp.q_end = q_end.as<uint32_t>(); cp.r_end = r_end.as<uint32_t>();
+        cp.cells = cells.as<unsigned long long>(); cp.status = status.as<uint32_t>(); cp.cigar_len = cigar_len.as<uint32_t>();
+        cp.out_off = out_off.as<uint64_t>(); cp.runs = runs.as<uint32_t>();
+        return cp;
+    }
+    ~BaChainBatch() {
+        ends.reset(); gaps.reset();
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+// The pieces of one inner batch into it (built on create, reloaded after); `side`: the pieces' indices -> their positions in its device order.
+static int chain_load_pieces(BaChainBatch* e, std::unique_ptr<BaBatch>& inner, const ChainPieceSet& P, const uint8_t* lo, const void* matrix, Gaps gaps,
+                             SizeRange size, int32_t x_drop, uint32_t mode, bool create, std::vector<uint32_t>& side) {
+    const size_t np = P.size();
+    if (!np) return 0;
+    float ms = 0;
+    ExtImages X;
+    X.host_base = lo; X.dev_base = e->raw.as<uint8_t>(); X.flags = P.flags.data(); X.seed_of = P.chain_of.data(); X.pack_ms = &ms; X.what = "chain";
+    auto get = [&](size_t p, int w, const uint8_t** ptr, size_t* len) { *ptr = P.src[2 * p + w]; *len = P.len[2 * p + w]; };
+    if (create) {
+        inner.reset(batch_build(e->kind, matrix, gaps, size, x_drop, mode, np, false, get, NoProfiles(), &X));
+        if (!inner) return 1;
+    } else if (batch_reload(inner.get(), np, false, get, NoProfiles(), &X)) return 1;
+    e->pack_ms += ms;
+    if (!inner->h_order.empty()) {
+        std::vector<uint32_t> pos(np);
+        for (uint32_t d = 0; d < np; d++) pos[inner->h_order[d]] = d;
+        for (uint32_t& x : side) if (x != ba::CHAIN_NO_PIECE) x = pos[x];
+    }
+    return 0;
+}
+// Load a planned set into the batch: the caller's bytes once to the device, the ends and the gaps into their inner batches, the anchors'
+// own images. `create`: size every buffer for this set; otherwise the set must fit them.
+static int chain_load(BaChainBatch* e, const ChainSet& S, size_t n, const void* matrix, Gaps gaps, SizeRange size, int32_t x_drop,
+                      const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor, const uint32_t* anchor_len, bool create) {
+    const size_t na = S.n_anchors;
+    if (create) {
+        e->cap_n = n; e->cap_anchors = na; e->cap_raw = S.bytes; e->cap_anchor_bytes = S.anchor_bytes;
+        if (e->raw.alloc(S.bytes) || e->anchor_pool.alloc(S.anchor_bytes + 64) || e->err.alloc(8)) return 1;
+        DevBuf* per_chain4[] = {&e->score, &e->left_score, &e->right_score, &e->q_start, &e->r_start, &e->q_end, &e->r_end, &e->status, &e->cigar_len};
+        for (DevBuf* d : per_chain4) if (d->alloc(n * 4)) return 1;
+        DevBuf* per_anchor4[] = {&e->anchor_len, &e->q_anchor, &e->r_anchor, &e->gap_side, &e->a_score, &e->a_nrun, &e->a_ops, &e->a_flen, &e->a_llen};
+        for (DevBuf* d : per_anchor4) if (d->alloc(na * 4)) return 1;
+        if (e->anchor_q.alloc(na * 8) || e->anchor_r.alloc(na * 8) || e->anchor_raw_q.alloc(na * 8) || e->anchor_raw_r.alloc(na * 8) || e->anchor_flags.alloc(2 * na) ||
+            e->anchor_first.alloc((n + 1) * 8) || e->end_side.alloc(2 * n * 4) || e->cells.alloc(n * 8) || e->out_off.alloc((n + 1) * 8) || e->matrix.alloc(1024)) return 1;
+        int8_t tmp[1024] = {0};
+        if (e->kind == BA_KIND_BYTES) { const ByteMatrix* bm = (const ByteMatrix*)matrix; tmp[0] = bm->match_score; tmp[1] = bm->mismatch_score; }
+        else memcpy(tmp, matrix, e->kind == BA_KIND_AA ? 27 * 32 : 8 * 16);
+        HIP_TRY(hipMemcpy(e->matrix.p, tmp, 1024, hipMemcpyHostToDevice));
+    } else {
+        if (n > e->cap_n) return fail("reload: %zu chains exceed the batch's capacity of %llu", n, (unsigned long long)e->cap_n);
+        if (na > e->cap_anchors) return fail("reload: %zu anchors exceed the batch's capacity of %llu", na, (unsigned long long)e->cap_anchors);
+        if (S.bytes > e->cap_raw) return fail("reload: %llu sequence bytes exceed the batch's capacity of %llu", (unsigned long long)S.bytes, (unsigned long long)e->cap_raw);
+        if (S.anchor_bytes > e->cap_anchor_bytes) return fail("reload: the anchors (%llu image bytes) exceed the batch's capacity of %llu", (unsigned long long)S.anchor_bytes, (unsigned long long)e->cap_anchor_bytes);
+        if (S.ends.size() && !e->ends) return fail("reload: the set has ends to align, and the batch was created with none");
+        if (S.gaps.size() && !e->gaps) return fail("reload: the set has gaps to align, and the batch was created with none");
+    }
+    e->n = 0; e->ran = false; e->pack_ms = 0;   // (a failure from here on leaves no chains loaded)
+    HIP_TRY(hipMemcpy(e->raw.p, S.lo, S.bytes, hipMemcpyHostToDevice));
+    std::vector<uint32_t> end_side(S.end_side), gap_side(S.gap_side);
+    {
+        // both inner batches live together: the first one plans with half of the free memory (as the ranges of ba_sized_batch_create share it)
+        struct CapReset { ~CapReset() { g_mem_cap = ~0ull; } } cap_reset;
+        if (create && S.ends.size() && S.gaps.size()) {
+            size_t free_b = 0, total_b = 0;
+            (void)hipMemGetInfo(&free_b, &total_b);
+            g_mem_cap = std::max<uint64_t>((uint64_t)((double)free_b * 0.95 * 0.5), 3ull << 30);
+        }
+        if (chain_load_pieces(e, e->ends, S.ends, S.lo, matrix, gaps, size, x_drop, e->mode, create, end_side)) return 1;
+        g_mem_cap = ~0ull;
+        if (chain_load_pieces(e, e->gaps, S.gaps, S.lo, matrix, gaps, size, 0, e->mode & ~(uint32_t)BA_X_DROP, create, gap_side)) return 1;
+    }
+    HIP_TRY(hipMemcpy(e->end_side.p, end_side.data(), 2 * n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->gap_side.p, gap_side.data(), na * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->anchor_first.p, anchor_first, (n + 1) * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->q_anchor.p, q_anchor, na * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->r_anchor.p, r_anchor, na * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->anchor_len.p, anchor_len, na * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->anchor_q.p, S.a_img_q.data(), na * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->anchor_r.p, S.a_img_r.data(), na * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->anchor_raw_q.p, S.a_raw_q.data(), na * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->anchor_raw_r.p, S.a_raw_r.data(), na * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->anchor_flags.p, S.a_flags.data(), 2 * na, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(e->cigar_len.p, 0, n * 4));
+    HIP_TRY(hipMemset(e->err.p, 0xff, 8));
+    HIP_TRY(hipEventRecord(e->ev[0], e->stream));
+    HIP_TRY(ba_launch_pack_images(e->stream, seq_kind(e->kind), e->raw.as<uint8_t>(), e->anchor_raw_q.as<uint64_t>(), e->anchor_raw_r.as<uint64_t>(),
+                                  e->anchor_flags.as<uint8_t>(), e->anchor_q.as<uint64_t>(), e->anchor_len.as<uint32_t>(), e->anchor_r.as<uint64_t>(),
+                                  e->anchor_len.as<uint32_t>(), e->anchor_pool.as<uint8_t>(), 0, (uint32_t)na, e->err.as<unsigned long long>()));
+    HIP_TRY(hipEventRecord(e->ev[1], e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, e->ev[0], e->ev[1]));
+    e->pack_ms += ms;
+    unsigned long long err = 0;
+    HIP_TRY(hipMemcpy(&err, e->err.p, 8, hipMemcpyDeviceToHost));
+    if (err != ~0ull) {
+        const uint64_t a = err >> 8;
+        const size_t c = (size_t)(std::upper_bound(anchor_first, anchor_first + n + 1, a) - anchor_first) - 1;
+        return fail("chain %zu, anchor %llu: byte 0x%02x is outside the matrix alphabet", c, (unsigned long long)(a - anchor_first[c]), (unsigned)(err & 0xff));
+    }
+    e->n = (uint32_t)n; e->n_anchors = (uint32_t)na; e->n_ends = (uint32_t)S.ends.size(); e->n_gaps = (uint32_t)S.gaps.size();
     return 0;
 }
 
@@ -2648,6 +2892,98 @@ int ba_extend_batch_text(BaExtendBatch* e, uint32_t what, uint64_t* offsets, cha
     return text_kernels(e->text, e->device, e->stream, e->runs_done, tp, e->cap_n, nullptr, offsets, text, capacity);
 }
 void ba_extend_batch_destroy(BaExtendBatch* e) { delete e; }
+
+BaChainBatch* ba_chain_batch_create(int kind, const void* matrix, Gaps gaps, SizeRange size, int32_t x_drop, uint32_t mode, const uint8_t* pool,
+                                    const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len, const uint64_t* anchor_first,
+                                    const uint32_t* q_anchor, const uint32_t* r_anchor, const uint32_t* anchor_len, const uint8_t* strand, uintptr_t n_chains) {
+    ChainSet S;   // every argument is checked before the device is touched
+    if (!matrix) { fail("null argument"); return nullptr; }
+    if (chain_check_params(kind, gaps, size, x_drop, mode) ||
+        chain_plan(kind, pool, q_off, q_len, r_off, r_len, anchor_first, q_anchor, r_anchor, anchor_len, strand, n_chains, S)) return nullptr;
+    if (ensure_device()) return nullptr;
+    std::unique_ptr<BaChainBatch> e(new BaChainBatch);
+    e->device = g_device; e->kind = kind; e->mode = mode; e->gap_open = gaps.open; e->gap_extend = gaps.extend;
+    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { fail("hipStreamCreate failed"); return nullptr; }
+    for (hipEvent_t& ev : e->ev) if (hipEventCreate(&ev) != hipSuccess) { fail("hipEventCreate failed"); return nullptr; }
+    if (chain_load(e.get(), S, n_chains, matrix, gaps, size, x_drop, anchor_first, q_anchor, r_anchor, anchor_len, true)) return nullptr;
+    return e.release();
+}
+int ba_chain_batch_reload(BaChainBatch* e, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len,
+                          const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor, const uint32_t* anchor_len, const uint8_t* strand,
+                          uintptr_t n_chains) {
+    if (!e) return fail("null batch");
+    ChainSet S;
+    if (chain_plan(e->kind, pool, q_off, q_len, r_off, r_len, anchor_first, q_anchor, r_anchor, anchor_len, strand, n_chains, S)) return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    return chain_load(e, S, n_chains, nullptr, Gaps{0, 0}, SizeRange{0, 0}, 0, anchor_first, q_anchor, r_anchor, anchor_len, false);   // (matrix, gaps, range: the batch's own)
+}
+int ba_chain_batch_run(BaChainBatch* e, float* kernel_ms) {
+    if (!e) return fail("null batch");
+    if (!e->n) return fail("no chains loaded (the last reload failed)");
+    HIP_TRY(hipSetDevice(e->device));
+    e->ran = false; e->ends_ms = 0; e->gaps_ms = 0; e->splice_ms = 0; e->total_runs = 0;
+    // One fill after the other, each waited for: a traced launch holds waves that wait for one another and needs the device to itself to be
+    // sure to end (ba_sized_batch_run). The splice reads final results only (re-runs included).
+    if (e->n_ends && batch_run(e->ends.get(), &e->ends_ms)) return 1;
+    if (e->n_gaps && batch_run(e->gaps.get(), &e->gaps_ms)) return 1;
+    ba::ChainParams cp = e->params();
+    HIP_TRY(hipEventRecord(e->ev[0], e->stream));
+    HIP_TRY(ba_launch_chain_results(e->stream, &cp));
+    if (e->mode & BA_TRACE) HIP_TRY(ba_launch_offsets(e->stream, cp.cigar_len, cp.out_off, cp.n));
+    HIP_TRY(hipEventRecord(e->ev[1], e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipEventElapsedTime(&e->splice_ms, e->ev[0], e->ev[1]));
+    if (e->mode & BA_TRACE) {
+        uint64_t total = 0;
+        HIP_TRY(hipMemcpy(&total, e->out_off.as<uint64_t>() + e->n, 8, hipMemcpyDeviceToHost));
+        if (total > e->runs_cap) {
+            if (e->runs.alloc(total * 4)) return 1;
+            e->runs_cap = total;
+        }
+        cp.runs = e->runs.as<uint32_t>();
+        HIP_TRY(hipEventRecord(e->ev[2], e->stream));
+        HIP_TRY(ba_launch_chain_gather(e->stream, &cp));
+        HIP_TRY(hipEventRecord(e->ev[3], e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, e->ev[2], e->ev[3]));
+        e->splice_ms += ms;
+        e->total_runs = total;
+    }
+    e->ran = true;
+    if (kernel_ms) *kernel_ms = e->ends_ms + e->gaps_ms;
+    return 0;
+}
+int ba_chain_batch_results(BaChainBatch* e, int32_t* score, uint32_t* q_start, uint32_t* r_start, uint32_t* q_end, uint32_t* r_end,
+                           int32_t* left_score, int32_t* right_score, uint64_t* cells, uint32_t* cigar_len, uint32_t* status) {
+    if (!e) return fail("null batch");
+    if (!e->ran) return fail("ba_chain_batch_run has not been called");
+    HIP_TRY(hipSetDevice(e->device));
+    if (d2h(e->score, score, e->n) || d2h(e->q_start, q_start, e->n) || d2h(e->r_start, r_start, e->n) || d2h(e->q_end, q_end, e->n) ||
+        d2h(e->r_end, r_end, e->n) || d2h(e->left_score, left_score, e->n) || d2h(e->right_score, right_score, e->n) ||
+        d2h(e->cells, cells, e->n) || d2h(e->cigar_len, cigar_len, e->n) || d2h(e->status, status, e->n)) return 1;
+    return 0;
+}
+int ba_chain_batch_cigars(BaChainBatch* e, uint32_t* runs, uint64_t capacity) {
+    if (!e) return fail("null batch");
+    if (!(e->mode & BA_TRACE)) return fail("batch was created without BA_TRACE");
+    if (!e->ran) return fail("ba_chain_batch_run has not been called");
+    if (e->total_runs > capacity) return fail("cigar buffer too small: need %llu entries", (unsigned long long)e->total_runs);
+    if (!e->total_runs) return 0;
+    if (!runs) return fail("null argument");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMemcpy(runs, e->runs.p, e->total_runs * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+int ba_chain_batch_times(BaChainBatch* e, float* ends_ms, float* gaps_ms, float* pack_ms, float* splice_ms) {
+    if (!e) return fail("null batch");
+    if (ends_ms) *ends_ms = e->ends_ms;
+    if (gaps_ms) *gaps_ms = e->gaps_ms;
+    if (pack_ms) *pack_ms = e->pack_ms;
+    if (splice_ms) *splice_ms = e->splice_ms;
+    return 0;
+}
+void ba_chain_batch_destroy(BaChainBatch* e) { delete e; }
 
 int block_batch_align(int kind, const void* matrix, Gaps gaps, SizeRange size, int32_t x_drop, uint32_t mode, const uint8_t* pool,
                       const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len, uintptr_t n,

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime_api.h>
 
+#include "ba_chain.h"
 #include "ba_exact.h"
 #include "ba_extend.h"
 #include "ba_params.h"
@@ -67,6 +68,9 @@ hipError_t ba_launch_pack_images(hipStream_t s, int kind, const uint8_t* raw, co
                                  uint8_t* image, uint32_t pad, uint32_t n, unsigned long long* err);
 hipError_t ba_launch_extend_results(hipStream_t s, const ba::ExtendParams* ep);
 hipError_t ba_launch_extend_gather(hipStream_t s, const ba::ExtendParams* ep);
+// ba_chain.hip
+hipError_t ba_launch_chain_results(hipStream_t s, const ba::ChainParams* cp);
+hipError_t ba_launch_chain_gather(hipStream_t s, const ba::ChainParams* cp);
 // ba_stats.hip
 hipError_t ba_launch_stats(hipStream_t s, const ba::StatsParams* sp);
 hipError_t ba_launch_stats_extend(hipStream_t s, const ba::ExtendParams* ep, const ba::AlignStats* side, ba::AlignStats* out);

@@ -194,6 +194,14 @@ def lib() -> C.CDLL:
         L.ba_extend_batch_create.argtypes = [C.c_int, vp, GapsC, SizeRangeC, i32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz]
         L.ba_extend_batch_reload.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz]
         L.ba_extend_batch_times.argtypes = [vp, vp, vp, vp]
+        L.ba_chain_batch_create.restype = vp
+        L.ba_chain_batch_create.argtypes = [C.c_int, vp, GapsC, SizeRangeC, i32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz]
+        L.ba_chain_batch_reload.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz]
+        L.ba_chain_batch_times.argtypes = [vp, vp, vp, vp, vp]
+        L.ba_chain_batch_run.argtypes = [vp, C.POINTER(C.c_float)]
+        L.ba_chain_batch_results.argtypes = [vp] * 11
+        L.ba_chain_batch_cigars.argtypes = [vp, vp, C.c_uint64]
+        L.ba_chain_batch_destroy.argtypes = [vp]
         for f, fields in (("ba_batch", 6), ("ba_sized_batch", 6), ("ba_multibatch", 6), ("ba_extend_batch", 10)):   # the calls of _Batch
             getattr(L, f"{f}_run").argtypes = [vp, C.POINTER(C.c_float)]
             getattr(L, f"{f}_results").argtypes = [vp] * (1 + fields)
@@ -945,6 +953,62 @@ class ExtendBatchAligner(_Batch):
         f, p, s = C.c_float(), C.c_float(), C.c_float()
         self._call("times", C.byref(f), C.byref(p), C.byref(s))
         return dict(fill_ms=f.value, pack_ms=p.value, splice_ms=s.value)
+
+
+class ChainBatchAligner(_Batch):
+    """Anchor-chain batch (ba_chain_batch_*): chain c holds the anchors anchor_first[c] .. anchor_first[c + 1] (anchor_first: one entry per
+    chain and one more, from 0), anchor k at q[q_anchor[k]:+anchor_len[k]] / r[r_anchor[k]:+anchor_len[k]] of the chain's sequences
+    q = pool[q_off[c]:+q_len[c]], r = pool[r_off[c]:+r_len[c]]. The stretches between consecutive anchors are aligned globally, the two ends
+    of the chain extended with X-drop as the sides of a seed, and everything spliced into one result per chain on the device. strand as for
+    ExtendBatchAligner. mode must hold X_DROP; TRACE and CIGAR_EQ are optional. Arguments are checked before the device is touched.
+
+    run() fills the ends, then the gaps, then splices, and returns both fills' time. results() has ExtendBatchAligner's keys; cigars() gives
+    chain c's runs. Statistics, strings and exact scores of chain batches are not offered ("Anchor chains")."""
+
+    _C = "ba_chain_batch"
+    RESULTS = ExtendBatchAligner.RESULTS
+
+    @staticmethod
+    def _arrays(pool, q_off, q_len, r_off, r_len, anchor_first, q_anchor, r_anchor, anchor_len, strand):
+        a = _pair_arrays(pool, q_off, q_len, r_off, r_len) + [np.ascontiguousarray(anchor_first, dtype=np.uint64)] + \
+            [np.ascontiguousarray(x, dtype=np.uint32) for x in (q_anchor, r_anchor, anchor_len)] + \
+            [None if strand is None else np.ascontiguousarray(strand, dtype=np.uint8)]
+        n = len(a[2])
+        if any(len(x) != n for x in a[1:5]) or (a[9] is not None and len(a[9]) != n):
+            raise ValueError("q_off, q_len, r_off, r_len and strand must have one entry per chain")
+        if len(a[5]) != n + 1:
+            raise ValueError("anchor_first must have one entry per chain and one more")
+        if any(len(x) != len(a[6]) for x in a[7:9]) or (n and len(a[6]) != int(a[5][-1])):
+            raise ValueError("q_anchor, r_anchor and anchor_len must have one entry per anchor (anchor_first[-1] of them)")
+        return a
+
+    def __init__(self, matrix, gaps, size, x_drop: int, mode: int, pool, q_off, q_len, r_off, r_len, anchor_first, q_anchor, r_anchor, anchor_len,
+                 strand=None):
+        a = self._arrays(pool, q_off, q_len, r_off, r_len, anchor_first, q_anchor, r_anchor, anchor_len, strand)
+        self.n = len(a[2])
+        self.mode = mode
+        raw = matrix.raw()
+        self._h = lib().ba_chain_batch_create(matrix.KIND, raw.ctypes.data, _gaps(gaps), _size(size), x_drop, mode, *_ptrs(a), self.n)
+        if not self._h:
+            raise RuntimeError(last_error())
+
+    def reload(self, pool, q_off, q_len, r_off, r_len, anchor_first, q_anchor, r_anchor, anchor_len, strand=None) -> None:
+        """Replace the chains and keep the device buffers (ba_chain_batch_reload): the new set must fit the original one's sizes."""
+        a = self._arrays(pool, q_off, q_len, r_off, r_len, anchor_first, q_anchor, r_anchor, anchor_len, strand)
+        self._call("reload", *_ptrs(a), len(a[2]))
+        self.n = len(a[2])
+
+    def times(self):
+        """Device milliseconds: both fills and the splice of the last run(), image packers of the last create / reload."""
+        e, g, p, s = C.c_float(), C.c_float(), C.c_float(), C.c_float()
+        self._call("times", C.byref(e), C.byref(g), C.byref(p), C.byref(s))
+        return dict(ends_ms=e.value, gaps_ms=g.value, pack_ms=p.value, splice_ms=s.value)
+
+    def _not_offered(self, *args, **kwargs):
+        raise RuntimeError("chain batches offer run, results, cigars, reload and times only: statistics, strings, exact scores and the "
+                           "accuracy report of chain batches are out of scope (INTEGRATION.md, \"Anchor chains\")")
+
+    stats = text = text_list = exact = exact_cigars = exact_paths = accuracy = _not_offered
 
 
 def batch_align_exp(matrix, gaps, size, x_drop: int, target_score: int, mode: int, pool, q_off, q_len, r_off, r_len):

@@ -314,6 +314,54 @@ int ba_extend_batch_cigars(BaExtendBatch* batch, uint32_t* runs, uint64_t capaci
 int ba_extend_batch_times(BaExtendBatch* batch, float* fill_ms, float* pack_ms, float* splice_ms);
 void ba_extend_batch_destroy(BaExtendBatch* batch);
 
+/* ---- anchor-chain batches: global alignment between the anchors of a chain, X-drop extension at its two ends, one result per chain
+ * ("Anchor chains").
+ *
+ * Chain c holds the K >= 1 anchors anchor_first[c] .. anchor_first[c + 1] (anchor_first: n_chains + 1 entries, from 0, increasing). Anchor k
+ * lies at q[q_anchor .. + anchor_len) and r[r_anchor .. + anchor_len) of the chain's query q = pool[q_off[c] .. +q_len[c]) and reference
+ * r = pool[r_off[c] .. +r_len[c]), anchor_len >= 1; the anchors of a chain are colinear and disjoint on both sequences (anchor k ends at or
+ * before the start of anchor k + 1) and lie inside them. strand as for ba_extend_batch_create: strand[c] = 1 (NucMatrix only) replaces q by its
+ * reverse complement, and the anchors and the results are in that frame.
+ *
+ * An anchor is ungapped and need not match exactly: its score is the sum of matrix(q, r) over its columns. Gap k, between anchors k and k + 1,
+ * has the slices gq = q[end of k .. start of k + 1) and gr likewise: both empty -- nothing; one empty -- one I run (gr empty) or one D run (gq
+ * empty) over the other's length d, score open + (d - 1) * extend, no cells; both non-empty -- Block::<TRACE, false>::align of gq against gr with
+ * the batch's matrix, gaps and block range, without X-drop, ending at its corner. The ends are the two sides of a seed (above): left of anchor 0
+ * the reversed prefixes, right of anchor K - 1 the suffixes, each with X-drop; an empty side is not aligned. All ends of a set are ONE X-drop
+ * batch on the device and all aligned gaps ONE global batch, their images cut out of the caller's bytes there; the fills run one after the
+ * other, and everything is spliced on the device. A chain of one anchor is a seed: results and runs are ba_extend_batch_*'s, bit for bit.
+ *
+ * Modes: BA_X_DROP is required (for the ends), BA_TRACE and BA_CIGAR_EQ are optional; LOCAL_START and FREE_QUERY_* are rejected, and so are
+ * profile batches. The gap batch has the same mode without BA_X_DROP. Every argument is checked before the device is touched (a chain without
+ * anchors, anchor_len 0, anchors that overlap or are out of order, an anchor past the end, anchor_first that does not start at 0 or decreases,
+ * a bad strand: a message naming the chain and the anchor). */
+typedef struct BaChainBatch BaChainBatch;
+BaChainBatch* ba_chain_batch_create(int kind, const void* matrix, struct Gaps gaps, struct SizeRange size, int32_t x_drop, uint32_t mode,
+                                    const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len,
+                                    const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor, const uint32_t* anchor_len,
+                                    const uint8_t* strand, uintptr_t n_chains);
+/* Replace the chains and keep the device buffers, as ba_extend_batch_reload: the new set must fit what the batch was created with -- no more
+ * chains, anchors or sequence bytes, and its ends and its aligned gaps no more than the original ones (in number, bytes and longest pair); a
+ * batch created without ends (or without aligned gaps) takes no set that has some. */
+int ba_chain_batch_reload(BaChainBatch* batch, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off,
+                          const uint32_t* r_len, const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor,
+                          const uint32_t* anchor_len, const uint8_t* strand, uintptr_t n_chains);
+/* Fill the ends, then the gaps (re-runs included), then splice. kernel_ms (optional) = HIP-event time of both fills. */
+int ba_chain_batch_run(BaChainBatch* batch, float* kernel_ms);
+/* Results per chain, in the caller's order; any pointer may be NULL. score = both ends + all anchors + all gaps; the alignment covers
+ * q[q_start .. q_end) and r[r_start .. r_end), taken from the first and the last anchor as for a seed; left_score / right_score = the ends'
+ * scores; cells = the sum over all aligned pieces; status = the OR of their BA_ST_* bits; cigar_len = runs per chain (BA_TRACE). */
+int ba_chain_batch_results(BaChainBatch* batch, int32_t* score, uint32_t* q_start, uint32_t* r_start, uint32_t* q_end, uint32_t* r_end,
+                           int32_t* left_score, int32_t* right_score, uint64_t* cells, uint32_t* cigar_len, uint32_t* status);
+/* BA_TRACE: every chain's runs, concatenated in chain order: the left end's runs reversed, anchor 0, gap 0, anchor 1, ..., anchor K - 1, the
+ * right end's runs (an anchor: one M run, or its =/X runs with BA_CIGAR_EQ); adjacent runs with the same op are merged at every join, across
+ * any number of pieces. Every gap lies between two anchors, so two gap runs never merge and every merge is score-neutral: rescored over
+ * q[q_start .. q_end) / r[r_start .. r_end), the runs give `score` exactly. */
+int ba_chain_batch_cigars(BaChainBatch* batch, uint32_t* runs, uint64_t capacity);
+/* Device times in ms: the last run's two fills and its splice; the image packers of the last create / reload. Any pointer may be NULL. */
+int ba_chain_batch_times(BaChainBatch* batch, float* ends_ms, float* gaps_ms, float* pack_ms, float* splice_ms);
+void ba_chain_batch_destroy(BaChainBatch* batch);
+
 /* ---- every pair with its own block range. The reference's callers choose the range per pair -- percent_len(max(|q|, |r|), 0.01) ..=
  * percent_len(max(|q|, |r|), p) in /root/reference/examples/nanopore_bench_global.rs:144-171, Block::align(..., min..=max, x) in
  * src/scan_block.rs:847 --, while ba_batch_create takes one range for the whole batch. These calls bin the pairs by (min, max), align every bin as
