@@ -2985,6 +2985,203 @@ int ba_chain_batch_times(BaChainBatch* e, float* ends_ms, float* gaps_ms, float*
 }
 void ba_chain_batch_destroy(BaChainBatch* e) { delete e; }
 
+// ------------------------------------------------------------------ colinear anchor chaining (ba_chaining_*)
+// From a problem's raw hits to its best chains, in ba_chain_batch_create's layout (ba_chaining.hip; the rule: INTEGRATION.md, "Chaining
+// anchors"). The host checks the arguments, orders the problems longest first and sizes the buffers; the recurrence, the picking and the
+// gather are the device's.
+struct BaChaining {
+    int device = 0;
+    BaChainingParams P{};
+    uint32_t n = 0, ring = 0;
+    uint64_t n_anchors = 0, cap_n = 0, cap_anchors = 0, chains_cap = 0, total_chains = 0, total_kept = 0;
+    hipStream_t stream = nullptr; hipEvent_t ev[4] = {};
+    DevBuf anchor_first, q_anchor, r_anchor, anchor_len, order, counter, f, pred, gain, mark, pos, cand_len, cand_score, n_chains, n_kept, chain_off, kept_off;
+    DevBuf chain_problem, chain_rank, chain_score, out_first, out_q, out_r, out_len, out_src;
+    float fill_ms = 0, pick_ms = 0, gather_ms = 0;
+    bool ran = false;
+    ba::ChainingParams params() const {
+        ba::ChainingParams cp{};
+        cp.n = n; cp.match_w = P.match_w; cp.drift_cost = P.drift_cost; cp.skip_cost = P.skip_cost; cp.lookback = P.lookback; cp.max_dist = P.max_dist;
+        cp.bandwidth = P.bandwidth; cp.max_chains = P.max_chains; cp.min_score = P.min_score; cp.min_anchors = P.min_anchors; cp.ring = ring;
+        cp.anchor_first = anchor_first.as<uint64_t>(); cp.q_anchor = q_anchor.as<uint32_t>(); cp.r_anchor = r_anchor.as<uint32_t>();
+        cp.anchor_len = anchor_len.as<uint32_t>(); cp.order = order.as<uint32_t>(); cp.counter = counter.as<uint32_t>();
+        cp.f = f.as<int32_t>(); cp.pred = pred.as<uint32_t>(); cp.gain = gain.as<uint32_t>(); cp.mark = mark.as<uint32_t>(); cp.pos = pos.as<uint32_t>();
+        cp.cand_len = cand_len.as<uint32_t>(); cp.cand_score = cand_score.as<int32_t>(); cp.n_chains = n_chains.as<uint32_t>(); cp.n_kept = n_kept.as<uint32_t>();
+        cp.chain_off = chain_off.as<uint64_t>(); cp.kept_off = kept_off.as<uint64_t>();
+        cp.chain_problem = chain_problem.as<uint32_t>(); cp.chain_rank = chain_rank.as<uint32_t>(); cp.chain_score = chain_score.as<int32_t>();
+        cp.out_first = out_first.as<uint64_t>(); cp.out_q = out_q.as<uint32_t>(); cp.out_r = out_r.as<uint32_t>(); cp.out_len = out_len.as<uint32_t>();
+        cp.out_src = out_src.as<uint32_t>();
+        return cp;
+    }
+    ~BaChaining() {
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+static int chaining_check_params(const BaChainingParams& P) {
+    if (P.match_w < 1) return fail("chaining: match_w must be at least 1 (it is %d)", P.match_w);
+    if (P.drift_cost < 0 || P.skip_cost < 0) return fail("chaining: drift_cost and skip_cost must not be negative (they are %d and %d)", P.drift_cost, P.skip_cost);
+    if (P.lookback < 1 || P.lookback > ba::CHAINING_MAX_LOOKBACK) return fail("chaining: lookback must be between 1 and %u (it is %u)", ba::CHAINING_MAX_LOOKBACK, P.lookback);
+    if (P.max_dist < 1) return fail("chaining: max_dist must be at least 1");
+    if (P.max_chains < 1 || P.max_chains > ba::CHAINING_MAX_CHAINS) return fail("chaining: max_chains must be between 1 and %u (it is %u)", ba::CHAINING_MAX_CHAINS, P.max_chains);
+    if (P.min_anchors < 1) return fail("chaining: min_anchors must be at least 1");
+    if ((uint64_t)P.drift_cost * P.bandwidth + (uint64_t)P.skip_cost * P.max_dist >= (1ull << 30))
+        return fail("chaining: drift_cost * bandwidth + skip_cost * max_dist must stay below 2^30 (it is %llu)",
+                    (unsigned long long)((uint64_t)P.drift_cost * P.bandwidth + (uint64_t)P.skip_cost * P.max_dist));
+    return 0;
+}
+// Check a set of problems; -> the problems ordered by their number of anchors, the longest first.
+static int chaining_plan(const BaChainingParams& P, const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor, const uint32_t* anchor_len,
+                         size_t n, std::vector<uint32_t>& order) {
+    if (!anchor_first || !q_anchor || !r_anchor || !anchor_len) return fail("null argument");
+    if (n == 0 || n > (1u << 28)) return fail("a chaining batch must hold between 1 and 2^28 problems");
+    if (anchor_first[0] != 0) return fail("anchor_first must start at 0 (problem 0 starts at %llu)", (unsigned long long)anchor_first[0]);
+    for (size_t p = 0; p < n; p++)
+        if (anchor_first[p + 1] < anchor_first[p])
+            return fail("problem %zu: anchor_first must not decrease (%llu after %llu)", p, (unsigned long long)anchor_first[p + 1], (unsigned long long)anchor_first[p]);
+    if (anchor_first[n] > (1u << 28)) return fail("a chaining batch must hold at most 2^28 anchors");
+    for (size_t p = 0; p < n; p++) {
+        uint64_t sum = 0, pq = 0, pr = 0;
+        for (uint64_t a = anchor_first[p]; a < anchor_first[p + 1]; a++) {
+            const uint64_t k = a - anchor_first[p], L = anchor_len[a], qe = (uint64_t)q_anchor[a] + L, re = (uint64_t)r_anchor[a] + L;
+            if (L == 0) return fail("problem %zu, anchor %llu: anchor_len must be at least 1", p, (unsigned long long)k);
+            if (qe >= (1ull << 31) || re >= (1ull << 31))
+                return fail("problem %zu, anchor %llu: the anchor ends at query %llu, reference %llu: both must stay below 2^31", p, (unsigned long long)k,
+                            (unsigned long long)qe, (unsigned long long)re);
+            if (k && (re < pr || (re == pr && qe < pq)))
+                return fail("problem %zu, anchor %llu: the anchors must be sorted by (reference end, query end): (%llu, %llu) comes after (%llu, %llu)", p,
+                            (unsigned long long)k, (unsigned long long)re, (unsigned long long)qe, (unsigned long long)pr, (unsigned long long)pq);
+            pq = qe; pr = re; sum += L;
+        }
+        if (sum * (uint64_t)P.match_w >= (1ull << 31))
+            return fail("problem %zu: match_w * the sum of anchor_len must stay below 2^31 (it is %llu)", p, (unsigned long long)(sum * (uint64_t)P.match_w));
+    }
+    order.resize(n);
+    for (size_t p = 0; p < n; p++) order[p] = (uint32_t)p;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return anchor_first[a + 1] - anchor_first[a] > anchor_first[b + 1] - anchor_first[b]; });
+    return 0;
+}
+static int chaining_load(BaChaining* e, const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor, const uint32_t* anchor_len, size_t n,
+                         const std::vector<uint32_t>& order, bool create) {
+    const uint64_t na = anchor_first[n];
+    if (create) {
+        e->cap_n = n; e->cap_anchors = na;
+        DevBuf* per_anchor4[] = {&e->q_anchor, &e->r_anchor, &e->anchor_len, &e->f, &e->pred, &e->gain, &e->mark, &e->pos, &e->out_q, &e->out_r, &e->out_len, &e->out_src};
+        for (DevBuf* d : per_anchor4) if (d->alloc(na * 4)) return 1;
+        if (e->anchor_first.alloc((n + 1) * 8) || e->order.alloc(n * 4) || e->counter.alloc(4) || e->cand_len.alloc(n * e->P.max_chains * 4) ||
+            e->cand_score.alloc(n * e->P.max_chains * 4) || e->n_chains.alloc(n * 4) || e->n_kept.alloc(n * 4) || e->chain_off.alloc((n + 1) * 8) ||
+            e->kept_off.alloc((n + 1) * 8)) return 1;
+    } else {
+        if (n > e->cap_n) return fail("reload: %zu problems exceed the batch's capacity of %llu", n, (unsigned long long)e->cap_n);
+        if (na > e->cap_anchors) return fail("reload: %llu anchors exceed the batch's capacity of %llu", (unsigned long long)na, (unsigned long long)e->cap_anchors);
+    }
+    e->n = 0; e->ran = false;   // (a failure from here on leaves no problems loaded)
+    HIP_TRY(hipMemcpy(e->anchor_first.p, anchor_first, (n + 1) * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->order.p, order.data(), n * 4, hipMemcpyHostToDevice));
+    if (na) {
+        HIP_TRY(hipMemcpy(e->q_anchor.p, q_anchor, na * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(e->r_anchor.p, r_anchor, na * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(e->anchor_len.p, anchor_len, na * 4, hipMemcpyHostToDevice));
+    }
+    e->n = (uint32_t)n; e->n_anchors = na;
+    return 0;
+}
+BaChaining* ba_chaining_create(const BaChainingParams* params, const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor,
+                               const uint32_t* anchor_len, uintptr_t n_problems) {
+    std::vector<uint32_t> order;   // every argument is checked before the device is touched
+    if (!params) { fail("null argument"); return nullptr; }
+    if (chaining_check_params(*params) || chaining_plan(*params, anchor_first, q_anchor, r_anchor, anchor_len, n_problems, order)) return nullptr;
+    if (ensure_device()) return nullptr;
+    std::unique_ptr<BaChaining> e(new BaChaining);
+    e->device = g_device; e->P = *params;
+    e->ring = 128;
+    while (e->ring < params->lookback + 64u) e->ring <<= 1;
+    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { fail("hipStreamCreate failed"); return nullptr; }
+    for (hipEvent_t& ev : e->ev) if (hipEventCreate(&ev) != hipSuccess) { fail("hipEventCreate failed"); return nullptr; }
+    if (chaining_load(e.get(), anchor_first, q_anchor, r_anchor, anchor_len, n_problems, order, true)) return nullptr;
+    return e.release();
+}
+int ba_chaining_reload(BaChaining* e, const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor, const uint32_t* anchor_len,
+                       uintptr_t n_problems) {
+    if (!e) return fail("null batch");
+    std::vector<uint32_t> order;
+    if (chaining_plan(e->P, anchor_first, q_anchor, r_anchor, anchor_len, n_problems, order)) return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    return chaining_load(e, anchor_first, q_anchor, r_anchor, anchor_len, n_problems, order, false);
+}
+int ba_chaining_run(BaChaining* e, float* kernel_ms) {
+    if (!e) return fail("null batch");
+    if (!e->n) return fail("no problems loaded (the last reload failed)");
+    HIP_TRY(hipSetDevice(e->device));
+    e->ran = false; e->fill_ms = e->pick_ms = e->gather_ms = 0; e->total_chains = e->total_kept = 0;
+    ba::ChainingParams cp = e->params();
+    HIP_TRY(hipMemsetAsync(e->counter.p, 0, 4, e->stream));
+    HIP_TRY(hipEventRecord(e->ev[0], e->stream));
+    HIP_TRY(ba_launch_chaining_fill(e->stream, &cp));
+    HIP_TRY(hipEventRecord(e->ev[1], e->stream));
+    HIP_TRY(ba_launch_chaining_pick(e->stream, &cp));
+    HIP_TRY(ba_launch_offsets(e->stream, cp.n_chains, e->chain_off.as<uint64_t>(), cp.n));
+    HIP_TRY(ba_launch_offsets(e->stream, cp.n_kept, e->kept_off.as<uint64_t>(), cp.n));
+    HIP_TRY(hipEventRecord(e->ev[2], e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipEventElapsedTime(&e->fill_ms, e->ev[0], e->ev[1]));
+    HIP_TRY(hipEventElapsedTime(&e->pick_ms, e->ev[1], e->ev[2]));
+    uint64_t chains = 0, kept = 0;
+    HIP_TRY(hipMemcpy(&chains, e->chain_off.as<uint64_t>() + e->n, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&kept, e->kept_off.as<uint64_t>() + e->n, 8, hipMemcpyDeviceToHost));
+    if (chains > (uint64_t)e->n * e->P.max_chains || kept > e->n_anchors)
+        return fail("chaining: the device counted %llu chains and %llu anchors, more than the set can hold", (unsigned long long)chains, (unsigned long long)kept);
+    if (chains > e->chains_cap || !e->out_first.p) {   // (grows, never shrinks)
+        if (e->chain_problem.alloc(chains * 4) || e->chain_rank.alloc(chains * 4) || e->chain_score.alloc(chains * 4) || e->out_first.alloc((chains + 1) * 8)) return 1;
+        e->chains_cap = chains;
+        cp = e->params();
+    }
+    HIP_TRY(hipEventRecord(e->ev[2], e->stream));
+    HIP_TRY(ba_launch_chaining_gather(e->stream, &cp));
+    HIP_TRY(hipEventRecord(e->ev[3], e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipEventElapsedTime(&e->gather_ms, e->ev[2], e->ev[3]));
+    e->total_chains = chains; e->total_kept = kept;
+    e->ran = true;
+    if (kernel_ms) *kernel_ms = e->fill_ms + e->pick_ms + e->gather_ms;
+    return 0;
+}
+int ba_chaining_counts(BaChaining* e, uint64_t* n_chains, uint64_t* n_anchors, uint32_t* chains_per_problem) {
+    if (!e) return fail("null batch");
+    if (!e->ran) return fail("ba_chaining_run has not been called");
+    HIP_TRY(hipSetDevice(e->device));
+    if (n_chains) *n_chains = e->total_chains;
+    if (n_anchors) *n_anchors = e->total_kept;
+    return d2h(e->n_chains, chains_per_problem, e->n);
+}
+int ba_chaining_results(BaChaining* e, uint32_t* chain_problem, uint32_t* chain_rank, int32_t* chain_score, uint64_t* out_anchor_first, uint32_t* out_q_anchor,
+                        uint32_t* out_r_anchor, uint32_t* out_anchor_len, uint32_t* out_anchor_src) {
+    if (!e) return fail("null batch");
+    if (!e->ran) return fail("ba_chaining_run has not been called");
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t nc = e->total_chains, nk = e->total_kept;
+    if (d2h(e->chain_problem, chain_problem, nc) || d2h(e->chain_rank, chain_rank, nc) || d2h(e->chain_score, chain_score, nc) ||
+        d2h(e->out_first, out_anchor_first, nc + 1) || d2h(e->out_q, out_q_anchor, nk) || d2h(e->out_r, out_r_anchor, nk) ||
+        d2h(e->out_len, out_anchor_len, nk) || d2h(e->out_src, out_anchor_src, nk)) return 1;
+    return 0;
+}
+int ba_chaining_dp(BaChaining* e, int32_t* f, int32_t* pred) {
+    if (!e) return fail("null batch");
+    if (!e->ran) return fail("ba_chaining_run has not been called");
+    HIP_TRY(hipSetDevice(e->device));
+    if (d2h(e->f, f, e->n_anchors)) return 1;
+    if (pred) HIP_TRY(hipMemcpy(pred, e->pred.p, e->n_anchors * 4, hipMemcpyDeviceToHost));   // (CHAINING_NONE is -1)
+    return 0;
+}
+int ba_chaining_times(BaChaining* e, float* fill_ms, float* pick_ms, float* gather_ms) {
+    if (!e) return fail("null batch");
+    if (fill_ms) *fill_ms = e->fill_ms;
+    if (pick_ms) *pick_ms = e->pick_ms;
+    if (gather_ms) *gather_ms = e->gather_ms;
+    return 0;
+}
+void ba_chaining_destroy(BaChaining* e) { delete e; }
+
 int block_batch_align(int kind, const void* matrix, Gaps gaps, SizeRange size, int32_t x_drop, uint32_t mode, const uint8_t* pool,
                       const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len, uintptr_t n,
                       AlignResult* results, uint32_t* cigar_runs, uint64_t cigar_capacity, uint32_t* cigar_len) {

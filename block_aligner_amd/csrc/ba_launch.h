@@ -4,6 +4,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "ba_chain.h"
+#include "ba_chaining.h"
 #include "ba_exact.h"
 #include "ba_extend.h"
 #include "ba_params.h"
@@ -71,6 +72,10 @@ hipError_t ba_launch_extend_gather(hipStream_t s, const ba::ExtendParams* ep);
 // ba_chain.hip
 hipError_t ba_launch_chain_results(hipStream_t s, const ba::ChainParams* cp);
 hipError_t ba_launch_chain_gather(hipStream_t s, const ba::ChainParams* cp);
+// ba_chaining.hip
+hipError_t ba_launch_chaining_fill(hipStream_t s, const ba::ChainingParams* cp);
+hipError_t ba_launch_chaining_pick(hipStream_t s, const ba::ChainingParams* cp);
+hipError_t ba_launch_chaining_gather(hipStream_t s, const ba::ChainingParams* cp);
 // ba_stats.hip
 hipError_t ba_launch_stats(hipStream_t s, const ba::StatsParams* sp);
 hipError_t ba_launch_stats_extend(hipStream_t s, const ba::ExtendParams* ep, const ba::AlignStats* side, ba::AlignStats* out);

@@ -68,6 +68,12 @@ class ExactPathC(C.Structure):
                 ("rows", C.c_uint32)]
 
 
+class ChainingParamsC(C.Structure):
+    """struct BaChainingParams (include/block_aligner_hip.h): the parameters of the ba_chaining_* calls."""
+    _fields_ = [("match_w", C.c_int32), ("drift_cost", C.c_int32), ("skip_cost", C.c_int32), ("lookback", C.c_uint32), ("max_dist", C.c_uint32),
+                ("bandwidth", C.c_uint32), ("max_chains", C.c_uint32), ("min_score", C.c_int32), ("min_anchors", C.c_uint32)]
+
+
 class AccuracyC(C.Structure):
     """struct BaAccuracy: what ba_accuracy_summary reports."""
     _fields_ = [("n", C.c_uint64), ("compared", C.c_uint64), ("skipped", C.c_uint64), ("wrong", C.c_uint64), ("below", C.c_uint64),
@@ -202,6 +208,15 @@ def lib() -> C.CDLL:
         L.ba_chain_batch_results.argtypes = [vp] * 11
         L.ba_chain_batch_cigars.argtypes = [vp, vp, C.c_uint64]
         L.ba_chain_batch_destroy.argtypes = [vp]
+        L.ba_chaining_create.restype = vp
+        L.ba_chaining_create.argtypes = [C.POINTER(ChainingParamsC), vp, vp, vp, vp, sz]
+        L.ba_chaining_reload.argtypes = [vp, vp, vp, vp, vp, sz]
+        L.ba_chaining_run.argtypes = [vp, C.POINTER(C.c_float)]
+        L.ba_chaining_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
+        L.ba_chaining_results.argtypes = [vp] * 9
+        L.ba_chaining_dp.argtypes = [vp, vp, vp]
+        L.ba_chaining_times.argtypes = [vp, vp, vp, vp]
+        L.ba_chaining_destroy.argtypes = [vp]
         for f, fields in (("ba_batch", 6), ("ba_sized_batch", 6), ("ba_multibatch", 6), ("ba_extend_batch", 10)):   # the calls of _Batch
             getattr(L, f"{f}_run").argtypes = [vp, C.POINTER(C.c_float)]
             getattr(L, f"{f}_results").argtypes = [vp] * (1 + fields)
@@ -1009,6 +1024,99 @@ class ChainBatchAligner(_Batch):
                            "accuracy report of chain batches are out of scope (INTEGRATION.md, \"Anchor chains\")")
 
     stats = text = text_list = exact = exact_cigars = exact_paths = accuracy = _not_offered
+
+
+class AnchorChainer:
+    """Colinear anchor chaining on the device (ba_chaining_*; the rule: INTEGRATION.md, "Chaining anchors"). Problem p -- one read against one
+    reference on one strand -- holds the raw hits anchor_first[p] .. anchor_first[p + 1] (anchor_first: one entry per problem and one more,
+    from 0), hit k at q[q_anchor[k]:+anchor_len[k]] / r[r_anchor[k]:+anchor_len[k]], sorted within the problem by (r_anchor + anchor_len,
+    q_anchor + anchor_len). Arguments are checked before the device is touched.
+
+    run() computes the chains and returns the kernels' time; results() gives them in the layout ChainBatchAligner takes, dp() the raw fill.
+    ChainBatchAligner(m, gaps, size, x_drop, mode, *ch.chain_batch_args(pool, q_off, q_len, r_off, r_len)) aligns every chain found."""
+
+    @staticmethod
+    def _arrays(anchor_first, q_anchor, r_anchor, anchor_len):
+        a = [np.ascontiguousarray(anchor_first, dtype=np.uint64)] + [np.ascontiguousarray(x, dtype=np.uint32) for x in (q_anchor, r_anchor, anchor_len)]
+        if len(a[0]) < 1:
+            raise ValueError("anchor_first must have one entry per problem and one more")
+        if any(len(x) != len(a[1]) for x in a[2:]) or len(a[1]) != int(a[0][-1]):
+            raise ValueError("q_anchor, r_anchor and anchor_len must have one entry per anchor (anchor_first[-1] of them)")
+        return a
+
+    def __init__(self, match_w: int, drift_cost: int, skip_cost: int, lookback: int, max_dist: int, bandwidth: int, max_chains: int, min_score: int,
+                 min_anchors: int, anchor_first, q_anchor, r_anchor, anchor_len):
+        a = self._arrays(anchor_first, q_anchor, r_anchor, anchor_len)
+        self.n = len(a[0]) - 1
+        self.n_anchors = len(a[1])
+        self.params = ChainingParamsC(match_w, drift_cost, skip_cost, lookback, max_dist, bandwidth, max_chains, min_score, min_anchors)
+        self._res = None
+        self._h = lib().ba_chaining_create(C.byref(self.params), *_ptrs(a), self.n)
+        if not self._h:
+            raise RuntimeError(last_error())
+
+    def _call(self, name, *args):
+        if getattr(lib(), f"ba_chaining_{name}")(self._h, *args):
+            raise RuntimeError(last_error())
+
+    def reload(self, anchor_first, q_anchor, r_anchor, anchor_len) -> None:
+        """Replace the problems and keep parameters and device buffers (ba_chaining_reload): no more problems and no more anchors than at first."""
+        a = self._arrays(anchor_first, q_anchor, r_anchor, anchor_len)
+        self._res = None
+        self._call("reload", *_ptrs(a), len(a[0]) - 1)
+        self.n, self.n_anchors = len(a[0]) - 1, len(a[1])
+
+    def run(self) -> float:
+        ms = C.c_float()
+        self._res = None
+        self._call("run", C.byref(ms))
+        return ms.value
+
+    def results(self):
+        """-> dict: per kept chain chain_problem, chain_rank, chain_score and anchor_first (one more entry); per kept anchor, in path order,
+        q_anchor, r_anchor, anchor_len (trimmed: disjoint and colinear) and anchor_src (the input anchor, an index within its problem); per
+        problem chains_per_problem."""
+        if self._res is None:
+            nc, na = C.c_uint64(), C.c_uint64()
+            per = np.zeros(self.n, np.uint32)
+            self._call("counts", C.byref(nc), C.byref(na), per.ctypes.data)
+            out = dict(chain_problem=np.zeros(nc.value, np.uint32), chain_rank=np.zeros(nc.value, np.uint32), chain_score=np.zeros(nc.value, np.int32),
+                       anchor_first=np.zeros(nc.value + 1, np.uint64), q_anchor=np.zeros(na.value, np.uint32), r_anchor=np.zeros(na.value, np.uint32),
+                       anchor_len=np.zeros(na.value, np.uint32), anchor_src=np.zeros(na.value, np.uint32))
+            self._call("results", *_ptrs(out.values()))
+            out["chains_per_problem"] = per
+            self._res = out
+        return self._res
+
+    def dp(self):
+        """The raw fill per input anchor -> (f, pred): pred is an index within the problem, -1 for none."""
+        f, pred = np.zeros(self.n_anchors, np.int32), np.zeros(self.n_anchors, np.int32)
+        self._call("dp", f.ctypes.data, pred.ctypes.data)
+        return f, pred
+
+    def times(self):
+        """Device milliseconds of the last run(): the fill, the pick with its offset scans, the gather."""
+        f, p, g = C.c_float(), C.c_float(), C.c_float()
+        self._call("times", C.byref(f), C.byref(p), C.byref(g))
+        return dict(fill_ms=f.value, pick_ms=p.value, gather_ms=g.value)
+
+    def chain_batch_args(self, pool, q_off, q_len, r_off, r_len, strand=None):
+        """The positional arguments of ChainBatchAligner after `mode` for the chains found: the per-problem arrays q_off, q_len, r_off, r_len
+        and strand expanded by chain_problem, and the chains' anchors."""
+        res = self.results()
+        per = [np.asarray(x) for x in (q_off, q_len, r_off, r_len)] + ([] if strand is None else [np.asarray(strand)])
+        if any(len(x) != self.n for x in per):
+            raise ValueError("q_off, q_len, r_off, r_len and strand must have one entry per problem")
+        cp = res["chain_problem"]
+        return (pool, per[0][cp], per[1][cp], per[2][cp], per[3][cp], res["anchor_first"], res["q_anchor"], res["r_anchor"], res["anchor_len"],
+                None if strand is None else per[4][cp])
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.ba_chaining_destroy(self._h)
+            self._h = None
+
+    __del__ = close
 
 
 def batch_align_exp(matrix, gaps, size, x_drop: int, target_score: int, mode: int, pool, q_off, q_len, r_off, r_len):

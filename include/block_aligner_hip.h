@@ -362,6 +362,49 @@ int ba_chain_batch_cigars(BaChainBatch* batch, uint32_t* runs, uint64_t capacity
 int ba_chain_batch_times(BaChainBatch* batch, float* ends_ms, float* gaps_ms, float* pack_ms, float* splice_ms);
 void ba_chain_batch_destroy(BaChainBatch* batch);
 
+/* ---- colinear anchor chaining on the device: from the raw hits of a problem (one read against one reference on one strand: a future row of a
+ * chain batch) to its best colinear chains, in the array layout ba_chain_batch_create takes ("Chaining anchors": the rule).
+ *
+ * Problem p holds the anchors anchor_first[p] .. anchor_first[p + 1] (n_problems + 1 entries, from 0, never decreasing; a problem may be
+ * empty), anchor_len >= 1. With qe = q_anchor + anchor_len and re = r_anchor + anchor_len, the anchors of a problem are sorted by (re, qe)
+ * ascending (equal keys allowed), qe and re stay below 2^31, match_w * the sum of a problem's anchor_len stays below 2^31 and
+ * drift_cost * bandwidth + skip_cost * max_dist below 2^30. Every argument is checked before the device is touched; a message names the
+ * problem and the anchor. Scores are exact int32 arithmetic. */
+struct BaChainingParams {
+    int32_t match_w;       /* >= 1: what a column of an anchor is worth */
+    int32_t drift_cost;    /* >= 0: per diagonal between consecutive anchors, |dq - dr| */
+    int32_t skip_cost;     /* >= 0: per column skipped between consecutive anchors, min(dq, dr) - gain */
+    uint32_t lookback;     /* 1 .. 1024: the anchors before an anchor that may precede it (H) */
+    uint32_t max_dist;     /* >= 1: dq, dr <= max_dist */
+    uint32_t bandwidth;    /* |dq - dr| <= bandwidth */
+    uint32_t max_chains;   /* 1 .. 64: candidates walked per problem */
+    int32_t min_score;     /* a chain is kept from this score */
+    uint32_t min_anchors;  /* >= 1: ... and from this many anchors */
+};
+typedef struct BaChaining BaChaining;
+BaChaining* ba_chaining_create(const struct BaChainingParams* params, const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor,
+                               const uint32_t* anchor_len, uintptr_t n_problems);
+/* Replace the problems and keep parameters and device buffers: the new set must hold no more problems and no more anchors. */
+int ba_chaining_reload(BaChaining* batch, const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor, const uint32_t* anchor_len,
+                       uintptr_t n_problems);
+/* The fill, the pick, the offsets and the gather. kernel_ms (optional): the sum of their HIP-event times. */
+int ba_chaining_run(BaChaining* batch, float* kernel_ms);
+/* After a run: kept chains, their anchors, and the chains of every problem (n_problems entries). Any pointer may be NULL. */
+int ba_chaining_counts(BaChaining* batch, uint64_t* n_chains, uint64_t* n_anchors, uint32_t* chains_per_problem);
+/* After a run; any pointer may be NULL. Per kept chain (n_chains entries; problems in order, the chains of a problem in the order picked):
+ * its problem, its rank within the problem and its score; out_anchor_first (n_chains + 1 entries): where its anchors start. Per kept anchor
+ * (n_anchors entries, in path order): the anchor trimmed to its gain -- disjoint from and colinear with the one before it on both
+ * sequences, at least one column -- and out_anchor_src, the input anchor it came from (an index within its problem).
+ * chain_problem expands per-problem arrays to per-chain ones; out_anchor_first, out_q_anchor, out_r_anchor and out_anchor_len are
+ * ba_chain_batch_create's arguments as they stand. */
+int ba_chaining_results(BaChaining* batch, uint32_t* chain_problem, uint32_t* chain_rank, int32_t* chain_score, uint64_t* out_anchor_first,
+                        uint32_t* out_q_anchor, uint32_t* out_r_anchor, uint32_t* out_anchor_len, uint32_t* out_anchor_src);
+/* After a run: the raw fill per input anchor, f and pred (an index within the problem, -1: none). Either pointer may be NULL. */
+int ba_chaining_dp(BaChaining* batch, int32_t* f, int32_t* pred);
+/* Device times of the last run in ms: the fill, the pick with both offset scans, the gather. Any pointer may be NULL. */
+int ba_chaining_times(BaChaining* batch, float* fill_ms, float* pick_ms, float* gather_ms);
+void ba_chaining_destroy(BaChaining* batch);
+
 /* ---- every pair with its own block range. The reference's callers choose the range per pair -- percent_len(max(|q|, |r|), 0.01) ..=
  * percent_len(max(|q|, |r|), p) in /root/reference/examples/nanopore_bench_global.rs:144-171, Block::align(..., min..=max, x) in
  * src/scan_block.rs:847 --, while ba_batch_create takes one range for the whole batch. These calls bin the pairs by (min, max), align every bin as
