@@ -3061,8 +3061,9 @@ static int chaining_plan(const BaChainingParams& P, const uint64_t* anchor_first
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return anchor_first[a + 1] - anchor_first[a] > anchor_first[b + 1] - anchor_first[b]; });
     return 0;
 }
+// (the three anchor arrays are host arrays, or with from = hipMemcpyDeviceToDevice arrays on the batch's device: ba_chaining_create_seeded)
 static int chaining_load(BaChaining* e, const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor, const uint32_t* anchor_len, size_t n,
-                         const std::vector<uint32_t>& order, bool create) {
+                         const std::vector<uint32_t>& order, bool create, hipMemcpyKind from = hipMemcpyHostToDevice) {
     const uint64_t na = anchor_first[n];
     if (create) {
         e->cap_n = n; e->cap_anchors = na;
@@ -3079,9 +3080,18 @@ static int chaining_load(BaChaining* e, const uint64_t* anchor_first, const uint
     HIP_TRY(hipMemcpy(e->anchor_first.p, anchor_first, (n + 1) * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(e->order.p, order.data(), n * 4, hipMemcpyHostToDevice));
     if (na) {
-        HIP_TRY(hipMemcpy(e->q_anchor.p, q_anchor, na * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(e->r_anchor.p, r_anchor, na * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(e->anchor_len.p, anchor_len, na * 4, hipMemcpyHostToDevice));
+        if (from == hipMemcpyDeviceToDevice) {
+            // on the batch's own stream, which its kernels follow, and waited for: a device-to-device hipMemcpy need not have finished when it
+            // returns, and the source may be reloaded or freed as soon as this call is over
+            HIP_TRY(hipMemcpyAsync(e->q_anchor.p, q_anchor, na * 4, from, e->stream));
+            HIP_TRY(hipMemcpyAsync(e->r_anchor.p, r_anchor, na * 4, from, e->stream));
+            HIP_TRY(hipMemcpyAsync(e->anchor_len.p, anchor_len, na * 4, from, e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream));
+        } else {
+            HIP_TRY(hipMemcpy(e->q_anchor.p, q_anchor, na * 4, from));
+            HIP_TRY(hipMemcpy(e->r_anchor.p, r_anchor, na * 4, from));
+            HIP_TRY(hipMemcpy(e->anchor_len.p, anchor_len, na * 4, from));
+        }
     }
     e->n = (uint32_t)n; e->n_anchors = na;
     return 0;
@@ -3181,6 +3191,265 @@ int ba_chaining_times(BaChaining* e, float* fill_ms, float* pick_ms, float* gath
     return 0;
 }
 void ba_chaining_destroy(BaChaining* e) { delete e; }
+
+// ------------------------------------------------------------------ minimizer seeding (ba_seeding_*)
+// From the bytes of a problem to its raw hits, in the order ba_chaining_create demands (ba_seeding.hip; the rule: INTEGRATION.md,
+// "Seeding"). The host checks the arguments, orders sequences and problems longest first and sizes the buffers between the passes; the
+// sketch, the sort and the match are the device's.
+struct SeedingSet {   // a checked set of problems: the extent of its sequences in the caller's pool, the per-sequence arrays, the orders
+    const uint8_t* lo = nullptr; uint64_t bytes = 0;
+    std::vector<uint64_t> off; std::vector<uint32_t> len; std::vector<uint8_t> rc;   // 2n: the queries, then the references
+    std::vector<uint32_t> seq_order, sort_order, match_order;
+};
+struct BaSeeding {
+    int device = 0;
+    BaSeedingParams P{};
+    uint32_t n = 0;
+    uint64_t cap_n = 0, cap_raw = 0, seeds_cap = 0, q_seeds_cap = 0, hits_cap = 0, n_q_seeds = 0, n_seeds = 0, n_hits = 0;
+    hipStream_t stream = nullptr; hipEvent_t ev[8] = {};
+    DevBuf raw, seq_off, seq_len, seq_rc, seq_order, sort_order, match_order, counter, seed_cnt, seed_first, seed_pos, seed_code, q_key, hit_cnt, hit_first,
+           q_hit, r_hit, hit_len;
+    float sketch_ms = 0, sort_ms = 0, match_ms = 0;
+    bool ran = false;
+    ba::SeedingParams params() const {
+        ba::SeedingParams sp{};
+        sp.n = n; sp.k = P.k; sp.w = P.w; sp.max_occ = P.max_occ;
+        sp.pool = raw.as<uint8_t>(); sp.seq_off = seq_off.as<uint64_t>(); sp.seq_len = seq_len.as<uint32_t>(); sp.seq_rc = seq_rc.as<uint8_t>();
+        sp.seq_order = seq_order.as<uint32_t>(); sp.sort_order = sort_order.as<uint32_t>(); sp.match_order = match_order.as<uint32_t>();
+        sp.counter = counter.as<uint32_t>(); sp.seed_cnt = seed_cnt.as<uint32_t>(); sp.seed_first = seed_first.as<uint64_t>();
+        sp.seed_pos = seed_pos.as<uint32_t>(); sp.seed_code = seed_code.as<uint32_t>(); sp.q_key = q_key.as<uint64_t>();
+        sp.hit_cnt = hit_cnt.as<uint32_t>(); sp.hit_first = hit_first.as<uint64_t>();
+        sp.q_hit = q_hit.as<uint32_t>(); sp.r_hit = r_hit.as<uint32_t>(); sp.hit_len = hit_len.as<uint32_t>();
+        return sp;
+    }
+    ~BaSeeding() {
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+static int seeding_check_params(const BaSeedingParams& P) {
+    if (P.k < ba::SEEDING_MIN_K || P.k > ba::SEEDING_MAX_K) return fail("seeding: k must be between %u and %u (it is %u)", ba::SEEDING_MIN_K, ba::SEEDING_MAX_K, P.k);
+    if (P.w < 1 || P.w > ba::SEEDING_MAX_W) return fail("seeding: w must be between 1 and %u (it is %u)", ba::SEEDING_MAX_W, P.w);
+    if (P.max_occ < 1) return fail("seeding: max_occ must be at least 1");
+    return 0;
+}
+// Check a set of problems; -> the per-sequence arrays (offsets relative to the lowest byte any sequence has) and the three orders.
+static int seeding_plan(const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len, const uint8_t* strand,
+                        size_t n, SeedingSet& S) {
+    if (!pool || !q_off || !q_len || !r_off || !r_len) return fail("null argument");
+    if (n == 0 || n > (1u << 28)) return fail("a seeding batch must hold between 1 and 2^28 problems");
+    S = SeedingSet();
+    S.off.resize(2 * n); S.len.resize(2 * n); S.rc.assign(2 * n, 0);
+    const uint8_t* hi = nullptr;
+    for (size_t p = 0; p < n; p++) {
+        const uint8_t st = strand ? strand[p] : 0;
+        if (st > 1) return fail("problem %zu: strand must be 0 or 1", p);
+        if (q_len[p] >= ba::SEEDING_MAX_LEN || r_len[p] >= ba::SEEDING_MAX_LEN)
+            return fail("problem %zu: the sequences (query %u, reference %u bytes) must be shorter than 2^31 - 16 bytes", p, q_len[p], r_len[p]);
+        // (an empty sequence names no byte: whatever its offset, it does not widen what is uploaded)
+        if (q_len[p]) { const uint8_t* q = pool + q_off[p]; if (!S.lo || q < S.lo) S.lo = q; if (!hi || q + q_len[p] > hi) hi = q + q_len[p]; }
+        if (r_len[p]) { const uint8_t* r = pool + r_off[p]; if (!S.lo || r < S.lo) S.lo = r; if (!hi || r + r_len[p] > hi) hi = r + r_len[p]; }
+        S.off[p] = q_off[p]; S.off[n + p] = r_off[p];
+        S.len[p] = q_len[p]; S.len[n + p] = r_len[p];
+        S.rc[p] = st;
+    }
+    const uint64_t base = S.lo ? (uint64_t)(S.lo - pool) : 0;
+    for (size_t s = 0; s < 2 * n; s++) S.off[s] = S.len[s] ? S.off[s] - base : 0;
+    S.bytes = S.lo ? (uint64_t)(hi - S.lo) : 0;
+    auto by = [](const uint32_t* len, std::vector<uint32_t>& order, size_t m) {
+        order.resize(m);
+        for (size_t i = 0; i < m; i++) order[i] = (uint32_t)i;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return len[a] > len[b]; });
+    };
+    by(S.len.data(), S.seq_order, 2 * n);
+    by(q_len, S.sort_order, n);
+    by(r_len, S.match_order, n);
+    return 0;
+}
+static int seeding_load(BaSeeding* e, const SeedingSet& S, size_t n, bool create) {
+    if (create) {
+        e->cap_n = n; e->cap_raw = S.bytes;
+        if (e->raw.alloc(S.bytes) || e->seq_off.alloc(2 * n * 8) || e->seq_len.alloc(2 * n * 4) || e->seq_rc.alloc(2 * n) || e->seq_order.alloc(2 * n * 4) ||
+            e->sort_order.alloc(n * 4) || e->match_order.alloc(n * 4) || e->counter.alloc(4) || e->seed_cnt.alloc(2 * n * 4) ||
+            e->seed_first.alloc((2 * n + 1) * 8) || e->hit_cnt.alloc(n * 4) || e->hit_first.alloc((n + 1) * 8)) return 1;
+    } else {
+        if (n > e->cap_n) return fail("reload: %zu problems exceed the batch's capacity of %llu", n, (unsigned long long)e->cap_n);
+        if (S.bytes > e->cap_raw) return fail("reload: %llu sequence bytes exceed the batch's capacity of %llu", (unsigned long long)S.bytes, (unsigned long long)e->cap_raw);
+    }
+    e->n = 0; e->ran = false;   // (a failure from here on leaves no problems loaded)
+    if (S.bytes) HIP_TRY(hipMemcpy(e->raw.p, S.lo, S.bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->seq_off.p, S.off.data(), 2 * n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->seq_len.p, S.len.data(), 2 * n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->seq_rc.p, S.rc.data(), 2 * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->seq_order.p, S.seq_order.data(), 2 * n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->sort_order.p, S.sort_order.data(), n * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->match_order.p, S.match_order.data(), n * 4, hipMemcpyHostToDevice));
+    e->n = (uint32_t)n;
+    return 0;
+}
+BaSeeding* ba_seeding_create(const BaSeedingParams* params, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off,
+                             const uint32_t* r_len, const uint8_t* strand, uintptr_t n_problems) {
+    SeedingSet S;   // every argument is checked before the device is touched
+    if (!params) { fail("null argument"); return nullptr; }
+    if (seeding_check_params(*params) || seeding_plan(pool, q_off, q_len, r_off, r_len, strand, n_problems, S)) return nullptr;
+    if (ensure_device()) return nullptr;
+    std::unique_ptr<BaSeeding> e(new BaSeeding);
+    e->device = g_device; e->P = *params;
+    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { fail("hipStreamCreate failed"); return nullptr; }
+    for (hipEvent_t& ev : e->ev) if (hipEventCreate(&ev) != hipSuccess) { fail("hipEventCreate failed"); return nullptr; }
+    if (seeding_load(e.get(), S, n_problems, true)) return nullptr;
+    return e.release();
+}
+int ba_seeding_reload(BaSeeding* e, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len,
+                      const uint8_t* strand, uintptr_t n_problems) {
+    if (!e) return fail("null batch");
+    SeedingSet S;
+    if (seeding_plan(pool, q_off, q_len, r_off, r_len, strand, n_problems, S)) return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    return seeding_load(e, S, n_problems, false);
+}
+int ba_seeding_run(BaSeeding* e, float* kernel_ms) {
+    if (!e) return fail("null batch");
+    if (!e->n) return fail("no problems loaded (the last reload failed)");
+    HIP_TRY(hipSetDevice(e->device));
+    e->ran = false; e->sketch_ms = e->sort_ms = e->match_ms = 0; e->n_q_seeds = e->n_seeds = e->n_hits = 0;
+    const uint32_t n = e->n;
+    ba::SeedingParams sp = e->params();
+    // the sketch: count, scan, emit
+    HIP_TRY(hipMemsetAsync(e->counter.p, 0, 4, e->stream));
+    HIP_TRY(hipEventRecord(e->ev[0], e->stream));
+    HIP_TRY(ba_launch_seeding_sketch(e->stream, &sp, 0));
+    HIP_TRY(ba_launch_offsets(e->stream, sp.seed_cnt, e->seed_first.as<uint64_t>(), 2 * n));
+    HIP_TRY(hipEventRecord(e->ev[1], e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    uint64_t q_seeds = 0, seeds = 0;
+    HIP_TRY(hipMemcpy(&q_seeds, e->seed_first.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&seeds, e->seed_first.as<uint64_t>() + 2 * (size_t)n, 8, hipMemcpyDeviceToHost));
+    if (seeds > e->seeds_cap || !e->seed_pos.p) {   // (grow, never shrink)
+        if (e->seed_pos.alloc(seeds * 4) || e->seed_code.alloc(seeds * 4)) return 1;
+        e->seeds_cap = seeds;
+    }
+    if (q_seeds > e->q_seeds_cap || !e->q_key.p) {
+        if (e->q_key.alloc(q_seeds * 8)) return 1;
+        e->q_seeds_cap = q_seeds;
+    }
+    sp = e->params();
+    HIP_TRY(hipMemsetAsync(e->counter.p, 0, 4, e->stream));
+    HIP_TRY(hipEventRecord(e->ev[2], e->stream));
+    HIP_TRY(ba_launch_seeding_sketch(e->stream, &sp, 1));
+    HIP_TRY(hipEventRecord(e->ev[3], e->stream));
+    // the sort of the queries' keys; the match: count, scan
+    HIP_TRY(ba_launch_seeding_sort(e->stream, &sp));
+    HIP_TRY(hipEventRecord(e->ev[4], e->stream));
+    HIP_TRY(ba_launch_seeding_match(e->stream, &sp, 0));
+    HIP_TRY(ba_launch_offsets(e->stream, sp.hit_cnt, e->hit_first.as<uint64_t>(), n));
+    HIP_TRY(hipEventRecord(e->ev[5], e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    uint64_t hits = 0;
+    HIP_TRY(hipMemcpy(&hits, e->hit_first.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost));
+    if (hits > ba::SEEDING_MAX_HITS) {   // no emit: name the first problem that does not fit what the ones before it left
+        std::vector<uint32_t> per(n);
+        HIP_TRY(hipMemcpy(per.data(), e->hit_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        uint64_t left = ba::SEEDING_MAX_HITS;
+        size_t p = 0;
+        while (p + 1 < n && per[p] <= left) left -= per[p++];
+        return fail("seeding: the set has more than 2^28 hits: problem %zu alone has %s%u, with %llu left after the problems before it; lower max_occ "
+                    "(it is %u) or seed fewer problems at once", p, per[p] == 0xffffffffu ? "at least " : "", per[p], (unsigned long long)left, e->P.max_occ);
+    }
+    if (hits > e->hits_cap || !e->q_hit.p) {
+        if (e->q_hit.alloc(hits * 4) || e->r_hit.alloc(hits * 4) || e->hit_len.alloc(hits * 4)) return 1;
+        e->hits_cap = hits;
+    }
+    sp = e->params();
+    HIP_TRY(hipEventRecord(e->ev[6], e->stream));
+    HIP_TRY(ba_launch_seeding_match(e->stream, &sp, 1));
+    HIP_TRY(hipEventRecord(e->ev[7], e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    float a = 0, b = 0;
+    HIP_TRY(hipEventElapsedTime(&a, e->ev[0], e->ev[1]));
+    HIP_TRY(hipEventElapsedTime(&b, e->ev[2], e->ev[3]));
+    e->sketch_ms = a + b;
+    HIP_TRY(hipEventElapsedTime(&e->sort_ms, e->ev[3], e->ev[4]));
+    HIP_TRY(hipEventElapsedTime(&a, e->ev[4], e->ev[5]));
+    HIP_TRY(hipEventElapsedTime(&b, e->ev[6], e->ev[7]));
+    e->match_ms = a + b;
+    e->n_q_seeds = q_seeds; e->n_seeds = seeds; e->n_hits = hits;
+    e->ran = true;
+    if (kernel_ms) *kernel_ms = e->sketch_ms + e->sort_ms + e->match_ms;
+    return 0;
+}
+int ba_seeding_counts(BaSeeding* e, uint64_t* n_hits, uint64_t* n_q_seeds, uint64_t* n_r_seeds, uint32_t* hits_per_problem) {
+    if (!e) return fail("null batch");
+    if (!e->ran) return fail("ba_seeding_run has not been called");
+    HIP_TRY(hipSetDevice(e->device));
+    if (n_hits) *n_hits = e->n_hits;
+    if (n_q_seeds) *n_q_seeds = e->n_q_seeds;
+    if (n_r_seeds) *n_r_seeds = e->n_seeds - e->n_q_seeds;
+    return d2h(e->hit_cnt, hits_per_problem, e->n);
+}
+int ba_seeding_results(BaSeeding* e, uint64_t* hit_first, uint32_t* q_hit, uint32_t* r_hit, uint32_t* hit_len) {
+    if (!e) return fail("null batch");
+    if (!e->ran) return fail("ba_seeding_run has not been called");
+    HIP_TRY(hipSetDevice(e->device));
+    if (d2h(e->hit_first, hit_first, (size_t)e->n + 1) || d2h(e->q_hit, q_hit, e->n_hits) || d2h(e->r_hit, r_hit, e->n_hits) ||
+        d2h(e->hit_len, hit_len, e->n_hits)) return 1;
+    return 0;
+}
+int ba_seeding_sketch(BaSeeding* e, uint64_t* q_seed_first, uint32_t* q_seed_pos, uint32_t* q_seed_code, uint64_t* r_seed_first, uint32_t* r_seed_pos,
+                      uint32_t* r_seed_code) {
+    if (!e) return fail("null batch");
+    if (!e->ran) return fail("ba_seeding_run has not been called");
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t n = e->n, nq = e->n_q_seeds, nr = e->n_seeds - e->n_q_seeds;
+    if (d2h(e->seed_first, q_seed_first, n + 1) || d2h(e->seed_pos, q_seed_pos, nq) || d2h(e->seed_code, q_seed_code, nq)) return 1;
+    if (r_seed_first) {   // (the references' entries lie behind the queries')
+        HIP_TRY(hipMemcpy(r_seed_first, e->seed_first.as<uint64_t>() + n, (n + 1) * 8, hipMemcpyDeviceToHost));
+        for (size_t p = 0; p <= n; p++) r_seed_first[p] -= nq;
+    }
+    if (r_seed_pos) HIP_TRY(hipMemcpy(r_seed_pos, e->seed_pos.as<uint32_t>() + nq, nr * 4, hipMemcpyDeviceToHost));
+    if (r_seed_code) HIP_TRY(hipMemcpy(r_seed_code, e->seed_code.as<uint32_t>() + nq, nr * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+int ba_seeding_times(BaSeeding* e, float* sketch_ms, float* sort_ms, float* match_ms) {
+    if (!e) return fail("null batch");
+    if (sketch_ms) *sketch_ms = e->sketch_ms;
+    if (sort_ms) *sort_ms = e->sort_ms;
+    if (match_ms) *match_ms = e->match_ms;
+    return 0;
+}
+void ba_seeding_destroy(BaSeeding* e) { delete e; }
+
+// The hand-off: a BaChaining over the seeder's hits where they lie. hit_first is the only thing downloaded; the per-anchor conditions of
+// chaining_plan hold by construction (hit_len = k >= 4, sorted by (r_hit, q_hit), every hit inside sequences shorter than 2^31 - 16).
+BaChaining* ba_chaining_create_seeded(const BaChainingParams* params, BaSeeding* s) {
+    if (!params) { fail("null argument"); return nullptr; }
+    if (!s) { fail("null batch"); return nullptr; }
+    if (chaining_check_params(*params)) return nullptr;
+    if (!s->ran) { fail("ba_seeding_run has not been called"); return nullptr; }
+    if (hipSetDevice(s->device) != hipSuccess) { fail("hipSetDevice failed"); return nullptr; }
+    const size_t n = s->n;
+    std::vector<uint64_t> first(n + 1);
+    if (d2h(s->hit_first, first.data(), n + 1)) return nullptr;
+    for (size_t p = 0; p < n; p++) {
+        const uint64_t sum = (first[p + 1] - first[p]) * s->P.k;
+        if (sum * (uint64_t)params->match_w >= (1ull << 31)) {
+            fail("problem %zu: match_w * the sum of anchor_len must stay below 2^31 (it is %llu)", p, (unsigned long long)(sum * (uint64_t)params->match_w));
+            return nullptr;
+        }
+    }
+    std::vector<uint32_t> order(n);
+    for (size_t p = 0; p < n; p++) order[p] = (uint32_t)p;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return first[a + 1] - first[a] > first[b + 1] - first[b]; });
+    std::unique_ptr<BaChaining> e(new BaChaining);
+    e->device = s->device; e->P = *params;
+    e->ring = 128;
+    while (e->ring < params->lookback + 64u) e->ring <<= 1;
+    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { fail("hipStreamCreate failed"); return nullptr; }
+    for (hipEvent_t& ev : e->ev) if (hipEventCreate(&ev) != hipSuccess) { fail("hipEventCreate failed"); return nullptr; }
+    if (chaining_load(e.get(), first.data(), s->q_hit.as<uint32_t>(), s->r_hit.as<uint32_t>(), s->hit_len.as<uint32_t>(), n, order, true,
+                      hipMemcpyDeviceToDevice)) return nullptr;
+    return e.release();
+}
 
 int block_batch_align(int kind, const void* matrix, Gaps gaps, SizeRange size, int32_t x_drop, uint32_t mode, const uint8_t* pool,
                       const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len, uintptr_t n,

@@ -8,6 +8,7 @@
 #include "ba_exact.h"
 #include "ba_extend.h"
 #include "ba_params.h"
+#include "ba_seeding.h"
 #include "ba_stats.h"
 #include "ba_text.h"
 
@@ -76,6 +77,10 @@ hipError_t ba_launch_chain_gather(hipStream_t s, const ba::ChainParams* cp);
 hipError_t ba_launch_chaining_fill(hipStream_t s, const ba::ChainingParams* cp);
 hipError_t ba_launch_chaining_pick(hipStream_t s, const ba::ChainingParams* cp);
 hipError_t ba_launch_chaining_gather(hipStream_t s, const ba::ChainingParams* cp);
+// ba_seeding.hip (emit 0: the count pass, 1: the emit pass)
+hipError_t ba_launch_seeding_sketch(hipStream_t s, const ba::SeedingParams* sp, int emit);
+hipError_t ba_launch_seeding_sort(hipStream_t s, const ba::SeedingParams* sp);
+hipError_t ba_launch_seeding_match(hipStream_t s, const ba::SeedingParams* sp, int emit);
 // ba_stats.hip
 hipError_t ba_launch_stats(hipStream_t s, const ba::StatsParams* sp);
 hipError_t ba_launch_stats_extend(hipStream_t s, const ba::ExtendParams* ep, const ba::AlignStats* side, ba::AlignStats* out);

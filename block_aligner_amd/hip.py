@@ -74,6 +74,11 @@ class ChainingParamsC(C.Structure):
                 ("bandwidth", C.c_uint32), ("max_chains", C.c_uint32), ("min_score", C.c_int32), ("min_anchors", C.c_uint32)]
 
 
+class SeedingParamsC(C.Structure):
+    """struct BaSeedingParams (include/block_aligner_hip.h): the parameters of the ba_seeding_* calls."""
+    _fields_ = [("k", C.c_uint32), ("w", C.c_uint32), ("max_occ", C.c_uint32)]
+
+
 class AccuracyC(C.Structure):
     """struct BaAccuracy: what ba_accuracy_summary reports."""
     _fields_ = [("n", C.c_uint64), ("compared", C.c_uint64), ("skipped", C.c_uint64), ("wrong", C.c_uint64), ("below", C.c_uint64),
@@ -217,6 +222,17 @@ def lib() -> C.CDLL:
         L.ba_chaining_dp.argtypes = [vp, vp, vp]
         L.ba_chaining_times.argtypes = [vp, vp, vp, vp]
         L.ba_chaining_destroy.argtypes = [vp]
+        L.ba_chaining_create_seeded.restype = vp
+        L.ba_chaining_create_seeded.argtypes = [C.POINTER(ChainingParamsC), vp]
+        L.ba_seeding_create.restype = vp
+        L.ba_seeding_create.argtypes = [C.POINTER(SeedingParamsC), vp, vp, vp, vp, vp, vp, sz]
+        L.ba_seeding_reload.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz]
+        L.ba_seeding_run.argtypes = [vp, C.POINTER(C.c_float)]
+        L.ba_seeding_counts.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), vp]
+        L.ba_seeding_results.argtypes = [vp] * 5
+        L.ba_seeding_sketch.argtypes = [vp] * 7
+        L.ba_seeding_times.argtypes = [vp, vp, vp, vp]
+        L.ba_seeding_destroy.argtypes = [vp]
         for f, fields in (("ba_batch", 6), ("ba_sized_batch", 6), ("ba_multibatch", 6), ("ba_extend_batch", 10)):   # the calls of _Batch
             getattr(L, f"{f}_run").argtypes = [vp, C.POINTER(C.c_float)]
             getattr(L, f"{f}_results").argtypes = [vp] * (1 + fields)
@@ -1055,6 +1071,23 @@ class AnchorChainer:
         if not self._h:
             raise RuntimeError(last_error())
 
+    @classmethod
+    def from_seeder(cls, match_w: int, drift_cost: int, skip_cost: int, lookback: int, max_dist: int, bandwidth: int, max_chains: int, min_score: int,
+                    min_anchors: int, seeder: "Seeder"):
+        """A chainer over the hits of a Seeder that has run (ba_chaining_create_seeded): the hits go from the seeder's buffers to the chainer's
+        on the device, without a round trip through the host. The chainer is like any other afterwards and does not depend on the seeder."""
+        self = cls.__new__(cls)
+        self._h = None
+        self._res = None
+        self.params = ChainingParamsC(match_w, drift_cost, skip_cost, lookback, max_dist, bandwidth, max_chains, min_score, min_anchors)
+        h = lib().ba_chaining_create_seeded(C.byref(self.params), seeder._h)
+        if not h:
+            raise RuntimeError(last_error())
+        self._h = h
+        self.n = seeder.n
+        self.n_anchors = seeder.n_hits
+        return self
+
     def _call(self, name, *args):
         if getattr(lib(), f"ba_chaining_{name}")(self._h, *args):
             raise RuntimeError(last_error())
@@ -1114,6 +1147,93 @@ class AnchorChainer:
     def close(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.ba_chaining_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class Seeder:
+    """Minimizer seeding on the device (ba_seeding_*; the rule: INTEGRATION.md, "Seeding"). Problem p is the read q = pool[q_off[p]:+q_len[p]]
+    against the reference stretch r = pool[r_off[p]:+r_len[p]] on strand[p] (1: q is read as its reverse complement, and query positions are
+    in that frame, the chain batch's): the pair layout of ChainBatchAligner. k = 4 .. 16, w = 1 .. 64; a code that more than max_occ of the
+    query's selected k-mers have gives no hits. Arguments are checked before the device is touched.
+
+    run() computes sketches and hits and returns the kernels' time; results() gives the hits of every problem, sorted by (r_hit, q_hit), as
+    AnchorChainer takes them; AnchorChainer.from_seeder(..., seeder) chains them where they lie."""
+
+    @staticmethod
+    def _arrays(pool, q_off, q_len, r_off, r_len, strand):
+        a = _pair_arrays(pool, q_off, q_len, r_off, r_len) + [None if strand is None else np.ascontiguousarray(strand, dtype=np.uint8)]
+        n = len(a[2])
+        if any(len(x) != n for x in a[1:] if x is not None):
+            raise ValueError("q_off, q_len, r_off, r_len and strand must have one entry per problem")
+        return a
+
+    def __init__(self, k: int, w: int, max_occ: int, pool, q_off, q_len, r_off, r_len, strand=None):
+        a = self._arrays(pool, q_off, q_len, r_off, r_len, strand)
+        self.n = len(a[2])
+        self.params = SeedingParamsC(k, w, max_occ)
+        self._counts = None
+        self._h = lib().ba_seeding_create(C.byref(self.params), *_ptrs(a), self.n)
+        if not self._h:
+            raise RuntimeError(last_error())
+
+    def _call(self, name, *args):
+        if getattr(lib(), f"ba_seeding_{name}")(self._h, *args):
+            raise RuntimeError(last_error())
+
+    def reload(self, pool, q_off, q_len, r_off, r_len, strand=None) -> None:
+        """Replace the problems and keep parameters and device buffers (ba_seeding_reload): no more problems and no more bytes than at first."""
+        a = self._arrays(pool, q_off, q_len, r_off, r_len, strand)
+        self._counts = None
+        self._call("reload", *_ptrs(a), len(a[2]))
+        self.n = len(a[2])
+
+    def run(self) -> float:
+        ms = C.c_float()
+        self._counts = None
+        self._call("run", C.byref(ms))
+        return ms.value
+
+    def counts(self):
+        """After run() -> dict: n_hits, n_q_seeds, n_r_seeds and hits_per_problem."""
+        if self._counts is None:
+            h, q, r = C.c_uint64(), C.c_uint64(), C.c_uint64()
+            per = np.zeros(self.n, np.uint32)
+            self._call("counts", C.byref(h), C.byref(q), C.byref(r), per.ctypes.data)
+            self._counts = dict(n_hits=h.value, n_q_seeds=q.value, n_r_seeds=r.value, hits_per_problem=per)
+        return self._counts
+
+    @property
+    def n_hits(self) -> int:
+        return self.counts()["n_hits"]
+
+    def results(self):
+        """After run() -> (hit_first, q_hit, r_hit, hit_len, hits_per_problem): AnchorChainer's anchor_first, q_anchor, r_anchor and anchor_len."""
+        c = self.counts()
+        first = np.zeros(self.n + 1, np.uint64)
+        q, r, ln = (np.zeros(c["n_hits"], np.uint32) for _ in range(3))
+        self._call("results", first.ctypes.data, q.ctypes.data, r.ctypes.data, ln.ctypes.data)
+        return first, q, r, ln, c["hits_per_problem"]
+
+    def sketch(self):
+        """After run(): the raw sketches in position order -> dict: q_first, q_pos, q_code, r_first, r_pos, r_code (first: one entry per
+        problem and one more)."""
+        c = self.counts()
+        out = dict(q_first=np.zeros(self.n + 1, np.uint64), q_pos=np.zeros(c["n_q_seeds"], np.uint32), q_code=np.zeros(c["n_q_seeds"], np.uint32),
+                   r_first=np.zeros(self.n + 1, np.uint64), r_pos=np.zeros(c["n_r_seeds"], np.uint32), r_code=np.zeros(c["n_r_seeds"], np.uint32))
+        self._call("sketch", *_ptrs(out.values()))
+        return out
+
+    def times(self):
+        """Device milliseconds of the last run(): the sketch, the sort, the match."""
+        a, b, c = C.c_float(), C.c_float(), C.c_float()
+        self._call("times", C.byref(a), C.byref(b), C.byref(c))
+        return dict(sketch_ms=a.value, sort_ms=b.value, match_ms=c.value)
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.ba_seeding_destroy(self._h)
             self._h = None
 
     __del__ = close

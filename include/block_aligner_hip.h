@@ -405,6 +405,54 @@ int ba_chaining_dp(BaChaining* batch, int32_t* f, int32_t* pred);
 int ba_chaining_times(BaChaining* batch, float* fill_ms, float* pick_ms, float* gather_ms);
 void ba_chaining_destroy(BaChaining* batch);
 
+/* ---- minimizer seeding on the device: from the bytes of a problem (one read against one reference stretch on one strand, in the pair layout
+ * of ba_chain_batch_create: q = pool[q_off[p] .. + q_len[p]), r likewise, strand[p] or NULL) to its raw hits, in the order ba_chaining_create
+ * demands ("Seeding": the rule, normative; all integer arithmetic).
+ *
+ * With strand[p] = 1 the query is read as its reverse complement (uppercased, A<->T, C<->G, every other byte as it is), and every query
+ * position is in that frame: the chain batch's. A k-mer's code takes A, C, G, T (either case) as 0 .. 3, the first base most significant; a
+ * k-mer over any other byte is invalid: never selected, never compared. h(x), in uint32: x ^= 0x9e3779b9; x ^= x >> 16; x *= 0x85ebca6b;
+ * x ^= x >> 13; x *= 0xc2b2ae35; x ^= x >> 16 (a bijection). A sequence with nk k-mers has the windows [s, s + w) for s = 0 .. nk - w, or the
+ * one window [0, nk) if nk <= w; a window selects its valid k-mer with the smallest h, the leftmost of equals; the sketch is the set of
+ * selected positions, ascending. Per problem the reference's sketch is walked in position order: an entry (j, c) whose code occurs m times
+ * among the query's selected entries gives, if 1 <= m <= max_occ, the hits (q_hit = i, r_hit = j, hit_len = k) for those m positions i,
+ * ascending. The hits of a problem are therefore sorted by (r_hit, q_hit), lie inside their sequences and end below 2^31.
+ *
+ * Every argument is checked before the device is touched (k, w, max_occ out of range; a strand that is not 0 or 1; a sequence of 2^31 - 16
+ * bytes or more: a message naming the problem). A set may hold at most 2^28 hits, the chainer's limit: ba_seeding_run fails otherwise. */
+struct BaSeedingParams {
+    uint32_t k;        /* 4 .. 16: bases of a k-mer */
+    uint32_t w;        /* 1 .. 64: k-mers of a window (1: every valid k-mer is selected) */
+    uint32_t max_occ;  /* >= 1: a code that more of the query's selected k-mers have gives no hits; 0xffffffff: no cap in practice */
+};
+typedef struct BaSeeding BaSeeding;
+BaSeeding* ba_seeding_create(const struct BaSeedingParams* params, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len,
+                             const uint64_t* r_off, const uint32_t* r_len, const uint8_t* strand, uintptr_t n_problems);
+/* Replace the problems and keep parameters and device buffers: the new set must hold no more problems and no more sequence bytes. */
+int ba_seeding_reload(BaSeeding* batch, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off,
+                      const uint32_t* r_len, const uint8_t* strand, uintptr_t n_problems);
+/* The sketch of every sequence, the sort of the queries' entries by code, the match. kernel_ms (optional): the sum of their HIP-event times.
+ * Fails, naming a problem, if the set has more than 2^28 hits; the batch can be reloaded and run again. */
+int ba_seeding_run(BaSeeding* batch, float* kernel_ms);
+/* After a run: hits, selected k-mers of all queries and of all references, and the hits of every problem (n_problems entries). Any pointer
+ * may be NULL. */
+int ba_seeding_counts(BaSeeding* batch, uint64_t* n_hits, uint64_t* n_q_seeds, uint64_t* n_r_seeds, uint32_t* hits_per_problem);
+/* After a run; any pointer may be NULL. hit_first (n_problems + 1 entries): where a problem's hits start; per hit (n_hits entries) q_hit, r_hit
+ * and hit_len (= k): ba_chaining_create's anchor_first, q_anchor, r_anchor and anchor_len as they stand. */
+int ba_seeding_results(BaSeeding* batch, uint64_t* hit_first, uint32_t* q_hit, uint32_t* r_hit, uint32_t* hit_len);
+/* After a run: the raw sketches, in position order; any pointer may be NULL. q_seed_first / r_seed_first (n_problems + 1 entries each):
+ * where the entries of a problem's query / reference start; per entry (n_q_seeds / n_r_seeds of them) its position and its code. */
+int ba_seeding_sketch(BaSeeding* batch, uint64_t* q_seed_first, uint32_t* q_seed_pos, uint32_t* q_seed_code, uint64_t* r_seed_first,
+                      uint32_t* r_seed_pos, uint32_t* r_seed_code);
+/* Device times of the last run in ms: the sketch's two passes, the sort, the match's two passes (each with its scan). Any pointer may be NULL. */
+int ba_seeding_times(BaSeeding* batch, float* sketch_ms, float* sort_ms, float* match_ms);
+void ba_seeding_destroy(BaSeeding* batch);
+/* The hand-off: a chaining batch over the hits of a seeder that has run, copied device to device on the seeder's device (hit_first is the
+ * only thing that passes through the host). match_w * k * the hits of a problem must stay below 2^31. The handle is a BaChaining like any
+ * other -- run, counts, results, dp, times, destroy; reload takes host arrays that fit its capacity -- and does not depend on the seeder
+ * afterwards: the copy is complete when the call returns, and the seeder may be reloaded, run again or destroyed at once. */
+BaChaining* ba_chaining_create_seeded(const struct BaChainingParams* params, BaSeeding* ran);
+
 /* ---- every pair with its own block range. The reference's callers choose the range per pair -- percent_len(max(|q|, |r|), 0.01) ..=
  * percent_len(max(|q|, |r|), p) in /root/reference/examples/nanopore_bench_global.rs:144-171, Block::align(..., min..=max, x) in
  * src/scan_block.rs:847 --, while ba_batch_create takes one range for the whole batch. These calls bin the pairs by (min, max), align every bin as
