@@ -3201,16 +3201,35 @@ struct SeedingSet {   // a checked set of problems: the extent of its sequences 
     std::vector<uint64_t> off; std::vector<uint32_t> len; std::vector<uint8_t> rc;   // 2n: the queries, then the references
     std::vector<uint32_t> seq_order, sort_order, match_order;
 };
+struct IndexData {   // a reference index on the device (ba_ref_index_*): shared by the index and the seeders made from it, freed with the last
+    int device = 0;
+    uint32_t k = 0, w = 0, prefix_bits = 0, longest_run = 0;
+    uint64_t ref_len = 0, n_entries = 0;
+    DevBuf key, table;   // n_entries keys code << 32 | pos, ascending; (1 << prefix_bits) + 1 bounds
+};
 struct BaSeeding {
     int device = 0;
     BaSeedingParams P{};
     uint32_t n = 0;
     uint64_t cap_n = 0, cap_raw = 0, seeds_cap = 0, q_seeds_cap = 0, hits_cap = 0, n_q_seeds = 0, n_seeds = 0, n_hits = 0;
-    hipStream_t stream = nullptr; hipEvent_t ev[8] = {};
+    hipStream_t stream = nullptr; hipEvent_t ev[9] = {};
     DevBuf raw, seq_off, seq_len, seq_rc, seq_order, sort_order, match_order, counter, seed_cnt, seed_first, seed_pos, seed_code, q_key, hit_cnt, hit_first,
            q_hit, r_hit, hit_len;
+    std::shared_ptr<const IndexData> index;   // an indexed seeder (ba_seeding_create_indexed): every problem's reference is the index's
+    uint32_t max_ref_occ = 0;
+    DevBuf hit_key;                           // ... its hits as sort keys, as large as the hit arrays
     float sketch_ms = 0, sort_ms = 0, match_ms = 0;
     bool ran = false;
+    ba::IndexLookupParams lookup_params() const {
+        ba::IndexLookupParams lp{};
+        lp.n = n; lp.k = P.k; lp.max_occ = P.max_occ; lp.max_ref_occ = max_ref_occ;
+        lp.prefix_bits = index->prefix_bits; lp.n_entries = (uint32_t)index->n_entries;
+        lp.order = sort_order.as<uint32_t>(); lp.seed_first = seed_first.as<uint64_t>(); lp.q_key = q_key.as<uint64_t>();
+        lp.key = index->key.as<uint64_t>(); lp.table = index->table.as<uint32_t>();
+        lp.hit_cnt = hit_cnt.as<uint32_t>(); lp.hit_first = hit_first.as<uint64_t>(); lp.hit_key = hit_key.as<uint64_t>();
+        lp.q_hit = q_hit.as<uint32_t>(); lp.r_hit = r_hit.as<uint32_t>(); lp.hit_len = hit_len.as<uint32_t>();
+        return lp;
+    }
     ba::SeedingParams params() const {
         ba::SeedingParams sp{};
         sp.n = n; sp.k = P.k; sp.w = P.w; sp.max_occ = P.max_occ;
@@ -3234,9 +3253,10 @@ static int seeding_check_params(const BaSeedingParams& P) {
     return 0;
 }
 // Check a set of problems; -> the per-sequence arrays (offsets relative to the lowest byte any sequence has) and the three orders.
+// indexed: the problems of an indexed seeder, reads against a reference index: r_off and r_len are not read, every reference is empty.
 static int seeding_plan(const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len, const uint8_t* strand,
-                        size_t n, SeedingSet& S) {
-    if (!pool || !q_off || !q_len || !r_off || !r_len) return fail("null argument");
+                        size_t n, SeedingSet& S, bool indexed = false) {
+    if (!pool || !q_off || !q_len || (!indexed && (!r_off || !r_len))) return fail("null argument");
     if (n == 0 || n > (1u << 28)) return fail("a seeding batch must hold between 1 and 2^28 problems");
     S = SeedingSet();
     S.off.resize(2 * n); S.len.resize(2 * n); S.rc.assign(2 * n, 0);
@@ -3244,13 +3264,14 @@ static int seeding_plan(const uint8_t* pool, const uint64_t* q_off, const uint32
     for (size_t p = 0; p < n; p++) {
         const uint8_t st = strand ? strand[p] : 0;
         if (st > 1) return fail("problem %zu: strand must be 0 or 1", p);
-        if (q_len[p] >= ba::SEEDING_MAX_LEN || r_len[p] >= ba::SEEDING_MAX_LEN)
-            return fail("problem %zu: the sequences (query %u, reference %u bytes) must be shorter than 2^31 - 16 bytes", p, q_len[p], r_len[p]);
+        const uint32_t rl = indexed ? 0u : r_len[p];
+        if (q_len[p] >= ba::SEEDING_MAX_LEN || rl >= ba::SEEDING_MAX_LEN)
+            return fail("problem %zu: the sequences (query %u, reference %u bytes) must be shorter than 2^31 - 16 bytes", p, q_len[p], rl);
         // (an empty sequence names no byte: whatever its offset, it does not widen what is uploaded)
         if (q_len[p]) { const uint8_t* q = pool + q_off[p]; if (!S.lo || q < S.lo) S.lo = q; if (!hi || q + q_len[p] > hi) hi = q + q_len[p]; }
-        if (r_len[p]) { const uint8_t* r = pool + r_off[p]; if (!S.lo || r < S.lo) S.lo = r; if (!hi || r + r_len[p] > hi) hi = r + r_len[p]; }
-        S.off[p] = q_off[p]; S.off[n + p] = r_off[p];
-        S.len[p] = q_len[p]; S.len[n + p] = r_len[p];
+        if (rl) { const uint8_t* r = pool + r_off[p]; if (!S.lo || r < S.lo) S.lo = r; if (!hi || r + rl > hi) hi = r + rl; }
+        S.off[p] = q_off[p]; S.off[n + p] = rl ? r_off[p] : 0;
+        S.len[p] = q_len[p]; S.len[n + p] = rl;
         S.rc[p] = st;
     }
     const uint64_t base = S.lo ? (uint64_t)(S.lo - pool) : 0;
@@ -3263,7 +3284,7 @@ static int seeding_plan(const uint8_t* pool, const uint64_t* q_off, const uint32
     };
     by(S.len.data(), S.seq_order, 2 * n);
     by(q_len, S.sort_order, n);
-    by(r_len, S.match_order, n);
+    by(S.len.data() + n, S.match_order, n);
     return 0;
 }
 static int seeding_load(BaSeeding* e, const SeedingSet& S, size_t n, bool create) {
@@ -3303,6 +3324,7 @@ BaSeeding* ba_seeding_create(const BaSeedingParams* params, const uint8_t* pool,
 int ba_seeding_reload(BaSeeding* e, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len,
                       const uint8_t* strand, uintptr_t n_problems) {
     if (!e) return fail("null batch");
+    if (e->index) return fail("ba_seeding_reload: the seeder was created over a reference index; call ba_seeding_reload_indexed");
     SeedingSet S;
     if (seeding_plan(pool, q_off, q_len, r_off, r_len, strand, n_problems, S)) return 1;
     HIP_TRY(hipSetDevice(e->device));
@@ -3341,7 +3363,9 @@ int ba_seeding_run(BaSeeding* e, float* kernel_ms) {
     // the sort of the queries' keys; the match: count, scan
     HIP_TRY(ba_launch_seeding_sort(e->stream, &sp));
     HIP_TRY(hipEventRecord(e->ev[4], e->stream));
-    HIP_TRY(ba_launch_seeding_match(e->stream, &sp, 0));
+    ba::IndexLookupParams lp{};   // an indexed seeder: the lookup in the index in place of the match
+    if (e->index) { lp = e->lookup_params(); HIP_TRY(ba_launch_index_lookup(e->stream, &lp, 0)); }
+    else HIP_TRY(ba_launch_seeding_match(e->stream, &sp, 0));
     HIP_TRY(ba_launch_offsets(e->stream, sp.hit_cnt, e->hit_first.as<uint64_t>(), n));
     HIP_TRY(hipEventRecord(e->ev[5], e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -3357,19 +3381,28 @@ int ba_seeding_run(BaSeeding* e, float* kernel_ms) {
                     "(it is %u) or seed fewer problems at once", p, per[p] == 0xffffffffu ? "at least " : "", per[p], (unsigned long long)left, e->P.max_occ);
     }
     if (hits > e->hits_cap || !e->q_hit.p) {
-        if (e->q_hit.alloc(hits * 4) || e->r_hit.alloc(hits * 4) || e->hit_len.alloc(hits * 4)) return 1;
+        if (e->q_hit.alloc(hits * 4) || e->r_hit.alloc(hits * 4) || e->hit_len.alloc(hits * 4) || (e->index && e->hit_key.alloc(hits * 8))) return 1;
         e->hits_cap = hits;
     }
     sp = e->params();
     HIP_TRY(hipEventRecord(e->ev[6], e->stream));
-    HIP_TRY(ba_launch_seeding_match(e->stream, &sp, 1));
-    HIP_TRY(hipEventRecord(e->ev[7], e->stream));
+    if (e->index) {   // the emit pass writes sort keys; the sort of every problem's keys unpacks them
+        lp = e->lookup_params();
+        HIP_TRY(ba_launch_index_lookup(e->stream, &lp, 1));
+        HIP_TRY(hipEventRecord(e->ev[7], e->stream));
+        HIP_TRY(ba_launch_index_hit_sort(e->stream, &lp));
+    } else {
+        HIP_TRY(ba_launch_seeding_match(e->stream, &sp, 1));
+        HIP_TRY(hipEventRecord(e->ev[7], e->stream));
+    }
+    HIP_TRY(hipEventRecord(e->ev[8], e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     float a = 0, b = 0;
     HIP_TRY(hipEventElapsedTime(&a, e->ev[0], e->ev[1]));
     HIP_TRY(hipEventElapsedTime(&b, e->ev[2], e->ev[3]));
     e->sketch_ms = a + b;
     HIP_TRY(hipEventElapsedTime(&e->sort_ms, e->ev[3], e->ev[4]));
+    if (e->index) { HIP_TRY(hipEventElapsedTime(&a, e->ev[7], e->ev[8])); e->sort_ms += a; }   // the sort of the hits
     HIP_TRY(hipEventElapsedTime(&a, e->ev[4], e->ev[5]));
     HIP_TRY(hipEventElapsedTime(&b, e->ev[6], e->ev[7]));
     e->match_ms = a + b;
@@ -3449,6 +3482,160 @@ BaChaining* ba_chaining_create_seeded(const BaChainingParams* params, BaSeeding*
     if (chaining_load(e.get(), first.data(), s->q_hit.as<uint32_t>(), s->r_hit.as<uint32_t>(), s->hit_len.as<uint32_t>(), n, order, true,
                       hipMemcpyDeviceToDevice)) return nullptr;
     return e.release();
+}
+
+// ------------------------------------------------------------------ the reference index (ba_ref_index_*, ba_seeding_*_indexed)
+// One reference's sketch, built once, and seeders whose problems are reads against all of it (ba_index.hip; the rule: INTEGRATION.md,
+// "Reference index"). The build keeps the reference's bytes on the device only until the keys are written.
+struct BaRefIndex {
+    std::shared_ptr<IndexData> d;
+    float sketch_ms = 0, sort_ms = 0, table_ms = 0;
+};
+struct IndexBuildTools {   // the stream and the events of one build
+    hipStream_t stream = nullptr; hipEvent_t ev[6] = {};
+    ~IndexBuildTools() {
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+static int index_build(BaRefIndex* x, const uint8_t* ref) {
+    IndexData& D = *x->d;
+    const uint32_t len = (uint32_t)D.ref_len, k = D.k, w = D.w;
+    const uint32_t nk = len >= k ? len - k + 1u : 0u, nw = nk == 0u ? 0u : nk > w ? nk - w + 1u : 1u;
+    IndexBuildTools T;
+    DevBuf raw, counter, span_cnt, span_first, unsorted, temp, longest;
+    ba::IndexParams ip{};
+    ip.k = k; ip.w = w; ip.len = len; ip.n_windows = nw; ip.n_spans = (nw + ba::INDEX_SPAN - 1u) / ba::INDEX_SPAN; ip.prefix_bits = D.prefix_bits;
+    HIP_TRY(hipStreamCreateWithFlags(&T.stream, hipStreamNonBlocking));
+    for (hipEvent_t& ev : T.ev) HIP_TRY(hipEventCreate(&ev));
+    if (raw.alloc(len) || counter.alloc(4) || span_cnt.alloc((size_t)ip.n_spans * 4) || span_first.alloc(((size_t)ip.n_spans + 1) * 8) || longest.alloc(4) ||
+        D.table.alloc(((size_t)(1u << ip.prefix_bits) + 1) * 4)) return 1;
+    if (len) HIP_TRY(hipMemcpy(raw.p, ref, len, hipMemcpyHostToDevice));
+    ip.ref = raw.as<uint8_t>(); ip.counter = counter.as<uint32_t>(); ip.span_cnt = span_cnt.as<uint32_t>(); ip.span_first = span_first.as<uint64_t>();
+    ip.table = D.table.as<uint32_t>(); ip.longest_run = longest.as<uint32_t>();
+    // the sketch: count, scan, emit
+    HIP_TRY(hipMemsetAsync(counter.p, 0, 4, T.stream));
+    HIP_TRY(hipEventRecord(T.ev[0], T.stream));
+    HIP_TRY(ba_launch_index_sketch(T.stream, &ip, 0));
+    HIP_TRY(ba_launch_offsets(T.stream, ip.span_cnt, span_first.as<uint64_t>(), ip.n_spans));
+    HIP_TRY(hipEventRecord(T.ev[1], T.stream));
+    HIP_TRY(hipStreamSynchronize(T.stream));
+    uint64_t total = 0;
+    HIP_TRY(hipMemcpy(&total, span_first.as<uint64_t>() + ip.n_spans, 8, hipMemcpyDeviceToHost));
+    if (unsorted.alloc(total * 8) || D.key.alloc(total * 8)) return 1;
+    ip.n_entries = (uint32_t)total; ip.unsorted = unsorted.as<uint64_t>(); ip.key = D.key.as<uint64_t>();
+    HIP_TRY(hipMemsetAsync(counter.p, 0, 4, T.stream));
+    HIP_TRY(hipEventRecord(T.ev[2], T.stream));
+    HIP_TRY(ba_launch_index_sketch(T.stream, &ip, 1));
+    HIP_TRY(hipEventRecord(T.ev[3], T.stream));
+    // the sort of the keys (a code has 2k bits above the position's 32), the table
+    if (total) {
+        size_t temp_bytes = 0;
+        HIP_TRY(ba_launch_index_sort(T.stream, ip.unsorted, D.key.as<uint64_t>(), ip.n_entries, 32u + 2u * k, nullptr, &temp_bytes));
+        if (temp.alloc(temp_bytes)) return 1;
+        HIP_TRY(ba_launch_index_sort(T.stream, ip.unsorted, D.key.as<uint64_t>(), ip.n_entries, 32u + 2u * k, temp.p, &temp_bytes));
+    }
+    HIP_TRY(hipEventRecord(T.ev[4], T.stream));
+    HIP_TRY(hipMemsetAsync(longest.p, 0, 4, T.stream));
+    HIP_TRY(ba_launch_index_table(T.stream, &ip));
+    HIP_TRY(hipEventRecord(T.ev[5], T.stream));
+    HIP_TRY(hipStreamSynchronize(T.stream));
+    HIP_TRY(hipMemcpy(&D.longest_run, longest.p, 4, hipMemcpyDeviceToHost));
+    D.n_entries = total;
+    float a = 0, b = 0;
+    HIP_TRY(hipEventElapsedTime(&a, T.ev[0], T.ev[1]));
+    HIP_TRY(hipEventElapsedTime(&b, T.ev[2], T.ev[3]));
+    x->sketch_ms = a + b;
+    HIP_TRY(hipEventElapsedTime(&x->sort_ms, T.ev[3], T.ev[4]));
+    HIP_TRY(hipEventElapsedTime(&x->table_ms, T.ev[4], T.ev[5]));
+    return 0;
+}
+BaRefIndex* ba_ref_index_create(uint32_t k, uint32_t w, const uint8_t* ref, uint64_t ref_len) {
+    if (seeding_check_params(BaSeedingParams{k, w, 1})) return nullptr;   // every argument is checked before the device is touched
+    if (!ref) { fail("null argument"); return nullptr; }
+    if (ref_len >= ba::SEEDING_MAX_LEN) { fail("the reference (%llu bytes) must be shorter than 2^31 - 16 bytes", (unsigned long long)ref_len); return nullptr; }
+    if (ensure_device()) return nullptr;
+    std::unique_ptr<BaRefIndex> x(new BaRefIndex);
+    x->d = std::make_shared<IndexData>();
+    x->d->device = g_device; x->d->k = k; x->d->w = w; x->d->ref_len = ref_len;
+    x->d->prefix_bits = 2u * k < ba::INDEX_MAX_PREFIX_BITS ? 2u * k : ba::INDEX_MAX_PREFIX_BITS;
+    if (index_build(x.get(), ref)) return nullptr;
+    return x.release();
+}
+int ba_ref_index_counts(BaRefIndex* x, uint64_t* n_entries, uint32_t* k, uint32_t* w, uint64_t* ref_len, uint32_t* longest_run) {
+    if (!x) return fail("null index");
+    if (n_entries) *n_entries = x->d->n_entries;
+    if (k) *k = x->d->k;
+    if (w) *w = x->d->w;
+    if (ref_len) *ref_len = x->d->ref_len;
+    if (longest_run) *longest_run = x->d->longest_run;
+    return 0;
+}
+int ba_ref_index_entries(BaRefIndex* x, uint32_t* code, uint32_t* pos) {
+    if (!x) return fail("null index");
+    HIP_TRY(hipSetDevice(x->d->device));
+    std::vector<uint64_t> key(x->d->n_entries);
+    if (d2h(x->d->key, key.data(), key.size())) return 1;
+    for (size_t i = 0; i < key.size(); i++) {
+        if (code) code[i] = (uint32_t)(key[i] >> 32);
+        if (pos) pos[i] = (uint32_t)key[i];
+    }
+    return 0;
+}
+int ba_ref_index_times(BaRefIndex* x, float* sketch_ms, float* sort_ms, float* table_ms) {
+    if (!x) return fail("null index");
+    if (sketch_ms) *sketch_ms = x->sketch_ms;
+    if (sort_ms) *sort_ms = x->sort_ms;
+    if (table_ms) *table_ms = x->table_ms;
+    return 0;
+}
+void ba_ref_index_destroy(BaRefIndex* x) { delete x; }
+
+// (The index is looked at last: the other arguments are judged without one, so without a device as well.)
+BaSeeding* ba_seeding_create_indexed(BaRefIndex* x, uint32_t max_occ, uint32_t max_ref_occ, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len,
+                                     const uint8_t* strand, uintptr_t n_problems) {
+    SeedingSet S;
+    if (max_occ < 1) { fail("seeding: max_occ must be at least 1"); return nullptr; }
+    if (max_ref_occ < 1) { fail("seeding: max_ref_occ must be at least 1"); return nullptr; }
+    if (seeding_plan(pool, q_off, q_len, nullptr, nullptr, strand, n_problems, S, true)) return nullptr;   // (empty references: the sketch skips them)
+    if (!x) { fail("null index"); return nullptr; }
+    if (hipSetDevice(x->d->device) != hipSuccess) { fail("hipSetDevice failed"); return nullptr; }   // the seeder lives on the index's device
+    std::unique_ptr<BaSeeding> e(new BaSeeding);
+    e->device = x->d->device; e->P = BaSeedingParams{x->d->k, x->d->w, max_occ};
+    e->index = x->d; e->max_ref_occ = max_ref_occ;
+    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { fail("hipStreamCreate failed"); return nullptr; }
+    for (hipEvent_t& ev : e->ev) if (hipEventCreate(&ev) != hipSuccess) { fail("hipEventCreate failed"); return nullptr; }
+    if (seeding_load(e.get(), S, n_problems, true)) return nullptr;
+    return e.release();
+}
+int ba_seeding_reload_indexed(BaSeeding* e, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint8_t* strand, uintptr_t n_problems) {
+    if (!e) return fail("null batch");
+    if (!e->index) return fail("ba_seeding_reload_indexed: the seeder was created without a reference index; call ba_seeding_reload");
+    SeedingSet S;
+    if (seeding_plan(pool, q_off, q_len, nullptr, nullptr, strand, n_problems, S, true)) return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    return seeding_load(e, S, n_problems, false);
+}
+
+// Candidate windows for chain batches: the reference stretch a chain can reach, so that a chain batch over a long reference packs no
+// more than that (host only). All arithmetic is 64-bit.
+int ba_chain_windows(const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len, const uint64_t* anchor_first, const uint32_t* q_anchor,
+                     const uint32_t* r_anchor, const uint32_t* anchor_len, uintptr_t n_chains, uint32_t margin, uint64_t* r_off_out, uint32_t* r_len_out,
+                     uint32_t* r_anchor_out) {
+    if (!q_len || !r_off || !r_len || !anchor_first || !q_anchor || !r_anchor || !anchor_len || !r_off_out || !r_len_out || !r_anchor_out) return fail("null argument");
+    for (size_t c = 0; c < n_chains; c++) {
+        const uint64_t a0 = anchor_first[c], a1 = anchor_first[c + 1];
+        if (a1 <= a0) return fail("chain %zu has no anchors", c);
+        for (uint64_t a = a0; a < a1; a++)
+            if ((uint64_t)q_anchor[a] + anchor_len[a] > q_len[c] || (uint64_t)r_anchor[a] + anchor_len[a] > r_len[c])
+                return fail("chain %zu: anchor %llu ends outside its sequences", c, (unsigned long long)(a - a0));
+        const uint64_t qa0 = q_anchor[a0], ra0 = r_anchor[a0], qe = (uint64_t)q_anchor[a1 - 1] + anchor_len[a1 - 1], re = (uint64_t)r_anchor[a1 - 1] + anchor_len[a1 - 1];
+        const uint64_t lo = ra0 - std::min(ra0, qa0 + margin), hi = re + std::min(r_len[c] - re, (q_len[c] - qe) + margin);
+        r_off_out[c] = r_off[c] + lo;
+        r_len_out[c] = (uint32_t)(hi - lo);
+        for (uint64_t a = a0; a < a1; a++) r_anchor_out[a] = (uint32_t)(r_anchor[a] - lo);
+    }
+    return 0;
 }
 
 int block_batch_align(int kind, const void* matrix, Gaps gaps, SizeRange size, int32_t x_drop, uint32_t mode, const uint8_t* pool,

@@ -1,0 +1,46 @@
+// block_aligner_amd — the reference index (ba_ref_index_*, ba_seeding_create_indexed): what the host (ba_host.cpp) and the kernels
+// (ba_index.hip, ba_index_sort.hip) share. Plain C++, no device code. The rule is stated in INTEGRATION.md, "Reference index".
+#pragma once
+#include <stdint.h>
+
+namespace ba {
+
+constexpr uint32_t INDEX_SPAN = 1024;          // windows of the reference that one work item of k_index_sketch covers (a multiple of 64)
+constexpr uint32_t INDEX_MAX_PREFIX_BITS = 20; // the prefix table is over the top min(2k, 20) bits of a code
+constexpr uint32_t INDEX_NO_CAP = 0xffffffffu; // max_ref_occ: no cap
+
+// The build. The index is keys code << 32 | pos, ascending, and table[x] .. table[x + 1] bounds the keys whose code starts with the
+// prefix_bits bits x (1 << prefix_bits entries and one more).
+struct IndexParams {
+    uint32_t k, w, len;              // the reference's bytes
+    uint32_t n_windows, n_spans;     // spans of INDEX_SPAN windows, the last one shorter
+    uint32_t prefix_bits;
+    uint32_t n_entries;              // selected k-mers (known after the count pass)
+    const uint8_t* ref;              // the bytes, on the device for the build only
+    uint32_t* counter;               // the sketch's work counter, zeroed before each launch
+    uint32_t* span_cnt;              // per span: selected k-mers (the count pass)
+    const uint64_t* span_first;      // n_spans + 1: the exclusive scan of span_cnt
+    uint64_t* unsorted;              // per selected k-mer, in position order: code << 32 | pos (the emit pass)
+    const uint64_t* key;             // the same, sorted
+    uint32_t* table;
+    uint32_t* longest_run;           // the largest number of entries that share one code (zeroed before k_index_table)
+};
+
+// The lookup of a set of n problems -- read p on its strand against the whole reference -- and the sort of their hits. The queries'
+// sketches and their sorted keys are ba::SeedingParams' (seed_first, q_key), made by ba_seeding.hip's kernels.
+struct IndexLookupParams {
+    uint32_t n;
+    uint32_t k, max_occ, max_ref_occ;
+    uint32_t prefix_bits, n_entries;
+    const uint32_t* order;           // the problems, longest query first (n)
+    const uint64_t* seed_first;      // n + 1: where a query's entries start
+    const uint64_t* q_key;           // per selected k-mer of a query: code << 32 | pos, sorted within the problem
+    const uint64_t* key;             // the index
+    const uint32_t* table;
+    uint32_t* hit_cnt;               // per problem: hits, saturating at 0xffffffff (the count pass)
+    const uint64_t* hit_first;       // n + 1: the exclusive scan of hit_cnt
+    uint64_t* hit_key;               // per hit: r_pos << 32 | q_pos (the emit pass), sorted within the problem by k_index_hit_sort
+    uint32_t* q_hit; uint32_t* r_hit; uint32_t* hit_len;   // per hit, by problem and within it by (r_hit, q_hit)
+};
+
+}  // namespace ba

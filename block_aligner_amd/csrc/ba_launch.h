@@ -7,6 +7,7 @@
 #include "ba_chaining.h"
 #include "ba_exact.h"
 #include "ba_extend.h"
+#include "ba_index.h"
 #include "ba_params.h"
 #include "ba_seeding.h"
 #include "ba_stats.h"
@@ -81,6 +82,12 @@ hipError_t ba_launch_chaining_gather(hipStream_t s, const ba::ChainingParams* cp
 hipError_t ba_launch_seeding_sketch(hipStream_t s, const ba::SeedingParams* sp, int emit);
 hipError_t ba_launch_seeding_sort(hipStream_t s, const ba::SeedingParams* sp);
 hipError_t ba_launch_seeding_match(hipStream_t s, const ba::SeedingParams* sp, int emit);
+// ba_index.hip (emit 0: the count pass, 1: the emit pass) and ba_index_sort.hip (temp null: only *temp_bytes is set)
+hipError_t ba_launch_index_sketch(hipStream_t s, const ba::IndexParams* ip, int emit);
+hipError_t ba_launch_index_table(hipStream_t s, const ba::IndexParams* ip);
+hipError_t ba_launch_index_lookup(hipStream_t s, const ba::IndexLookupParams* lp, int emit);
+hipError_t ba_launch_index_hit_sort(hipStream_t s, const ba::IndexLookupParams* lp);
+hipError_t ba_launch_index_sort(hipStream_t s, const uint64_t* in, uint64_t* out, uint32_t n, uint32_t bits, void* temp, size_t* temp_bytes);
 // ba_stats.hip
 hipError_t ba_launch_stats(hipStream_t s, const ba::StatsParams* sp);
 hipError_t ba_launch_stats_extend(hipStream_t s, const ba::ExtendParams* ep, const ba::AlignStats* side, ba::AlignStats* out);

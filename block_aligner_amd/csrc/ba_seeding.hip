@@ -18,94 +18,13 @@
 #include <hip/hip_runtime.h>
 
 #include "ba_launch.h"
+#include "ba_seed_device.hpp"
+
+using namespace ba::seed;   // the helpers shared with ba_index.hip
 
 namespace {
 
-constexpr uint64_t NO_KEY = ~0ull;
 constexpr uint32_t SKETCH_WAVES = 4, MATCH_WAVES = 4, SORT_THREADS = 1024;
-constexpr uint32_t CHUNK_KEYS = 128, CHUNK_BYTES = 192;   // 64 windows: at most 63 + 64 k-mers over at most 63 + 64 + 15 bytes
-
-struct SketchLds {   // one wave's
-    uint64_t key[CHUNK_KEYS];
-    uint32_t code[CHUNK_KEYS];
-    uint8_t two[CHUNK_BYTES];
-};
-
-// lanes of one wave hand data to one another through LDS: program order is enough for the hardware, the compiler must keep it
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ uint32_t bcast(uint32_t x, uint32_t lane) { return (uint32_t)__builtin_amdgcn_readlane((int)x, (int)lane); }
-__device__ __forceinline__ uint32_t wave_incl_sum(uint32_t x, uint32_t lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)x, d, 64);
-        x += lane >= (uint32_t)d ? o : 0u;
-    }
-    return x;
-}
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t x) {
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)x, d, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(x >> 32), d, 64);
-        x += (uint64_t)hi << 32 | lo;
-    }
-    return x;
-}
-__device__ __forceinline__ uint32_t hash32(uint32_t x) {
-    x ^= 0x9e3779b9u;
-    x ^= x >> 16;
-    x *= 0x85ebca6bu;
-    x ^= x >> 13;
-    x *= 0xc2b2ae35u;
-    x ^= x >> 16;
-    return x;
-}
-// A, C, G, T in either case -> 0 .. 3, any other byte -> 4; rc: the complement. (Clearing bit 5 maps no byte but a and A onto A.)
-__device__ __forceinline__ uint32_t two_bits(uint8_t c, bool rc) {
-    c &= 0xdfu;
-    const uint32_t v = c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u;
-    return rc && v < 4u ? 3u - v : v;
-}
-// the first index in a[0 .. n) whose key is not below x
-__device__ __forceinline__ uint32_t lower_bound(const uint64_t* a, uint32_t n, uint64_t x) {
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (a[mid] < x) lo = mid + 1u; else hi = mid;
-    }
-    return lo;
-}
-// one compare-exchange of the sort: ascending, and skipped when the partner lies past the end
-__device__ __forceinline__ void exchange(uint64_t* a, uint32_t i, uint32_t l, uint32_t n) {
-    if (l < n) {
-        const uint64_t x = a[i], y = a[l];
-        if (x > y) { a[i] = y; a[l] = x; }
-    }
-}
-// The normalized bitonic network over a[0 .. n), in LDS or in global memory, by all threads of the workgroup. Blocks of 2, 4, 8, ...: first
-// every entry against its mirror image in the block, then halves of halves at distance j.
-__device__ __forceinline__ void sort_network(uint64_t* a, uint32_t n) {
-    uint32_t lg = 1;
-    while ((1ull << lg) < n) lg++;
-    const uint32_t pairs = 1u << (lg - 1u);
-    for (uint32_t b = 1; b <= lg; b++) {   // blocks of 1 << b entries
-        for (uint32_t t = threadIdx.x; t < pairs; t += SORT_THREADS) {
-            const uint32_t i = (t >> (b - 1u)) << b | (t & ((1u << (b - 1u)) - 1u));
-            exchange(a, i, i ^ ((1u << b) - 1u), n);
-        }
-        __syncthreads();
-        for (uint32_t lj = b - 1u; lj-- > 0u;) {   // distance 1 << lj
-            for (uint32_t t = threadIdx.x; t < pairs; t += SORT_THREADS) {
-                const uint32_t i = (t >> lj) << (lj + 1u) | (t & ((1u << lj) - 1u));
-                exchange(a, i, i + (1u << lj), n);
-            }
-            __syncthreads();
-        }
-    }
-}
 
 }  // namespace
 
@@ -114,7 +33,6 @@ template <bool EMIT> __global__ void __launch_bounds__(64 * SKETCH_WAVES) k_seed
     const uint32_t lane = threadIdx.x & 63u;
     SketchLds& L = lds[threadIdx.x >> 6];
     const uint32_t k = sp.k, w = sp.w, n_seq = 2u * sp.n;
-    const uint32_t need_keys = 63u + w, need_bytes = need_keys + k - 1u;
     for (;;) {
         __builtin_amdgcn_wave_barrier();   // (a convergence point, as in k_chaining_fill)
         uint32_t t = 0;
@@ -130,35 +48,10 @@ template <bool EMIT> __global__ void __launch_bounds__(64 * SKETCH_WAVES) k_seed
         const uint64_t out0 = EMIT ? sp.seed_first[s] : 0ull;
         uint32_t count = 0;
         uint64_t prev = NO_KEY;   // the minimizer of the window before the chunk
+        const auto two = [&](uint32_t i) { return i < len ? two_bits(seq[rc ? len - 1u - i : i], rc) : 4u; };
         for (uint32_t s0 = 0; s0 < nw; s0 += 64u) {
-            for (uint32_t b = lane; b < need_bytes; b += 64u) {
-                const uint32_t i = s0 + b;
-                uint32_t v = 4;
-                if (i < len) v = two_bits(seq[rc ? len - 1u - i : i], rc);
-                L.two[b] = (uint8_t)v;
-            }
-            wave_sync();
-            for (uint32_t j = lane; j < need_keys; j += 64u) {
-                const uint32_t pos = s0 + j;
-                uint32_t code = 0, bad = 0;
-                for (uint32_t x = 0; x < k; x++) {
-                    const uint32_t v = L.two[j + x];
-                    bad |= v;
-                    code = code << 2 | (v & 3u);
-                }
-                L.key[j] = pos < nk && !(bad & 4u) ? (uint64_t)hash32(code) << 32 | pos : NO_KEY;
-                L.code[j] = code;
-            }
-            wave_sync();
-            uint64_t m = NO_KEY;   // (a window past the last one selects nothing)
-            if (s0 + lane < nw)
-                for (uint32_t x = 0; x < w; x++) {
-                    const uint64_t c = L.key[lane + x];
-                    m = c < m ? c : m;
-                }
-            const uint32_t bl = (uint32_t)__shfl_up((int)(uint32_t)m, 1, 64), bh = (uint32_t)__shfl_up((int)(uint32_t)(m >> 32), 1, 64);
-            const uint64_t before = lane ? (uint64_t)bh << 32 | bl : prev;
-            const bool take = m != NO_KEY && m != before;
+            const uint64_t m = chunk_minimizer(L, two, s0, nw, k, w, nk, lane);   // (a window past the last one selects nothing)
+            const bool take = chunk_select(m, prev, lane);
             const uint64_t ballot = __ballot(take);
             if (EMIT && take) {
                 const uint32_t pos = (uint32_t)m, code = L.code[pos - s0];
@@ -167,7 +60,6 @@ template <bool EMIT> __global__ void __launch_bounds__(64 * SKETCH_WAVES) k_seed
                 if (s < sp.n) sp.q_key[at] = (uint64_t)code << 32 | pos;   // (the queries' entries come first: the same index)
             }
             count += (uint32_t)__popcll(ballot);
-            prev = (uint64_t)bcast((uint32_t)(m >> 32), 63) << 32 | bcast((uint32_t)m, 63);
             wave_sync();   // the next chunk overwrites what this one read
         }
         if (!EMIT && lane == 0) sp.seed_cnt[s] = count;
@@ -185,11 +77,11 @@ __global__ void __launch_bounds__(SORT_THREADS) k_seeding_sort(const ba::Seeding
         if (cnt <= ba::SEEDING_SORT_LDS) {
             for (uint32_t i = threadIdx.x; i < cnt; i += SORT_THREADS) keys[i] = g[i];
             __syncthreads();
-            sort_network(keys, cnt);
+            sort_network<SORT_THREADS>(keys, cnt);
             for (uint32_t i = threadIdx.x; i < cnt; i += SORT_THREADS) g[i] = keys[i];
             __syncthreads();   // the next problem overwrites the keys
         } else {
-            sort_network(g, cnt);   // (__syncthreads orders the workgroup's global accesses as well)
+            sort_network<SORT_THREADS>(g, cnt);   // (__syncthreads orders the workgroup's global accesses as well)
         }
     }
 }

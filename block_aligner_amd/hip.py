@@ -233,6 +233,16 @@ def lib() -> C.CDLL:
         L.ba_seeding_sketch.argtypes = [vp] * 7
         L.ba_seeding_times.argtypes = [vp, vp, vp, vp]
         L.ba_seeding_destroy.argtypes = [vp]
+        L.ba_ref_index_create.restype = vp
+        L.ba_ref_index_create.argtypes = [u32, u32, vp, C.c_uint64]
+        L.ba_ref_index_counts.argtypes = [vp] * 6
+        L.ba_ref_index_entries.argtypes = [vp] * 3
+        L.ba_ref_index_times.argtypes = [vp] * 4
+        L.ba_ref_index_destroy.argtypes = [vp]
+        L.ba_seeding_create_indexed.restype = vp
+        L.ba_seeding_create_indexed.argtypes = [vp, u32, u32, vp, vp, vp, vp, sz]
+        L.ba_seeding_reload_indexed.argtypes = [vp, vp, vp, vp, vp, sz]
+        L.ba_chain_windows.argtypes = [vp] * 7 + [sz, u32, vp, vp, vp]
         for f, fields in (("ba_batch", 6), ("ba_sized_batch", 6), ("ba_multibatch", 6), ("ba_extend_batch", 10)):   # the calls of _Batch
             getattr(L, f"{f}_run").argtypes = [vp, C.POINTER(C.c_float)]
             getattr(L, f"{f}_results").argtypes = [vp] * (1 + fields)
@@ -1133,20 +1143,89 @@ class AnchorChainer:
         self._call("times", C.byref(f), C.byref(p), C.byref(g))
         return dict(fill_ms=f.value, pick_ms=p.value, gather_ms=g.value)
 
-    def chain_batch_args(self, pool, q_off, q_len, r_off, r_len, strand=None):
+    def chain_batch_args(self, pool, q_off, q_len, r_off, r_len, strand=None, margin=None):
         """The positional arguments of ChainBatchAligner after `mode` for the chains found: the per-problem arrays q_off, q_len, r_off, r_len
-        and strand expanded by chain_problem, and the chains' anchors."""
+        and strand expanded by chain_problem, and the chains' anchors. With a margin every chain's reference is cut to its candidate window
+        (chain_windows): reference positions of the batch's results are then relative to the window, and last_window_shift holds what to add
+        to them, per chain."""
         res = self.results()
         per = [np.asarray(x) for x in (q_off, q_len, r_off, r_len)] + ([] if strand is None else [np.asarray(strand)])
         if any(len(x) != self.n for x in per):
             raise ValueError("q_off, q_len, r_off, r_len and strand must have one entry per problem")
         cp = res["chain_problem"]
-        return (pool, per[0][cp], per[1][cp], per[2][cp], per[3][cp], res["anchor_first"], res["q_anchor"], res["r_anchor"], res["anchor_len"],
-                None if strand is None else per[4][cp])
+        st = None if strand is None else per[4][cp]
+        if margin is None:
+            return (pool, per[0][cp], per[1][cp], per[2][cp], per[3][cp], res["anchor_first"], res["q_anchor"], res["r_anchor"], res["anchor_len"], st)
+        r_off_w, r_len_w, r_anchor_w, self.last_window_shift = chain_windows(per[1][cp], per[2][cp], per[3][cp], res["anchor_first"], res["q_anchor"],
+                                                                             res["r_anchor"], res["anchor_len"], margin)
+        return (pool, per[0][cp], per[1][cp], r_off_w, r_len_w, res["anchor_first"], res["q_anchor"], r_anchor_w, res["anchor_len"], st)
 
     def close(self):
         if getattr(self, "_h", None) and _lib is not None:
             _lib.ba_chaining_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def chain_windows(q_len, r_off, r_len, anchor_first, q_anchor, r_anchor, anchor_len, margin: int):
+    """Candidate windows of chains (ba_chain_windows; INTEGRATION.md, "Reference index"): per chain, the stretch of its reference that the
+    chain can reach with `margin` bases to spare -> (r_off, r_len, r_anchor, shift): ChainBatchAligner's arguments in place of the ones given,
+    and per chain what was cut off in front (add it to the reference positions of the batch's results). Host only."""
+    a = [np.ascontiguousarray(x, dtype=t) for x, t in zip((q_len, r_off, r_len, anchor_first, q_anchor, r_anchor, anchor_len),
+                                                          (np.uint32, np.uint64, np.uint32, np.uint64, np.uint32, np.uint32, np.uint32))]
+    n = len(a[0])
+    if len(a[1]) != n or len(a[2]) != n or len(a[3]) != n + 1:
+        raise ValueError("q_len, r_off and r_len must have one entry per chain, anchor_first one more")
+    if any(len(x) != len(a[4]) for x in a[5:]) or len(a[4]) != int(a[3][-1]):
+        raise ValueError("q_anchor, r_anchor and anchor_len must have one entry per anchor (anchor_first[-1] of them)")
+    r_off_w, r_len_w, r_anchor_w = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(len(a[4]), np.uint32)
+    if lib().ba_chain_windows(*_ptrs(a), n, margin, r_off_w.ctypes.data, r_len_w.ctypes.data, r_anchor_w.ctypes.data):
+        raise RuntimeError(last_error())
+    return r_off_w, r_len_w, r_anchor_w, r_off_w - a[1]
+
+
+class RefIndex:
+    """The sketch of one reference, built once on the device (ba_ref_index_*; INTEGRATION.md, "Reference index"): the (w, k)-minimizers of
+    `ref` on strand 0 under the rule of "Seeding", sorted by (code, position), with a prefix table. Seeder.indexed(index, ...) seeds reads
+    against all of it. Arguments are checked before the device is touched; the bytes are not kept."""
+
+    def __init__(self, k: int, w: int, ref):
+        r = np.ascontiguousarray(np.frombuffer(ref, np.uint8) if isinstance(ref, (bytes, bytearray)) else ref, dtype=np.uint8)
+        n = len(r)
+        if n == 0:   # (an empty array has no address)
+            r = np.zeros(1, np.uint8)
+        self._h = lib().ba_ref_index_create(k, w, r.ctypes.data, n)
+        if not self._h:
+            raise RuntimeError(last_error())
+
+    def _call(self, name, *args):
+        if getattr(lib(), f"ba_ref_index_{name}")(self._h, *args):
+            raise RuntimeError(last_error())
+
+    def counts(self):
+        """-> dict: n_entries, k, w, ref_len and longest_run (the most entries that share one code)."""
+        n, ln, k, w, run = C.c_uint64(), C.c_uint64(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._call("counts", C.byref(n), C.byref(k), C.byref(w), C.byref(ln), C.byref(run))
+        return dict(n_entries=n.value, k=k.value, w=w.value, ref_len=ln.value, longest_run=run.value)
+
+    def entries(self):
+        """-> (code, pos): the entries, ascending by (code, pos)."""
+        n = self.counts()["n_entries"]
+        code, pos = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        self._call("entries", code.ctypes.data, pos.ctypes.data)
+        return code, pos
+
+    def times(self):
+        """Device milliseconds of the build: the sketch, the sort of the keys, the prefix table."""
+        a, b, c = C.c_float(), C.c_float(), C.c_float()
+        self._call("times", C.byref(a), C.byref(b), C.byref(c))
+        return dict(sketch_ms=a.value, sort_ms=b.value, table_ms=c.value)
+
+    def close(self):
+        """(Seeders made from the index keep what they need.)"""
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.ba_ref_index_destroy(self._h)
             self._h = None
 
     __del__ = close
@@ -1159,7 +1238,8 @@ class Seeder:
     query's selected k-mers have gives no hits. Arguments are checked before the device is touched.
 
     run() computes sketches and hits and returns the kernels' time; results() gives the hits of every problem, sorted by (r_hit, q_hit), as
-    AnchorChainer takes them; AnchorChainer.from_seeder(..., seeder) chains them where they lie."""
+    AnchorChainer takes them; AnchorChainer.from_seeder(..., seeder) chains them where they lie. Seeder.indexed(index, ...) is the same for
+    many reads against the one reference of a RefIndex."""
 
     @staticmethod
     def _arrays(pool, q_off, q_len, r_off, r_len, strand):
@@ -1177,6 +1257,40 @@ class Seeder:
         self._h = lib().ba_seeding_create(C.byref(self.params), *_ptrs(a), self.n)
         if not self._h:
             raise RuntimeError(last_error())
+
+    @staticmethod
+    def _arrays_indexed(pool, q_off, q_len, strand):
+        a = _pair_arrays(pool, q_off, q_len) + [None if strand is None else np.ascontiguousarray(strand, dtype=np.uint8)]
+        if any(len(x) != len(a[2]) for x in a[1:] if x is not None):
+            raise ValueError("q_off, q_len and strand must have one entry per problem")
+        return a
+
+    @classmethod
+    def indexed(cls, index: "RefIndex", max_occ: int, max_ref_occ: int, pool, q_off, q_len, strand=None):
+        """A seeder whose problem p is read p on strand[p] against the whole reference of a RefIndex (ba_seeding_create_indexed); k and w
+        are the index's. A reference entry whose code occurs more than max_ref_occ times in the reference's sketch gives no hits (0xffffffff:
+        no cap, and then the hits equal Seeder's with r the whole reference). Everything but reload() works as on any Seeder; sketch() has
+        no reference entries."""
+        a = cls._arrays_indexed(pool, q_off, q_len, strand)
+        self = cls.__new__(cls)
+        self._h = None
+        self._counts = None
+        self.n = len(a[2])
+        h = lib().ba_seeding_create_indexed(getattr(index, "_h", None), max_occ, max_ref_occ, *_ptrs(a), self.n)
+        if not h:
+            raise RuntimeError(last_error())
+        self._h = h
+        c = index.counts()
+        self.params = SeedingParamsC(c["k"], c["w"], max_occ)
+        self.max_ref_occ = max_ref_occ
+        return self
+
+    def reload_indexed(self, pool, q_off, q_len, strand=None) -> None:
+        """reload() for a seeder made by indexed() (ba_seeding_reload_indexed)."""
+        a = self._arrays_indexed(pool, q_off, q_len, strand)
+        self._counts = None
+        self._call("reload_indexed", *_ptrs(a), len(a[2]))
+        self.n = len(a[2])
 
     def _call(self, name, *args):
         if getattr(lib(), f"ba_seeding_{name}")(self._h, *args):

@@ -453,6 +453,41 @@ void ba_seeding_destroy(BaSeeding* batch);
  * afterwards: the copy is complete when the call returns, and the seeder may be reloaded, run again or destroyed at once. */
 BaChaining* ba_chaining_create_seeded(const struct BaChainingParams* params, BaSeeding* ran);
 
+/* ---- a reference index: the sketch of one reference, built once, and many reads seeded against all of it ("Reference
+ * index"). The index holds the (w, k)-minimizer sketch of ref[0 .. ref_len) on strand 0 under the rule of "Seeding", as keys
+ * code << 32 | pos in ascending order with a prefix table over the top min(2k, 20) bits of the code; the bytes are not kept. k is 4 .. 16, w
+ * is 1 .. 64, ref is not NULL and ref_len is below 2^31 - 16: checked before the device is touched. A reference shorter than k has no entries.
+ * Several reference sequences: concatenate them with N spacers. */
+typedef struct BaRefIndex BaRefIndex;
+BaRefIndex* ba_ref_index_create(uint32_t k, uint32_t w, const uint8_t* ref, uint64_t ref_len);
+/* Any pointer may be NULL. longest_run: the largest number of entries that share one code (what max_ref_occ is compared with). */
+int ba_ref_index_counts(BaRefIndex* index, uint64_t* n_entries, uint32_t* k, uint32_t* w, uint64_t* ref_len, uint32_t* longest_run);
+/* The entries, n_entries each, ascending by (code, pos). Either pointer may be NULL. */
+int ba_ref_index_entries(BaRefIndex* index, uint32_t* code, uint32_t* pos);
+/* Device times of the build in ms: the sketch's two passes, the sort of the keys, the prefix table. Any pointer may be NULL. */
+int ba_ref_index_times(BaRefIndex* index, float* sketch_ms, float* sort_ms, float* table_ms);
+/* Seeders made from the index share its device buffers and stay valid. */
+void ba_ref_index_destroy(BaRefIndex* index);
+/* A seeder whose problem p is read p = pool[q_off[p] .. + q_len[p]) on strand[p] (or NULL) against the whole indexed reference; k and w are
+ * the index's. The hits are those of ba_seeding_create with r the whole reference, except that a reference entry whose code occurs more
+ * than max_ref_occ times in the reference's sketch gives none (max_ref_occ >= 1; 0xffffffff: no cap, and then the hits are equal bit for
+ * bit). The handle is a BaSeeding on the index's device: run, counts, results, sketch (no reference entries: n_r_seeds is 0 and r_seed_first
+ * all zeros), times (the sketch; the sorts of the queries' keys and of the hits; the lookup), destroy and ba_chaining_create_seeded work on
+ * it. ba_seeding_reload refuses it and ba_seeding_reload_indexed refuses any other seeder. The other arguments are checked before the index
+ * is looked at. */
+BaSeeding* ba_seeding_create_indexed(BaRefIndex* index, uint32_t max_occ, uint32_t max_ref_occ, const uint8_t* pool, const uint64_t* q_off,
+                                     const uint32_t* q_len, const uint8_t* strand, uintptr_t n_problems);
+int ba_seeding_reload_indexed(BaSeeding* batch, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint8_t* strand,
+                              uintptr_t n_problems);
+/* Candidate windows (host only): the stretch of its reference that a chain can reach, so that ba_chain_batch_create packs no more than that.
+ * Chain c has the first anchor (qa0, ra0) and its last anchor ends at (qe, re); in 64-bit arithmetic lo = ra0 - min(ra0, qa0 + margin),
+ * hi = re + min(r_len - re, (q_len - qe) + margin), r_off_out = r_off + lo, r_len_out = hi - lo, r_anchor_out = r_anchor - lo. A chain without
+ * anchors or an anchor that ends outside its sequences is refused with the chain's number. The outputs, with the other arguments as they
+ * are, are a valid input of ba_chain_batch_create; reference positions of its results are relative to r_off_out. */
+int ba_chain_windows(const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len, const uint64_t* anchor_first, const uint32_t* q_anchor,
+                     const uint32_t* r_anchor, const uint32_t* anchor_len, uintptr_t n_chains, uint32_t margin, uint64_t* r_off_out,
+                     uint32_t* r_len_out, uint32_t* r_anchor_out);
+
 /* ---- every pair with its own block range. The reference's callers choose the range per pair -- percent_len(max(|q|, |r|), 0.01) ..=
  * percent_len(max(|q|, |r|), p) in /root/reference/examples/nanopore_bench_global.rs:144-171, Block::align(..., min..=max, x) in
  * src/scan_block.rs:847 --, while ba_batch_create takes one range for the whole batch. These calls bin the pairs by (min, max), align every bin as
