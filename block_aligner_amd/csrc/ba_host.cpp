@@ -1246,6 +1246,9 @@ static int batch_drop_class_bet(BaBatch* b) {
 }
 static int batch_launch(BaBatch* b) {
     if (b->in_flight) return fail("the batch already has a launch in flight (ba_batch_wait first)");
+    // the buffers are about to be written again: what the last run left is no result from here on, whether this launch gets onto the stream,
+    // times out or fails (ran is set again at the end of a successful batch_wait only)
+    b->ran = false;
     b->compacted = false;
     if (b->n == 0) return fail("the batch holds no pairs (its last reload failed)");
     if (!b->handle_mode && b->kind != BA_KIND_PROFILE_ && b->gap_open == b->gap_extend)
@@ -2494,9 +2497,17 @@ int ba_batch_reload_profile(BaBatch* b, const AAProfile* const* profiles, const 
 int ba_batch_run(BaBatch* b, float* kernel_ms) { return b ? batch_run(b, kernel_ms) : fail("null batch"); }
 int ba_batch_launch(BaBatch* b) { return b ? batch_launch(b) : fail("null batch"); }
 int ba_batch_wait(BaBatch* b, float* kernel_ms) { return b ? batch_wait(b, kernel_ms) : fail("null batch"); }
+// What a run leaves on the device is read after its wait only. In flight -- between ba_batch_launch and a ba_batch_wait that succeeded, a wait that
+// timed out included -- the kernels are still writing those buffers, and the batch's stream is non-blocking: a copy would not queue behind them. And a
+// launch takes the last run's results away (batch_launch clears ran), so a wait that failed leaves none. Before any device call of a getter.
+static int batch_results_refused(const BaBatch* b, const char* what) {
+    if (b->in_flight) return fail("%s: the batch has a launch in flight (ba_batch_wait first)", what);
+    if (!b->ran) return fail("ba_batch_run has not been called");
+    return 0;
+}
 int ba_batch_results(BaBatch* b, int32_t* score, uint32_t* qi, uint32_t* ri, uint64_t* cells, uint32_t* cigar_len, uint32_t* status) {
     if (!b) return fail("null batch");
-    if (!b->ran) return fail("ba_batch_run has not been called");
+    if (batch_results_refused(b, "results")) return 1;
     HIP_TRY(hipSetDevice(b->device));
     if (d2h(b->score, score, b->n) || d2h(b->qidx, qi, b->n) || d2h(b->ridx, ri, b->n) || d2h(b->cells, cells, b->n) ||
         d2h(b->cig_len, cigar_len, b->n) || d2h(b->status, status, b->n)) return 1;
@@ -2509,7 +2520,7 @@ int ba_batch_results(BaBatch* b, int32_t* score, uint32_t* qi, uint32_t* ri, uin
 int ba_batch_surviving_cells(BaBatch* b, uint64_t* cells) {
     if (!b || !cells) return fail("null argument");
     if (!(b->mode & BA_TRACE)) return fail("batch was created without BA_TRACE");
-    if (!b->ran) return fail("ba_batch_run has not been called");
+    if (batch_results_refused(b, "surviving cells")) return 1;
     HIP_TRY(hipSetDevice(b->device));
     std::vector<uint32_t> w(b->n);
     if (d2h(b->trace_words, w.data(), b->n)) return 1;
@@ -2563,7 +2574,7 @@ int ba_batch_compact_cigars(BaBatch* b, uint32_t* pinned_out, uint64_t pinned_ca
 int ba_batch_cigars(BaBatch* b, uint32_t* runs, uint64_t capacity) {
     if (!b) return fail("null batch");
     if (!(b->mode & BA_TRACE)) return fail("batch was created without BA_TRACE");
-    if (!b->ran) return fail("ba_batch_run has not been called");
+    if (batch_results_refused(b, "cigars")) return 1;
     HIP_TRY(hipSetDevice(b->device));
     if (b->compacted && b->retried == 0) {   // gathered behind the launch: one copy
         const unsigned long long total = *(volatile unsigned long long*)b->h_total;   // (written by the gather; the stream was synchronised by ba_batch_wait)
@@ -2623,6 +2634,8 @@ int ba_dev_kernel_forms(int family, int kind, int pclass, int special) {
 #endif
 int ba_batch_prof(BaBatch* b, uint64_t out[128]) {   // development: phase timers of a -DBA_TIMING build (all per-pair launches of a batch add up)
     if (!b) return fail("null batch");
+    if (batch_results_refused(b, "timers")) return 1;
+    HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipMemcpy(out, b->prof.p, 1024, hipMemcpyDeviceToHost));
     return 0;
 }
@@ -2636,7 +2649,7 @@ int ba_batch_info(BaBatch* b, uint64_t out[4]) {
 // operations per cell). Pairs re-run for a trace overflow are not in it.
 int ba_batch_spec_cells(BaBatch* b, uint64_t* cells) {
     if (!b || !cells) return fail("null argument");
-    if (!b->ran) return fail("ba_batch_run has not been called");
+    if (batch_results_refused(b, "speculative cells")) return 1;
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipMemcpy(cells, (const char*)b->prof.p + 60 * 8, 8, hipMemcpyDeviceToHost));
     return 0;
@@ -2646,7 +2659,7 @@ int ba_batch_spec_cells(BaBatch* b, uint64_t* cells) {
 // rectangles. 0 without X-drop, for byte-matrix and profile batches, in the special modes, and for a matrix that scores its padding byte at 0 or above.
 int ba_batch_skipped_cells(BaBatch* b, uint64_t* cells) {
     if (!b || !cells) return fail("null argument");
-    if (!b->ran) return fail("ba_batch_run has not been called");
+    if (batch_results_refused(b, "skipped cells")) return 1;
     HIP_TRY(hipSetDevice(b->device));
     HIP_TRY(hipMemcpy(cells, (const char*)b->prof.p + 61 * 8, 8, hipMemcpyDeviceToHost));
     return 0;
@@ -3866,7 +3879,29 @@ struct BaPartSet {
     std::vector<float> last_ms;                   // kernel time of every part in the last run
     size_t n = 0;
     uint32_t mode = 0;
+    // The last run of the set was begun and did not complete for every part. The parts' own `ran` cannot say so: after a timeout in the first
+    // of a sized set's chained ranges the later ones were never launched in that run and still hold the results of the run before.
+    bool incomplete = false;
 };
+// Every getter of a set begins here: no result of any part is served unless the set's last run completed for all of them. (A set that was never
+// run passes: its parts refuse what needs a run, and the exact calls need none.)
+static int parts_refused(const BaPartSet* m) {
+    if (!m) return fail("null batch");
+    for (const auto& b : m->part)
+        if (b && b->in_flight) return fail("the set has a launch in flight from a run that did not finish (run the set again: it waits for that launch first)");
+    if (m->incomplete) return fail("the set's last run did not complete for every part: it has no results (run the set again)");
+    return 0;
+}
+// Every run of a set begins here: the launches a timed-out run left in flight are waited for, under the current limit. 0: no part is in flight;
+// 1: one still is (batch_wait's message stands) and nothing may be launched. A launch that ends in an error here belonged to the earlier run, which
+// has failed already: the part is free again, and the run that follows starts every part afresh.
+static int parts_collect(BaPartSet* m) {
+    for (auto& b : m->part) {
+        if (!b || !b->in_flight) continue;
+        if (batch_wait(b.get(), nullptr) && b->in_flight) return 1;
+    }
+    return 0;
+}
 static bool one_run(const std::vector<uint64_t>& pos) { return !pos.empty() && pos.back() - pos.front() + 1 == pos.size(); }
 // One caller array as a part sees it: the part's slice of it when the part's positions are one run, else a buffer scatter() spreads.
 template <class T> struct PartOut {
@@ -3878,7 +3913,7 @@ template <class T> struct PartOut {
     void scatter() const { for (size_t i = 0; i < tmp.size(); i++) out[pos[i]] = tmp[i]; }
 };
 static int parts_results(BaPartSet* m, int32_t* score, uint32_t* qi, uint32_t* ri, uint64_t* cells, uint32_t* cigar_len, uint32_t* status) {
-    if (!m) return fail("null batch");
+    if (parts_refused(m)) return 1;
     for (size_t k = 0; k < m->part.size(); k++) {
         if (!m->part[k]) continue;
         const auto& pos = m->pos[k];
@@ -3891,7 +3926,7 @@ static int parts_results(BaPartSet* m, int32_t* score, uint32_t* qi, uint32_t* r
     return 0;
 }
 static int parts_cigars(BaPartSet* m, uint32_t* runs, uint64_t capacity) {   // concatenated in the caller's pair order, as ba_batch_cigars
-    if (!m) return fail("null batch");
+    if (parts_refused(m)) return 1;
     std::vector<uint32_t> len(m->n, 0);
     if (parts_results(m, nullptr, nullptr, nullptr, nullptr, len.data(), nullptr)) return 1;
     std::vector<uint64_t> off(m->n + 1, 0);
@@ -3915,7 +3950,7 @@ static int parts_cigars(BaPartSet* m, uint32_t* runs, uint64_t capacity) {   // 
     return 0;
 }
 static int parts_stats(BaPartSet* m, BaAlignStats* out) {
-    if (!m) return fail("null batch");
+    if (parts_refused(m)) return 1;
     if (!out) return fail("null argument");
     for (size_t k = 0; k < m->part.size(); k++) {
         if (!m->part[k]) continue;
@@ -3926,7 +3961,7 @@ static int parts_stats(BaPartSet* m, BaAlignStats* out) {
     return 0;
 }
 static int parts_exact(BaPartSet* m, uint32_t what, int32_t x_drop, const uint32_t* which, size_t n_which, BaExact* out) {   // every part computes its own pairs
-    if (!m) return fail("null batch");
+    if (parts_refused(m)) return 1;
     if (!out) return fail("null argument: out");
     const size_t cnt = which ? n_which : m->n;
     std::vector<uint32_t> part_of(m->n), local_of(m->n);
@@ -3952,7 +3987,7 @@ static int parts_exact(BaPartSet* m, uint32_t what, int32_t x_drop, const uint32
 template <class Rec>
 static int parts_exact_cigars(BaPartSet* m, uint32_t what, int32_t x_drop, const uint32_t* which, size_t n_which, Rec* out, uint64_t* run_off,
                               uint32_t* runs, uint64_t capacity) {
-    if (!m) return fail("null batch");
+    if (parts_refused(m)) return 1;
     if (!out) return fail("null argument: out");
     if (!run_off) return fail("null argument: run_off");
     const size_t cnt = which ? n_which : m->n;
@@ -3987,7 +4022,7 @@ static int parts_exact_cigars(BaPartSet* m, uint32_t what, int32_t x_drop, const
     return 0;
 }
 static int parts_text(BaPartSet* m, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) {   // sized per part, then rendered per part
-    if (!m) return fail("null batch");
+    if (parts_refused(m)) return 1;
     if (!offsets) return fail("null argument: offsets");
     if (text_check(BA_KIND_NUC, m->mode, what)) return 1;   // (the kind's refusals come from the parts)
     std::vector<std::vector<uint64_t>> po(m->part.size());   // every part's own offsets
@@ -4081,7 +4116,10 @@ BaMultiBatch* ba_multibatch_create(int kind, const void* matrix, Gaps gaps, Size
 int ba_multibatch_run(BaMultiBatch* m, float* kernel_ms) {
     if (!m) return fail("null batch");
     // all devices first, then collect. A failure does not leave the other parts in flight: every part that was launched is
-    // waited for before the first error is reported.
+    // waited for before the first error is reported -- except after a timeout: that part stays in flight, the set has no results
+    // (incomplete), and the next run collects it before it launches anything.
+    if (parts_collect(m)) return 1;
+    m->incomplete = true;
     std::string first_err;
     for (auto& b : m->part) {
         if (!b || !first_err.empty()) continue;
@@ -4098,6 +4136,7 @@ int ba_multibatch_run(BaMultiBatch* m, float* kernel_ms) {
         worst = std::max(worst, ms);
     }
     if (!first_err.empty()) return fail("%s", first_err.c_str());
+    m->incomplete = false;
     if (kernel_ms) *kernel_ms = worst;
     return 0;
 }
@@ -4119,6 +4158,7 @@ int ba_multibatch_exact(BaMultiBatch* m, uint32_t what, int32_t x_drop, const ui
 int ba_multibatch_text(BaMultiBatch* m, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) { return parts_text(m, what, offsets, text, capacity); }
 int ba_multibatch_kernel_ms(BaMultiBatch* m, float* ms, int capacity) {   // per slice, of the last run; returns the number of slices
     if (!m) return -1;
+    if (parts_refused(m)) return -1;   // (the times of a run that did not complete are no times: ba_last_error says why)
     for (int k = 0; k < capacity && k < (int)m->last_ms.size(); k++) ms[k] = m->last_ms[k];
     return (int)m->part.size();
 }
@@ -4190,6 +4230,8 @@ BaSizedBatch* ba_sized_batch_create_percent(int kind, const void* matrix, Gaps g
 }
 int ba_sized_batch_run(BaSizedBatch* m, float* kernel_ms) {
     if (!m) return fail("null batch");
+    if (parts_collect(m)) return 1;   // (what a timed-out run left in flight; still running: nothing is launched)
+    m->incomplete = true;
     // Round 5: all ranges' launches at once, each on its batch's own stream, the ones with the most work first: a range of a few thousand pairs
     // does not fill the device (its grid is what its pairs need), and the long ranges' launches end with a few long pairs. kernel_ms: the host's
     // clock from the first launch to the last completion (the device is idle before: the previous run was waited for).
@@ -4210,17 +4252,24 @@ int ba_sized_batch_run(BaSizedBatch* m, float* kernel_ms) {
     std::vector<size_t> free_run, chained;
     for (size_t k : order) (waits_inside(m->part[k].get()) ? chained : free_run).push_back(k);
     std::vector<char> launched(m->part.size(), 0);
-    auto wait_one = [&](size_t k) { float ms = 0; if (ba_batch_wait(m->part[k].get(), &ms) && !rc) { rc = 1; first_err = g_err; } m->last_ms[k] = ms; launched[k] = 0; };
+    // launched[k]: 1 = to be waited for in this call; 2 = its wait timed out, the part is still in flight: not waited for a second time here, and
+    // not forgotten -- the set stays incomplete, and the next run collects it (parts_collect)
+    auto wait_one = [&](size_t k) {
+        float ms = 0;
+        if (ba_batch_wait(m->part[k].get(), &ms) && !rc) { rc = 1; first_err = g_err; }
+        m->last_ms[k] = ms; launched[k] = m->part[k]->in_flight ? 2 : 0;
+    };
     auto launch_one = [&](size_t k) { if (rc) return; if (ba_batch_launch(m->part[k].get())) { rc = 1; first_err = g_err; } else launched[k] = 1; };
     if (!chained.empty()) launch_one(chained[0]);   // (the longest chain first: the other ranges fill the device around it)
     for (size_t k : free_run) launch_one(k);
     for (size_t i = 0; i < chained.size(); i++) {
-        if (launched[chained[i]]) wait_one(chained[i]);
+        if (launched[chained[i]] == 1) wait_one(chained[i]);
         if (i + 1 < chained.size()) launch_one(chained[i + 1]);
     }
-    for (size_t k : free_run) if (launched[k]) wait_one(k);   // (also after a failed launch: nothing is left in flight behind the caller's back)
-    for (size_t k = 0; k < launched.size(); k++) if (launched[k]) wait_one(k);
+    for (size_t k : free_run) if (launched[k] == 1) wait_one(k);   // (also after a failed launch: nothing but a timed-out part is left in flight)
+    for (size_t k = 0; k < launched.size(); k++) if (launched[k] == 1) wait_one(k);
     if (rc) return fail("%s", first_err.c_str());
+    m->incomplete = false;
     if (kernel_ms) *kernel_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return 0;
 }
@@ -4242,6 +4291,7 @@ int ba_sized_batch_exact(BaSizedBatch* m, uint32_t what, int32_t x_drop, const u
 int ba_sized_batch_text(BaSizedBatch* m, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) { return parts_text(m, what, offsets, text, capacity); }
 int ba_sized_batch_classes(BaSizedBatch* m, SizeRange* ranges, uint64_t* counts, int32_t* kernels, float* kernel_ms, int capacity) {   // the bins; returns their number
     if (!m) return -1;
+    if (parts_refused(m)) return -1;   // (as ba_multibatch_kernel_ms)
     for (int k = 0; k < capacity && k < (int)m->part.size(); k++) {
         if (ranges) ranges[k] = m->range[k];
         if (counts) counts[k] = m->pos[k].size();

@@ -851,6 +851,8 @@ class MultiBatchAligner(_Batch):
         """Kernel time of every slice in the last run() (ms; HIP events on the slice's own stream)."""
         t = np.zeros(64, np.float32)
         k = lib().ba_multibatch_kernel_ms(self._h, t.ctypes.data, 64)
+        if k < 0:   # (the last run did not complete)
+            raise RuntimeError(last_error())
         return t[:k].copy()
 
     def parts(self):
@@ -887,6 +889,8 @@ class SizedBatchAligner(_Batch):
         while True:   # (the call returns the number of bins, however many fit: a second call with room for all of them if there are more)
             r = np.zeros((cap, 2), np.uint64); c = np.zeros(cap, np.uint64); k = np.zeros(cap, np.int32); t = np.zeros(cap, np.float32)
             nb = lib().ba_sized_batch_classes(self._h, r.ctypes.data, c.ctypes.data, k.ctypes.data, t.ctypes.data, cap)
+            if nb < 0:   # (the last run did not complete)
+                raise RuntimeError(last_error())
             if nb <= cap:
                 break
             cap = nb

@@ -227,6 +227,16 @@ int ba_batch_reload_profile(BaBatch* batch, const struct AAProfile* const* profi
 int ba_batch_run(BaBatch* batch, float* kernel_ms);
 /* The two halves of ba_batch_run: enqueue on the batch's own stream and return / wait for it. Launches of different
  * batches overlap on the device; results, cigars and reload are valid after the wait.
+ * Which calls are valid when:
+ *   no results (created, reloaded, or the last wait failed): ba_batch_launch, ba_batch_run, ba_batch_reload, ba_batch_exact*; every getter of a
+ *     run's results is refused.
+ *   in flight (ba_batch_launch returned 0, no ba_batch_wait has succeeded or ended in an error since -- a wait that timed out leaves the batch
+ *     here): ba_batch_wait and ba_batch_compact_cigars. ba_batch_results, _cigars, _surviving_cells, _spec_cells, _skipped_cells, _prof, _stats,
+ *     _text, _exact*, _reload, _launch and _run are refused with "launch in flight (ba_batch_wait first)" before they touch the device: the
+ *     kernels are still writing what they would read, and the batch's stream is non-blocking.
+ *   results (a ba_batch_wait or ba_batch_run returned 0): everything but ba_batch_wait and ba_batch_compact_cigars.
+ *   ba_batch_info, _kernel, _geometry and _retried (the count of the last COMPLETED run) read host state and answer in every state.
+ * ba_batch_launch takes the results of the run before away: from then on the batch has none until a wait succeeds, whatever becomes of the launch.
  * At most TWO launches in flight per device if they are BA_TRACE batches of more than a few pairs per resident wave: such a launch's waves wait for each other
  * (the traceback waves for the fill waves' hand-offs, k_multi's idle waves for its last fill wave), so it must become fully resident to end. The first launch
  * on an idle device is; a second one follows it; three or more may each hold a part of the device and keep each other's remaining workgroups out
@@ -502,7 +512,11 @@ BaSizedBatch* ba_sized_batch_create_percent(int kind, const void* matrix, struct
                                             uintptr_t n_pairs);
 /* The bins are launched together (each on its own stream, sharing the device) and waited for. kernel_ms (optional): host wall-clock milliseconds from the
  * first launch to the last completion -- overflow re-runs and the host's work between the waits included; NOT a sum of HIP-event times: the bins overlap
- * (per-bin event times of the same run: ba_sized_batch_classes). */
+ * (per-bin event times of the same run: ba_sized_batch_classes).
+ * A run that fails -- a wait past ba_set_wait_limit_ms above all, which leaves bins in flight or never launched -- leaves the SET without results:
+ * ba_sized_batch_results, _cigars, _stats, _text, _exact* and _classes (returns -1) are refused until a later run completes for every bin. That
+ * later run first waits, under the current limit, for every bin still in flight; if one is still running it fails with the same "did not finish
+ * within ... still running" message and launches nothing, otherwise it runs all bins afresh. */
 int ba_sized_batch_run(BaSizedBatch* batch, float* kernel_ms);
 int ba_sized_batch_results(BaSizedBatch* batch, int32_t* score, uint32_t* query_idx, uint32_t* reference_idx, uint64_t* cells, uint32_t* cigar_len,
                            uint32_t* status);
@@ -519,7 +533,10 @@ typedef struct BaMultiBatch BaMultiBatch;
 BaMultiBatch* ba_multibatch_create(int kind, const void* matrix, struct Gaps gaps, struct SizeRange size, int32_t x_drop, uint32_t mode,
                                    const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off,
                                    const uint32_t* r_len, uintptr_t n_pairs, const int* devices, int n_devices);
-/* Launch on every device, then wait for all. kernel_ms (optional) = the longest device's kernel time. */
+/* Launch on every device, then wait for all. kernel_ms (optional) = the longest device's kernel time.
+ * As ba_sized_batch_run: after a run that failed or timed out the set has no results -- ba_multibatch_results, _cigars, _stats, _text, _exact* and
+ * _kernel_ms (returns -1) are refused --, and the next run first waits, under the current limit, for the slices still in flight (still running:
+ * the same message, nothing launched), then runs every slice afresh. */
 int ba_multibatch_run(BaMultiBatch* batch, float* kernel_ms);
 int ba_multibatch_results(BaMultiBatch* batch, int32_t* score, uint32_t* query_idx, uint32_t* reference_idx, uint64_t* cells,
                           uint32_t* cigar_len, uint32_t* status);
