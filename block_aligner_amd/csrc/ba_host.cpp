@@ -1494,38 +1494,226 @@ static void to_caller_order(const std::vector<uint32_t>& order, T* dst) {
     for (size_t s = 0; s < order.size(); s++) dst[order[s]] = tmp[s];
 }
 
-// ------------------------------------------------------------------ seed-and-extend batches (ba_extend_batch_*)
-// One seed = one result: X-drop alignment leftwards from the seed (reversed prefixes) and rightwards from its end. Every non-empty side of
-// every seed is a pair of ONE ordinary batch (batch_build: same planning, kernels and re-runs), whose images k_pack_images cuts out of the
-// caller's bytes on the device -- uploaded once, no slice copied on the host; the splice (ba_extend.hip) then scores the seeds and joins
-// both sides' results and CIGAR runs per seed on the device, in the caller's order.
-struct ExtSet {   // a seed set cut into sides (host addresses into the caller's pool; nothing is copied)
-    const uint8_t* lo = nullptr; uint64_t bytes = 0;   // extent of the seeds' sequences in the caller's pool
-    std::vector<const uint8_t*> src;                   // 2 per side (query, reference): first byte of the slice
-    std::vector<uint32_t> len;                         // 2 per side
-    std::vector<uint8_t> flags;                        // 2 per side: ba::IMG_*
-    std::vector<uint32_t> seed_of;                     // per side
-    std::vector<uint32_t> side;                        // 2 per seed (left, right): index of the side, or ba::EXT_NO_SIDE
-    std::vector<uint64_t> s_raw_q, s_raw_r, s_img_q, s_img_r;   // the seeds' own images: source offsets in the upload, offsets in the seed pool
-    std::vector<uint8_t> s_flags;                      // 2 per seed
-    uint64_t seed_bytes = 0;
-    // per seed, the whole query and reference: source offsets in the upload, lengths, strand (ba_extend_batch_text renders from them)
-    std::vector<uint64_t> t_raw_q, t_raw_r;
-    std::vector<uint32_t> t_ql, t_rl;
-    std::vector<uint8_t> t_strand;
+template <class T>
+static int h2d(DevBuf& buf, const T* src, size_t count) {
+    HIP_TRY(hipMemcpy(buf.p, src, count * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// ------------------------------------------------------------------ objects that own a stream and events
+// The device, one non-blocking stream and the timing events of an object with kernels of its own: extension and chain batches, the
+// chainer, the seeder, an index build. A struct derived from it destroys its own members first: inner batches go before the outer stream.
+namespace {   // (this and the other shared parts below add no name to the library's exports)
+struct StreamOwner {
+    int device = 0;
+    hipStream_t stream = nullptr; hipEvent_t ev[9] = {};
+    int open(size_t n_events) {
+        if (hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) return fail("hipStreamCreate failed");
+        for (size_t i = 0; i < n_events; i++) if (hipEventCreate(&ev[i]) != hipSuccess) return fail("hipEventCreate failed");
+        return 0;
+    }
+    int elapsed(int a, int b, float* ms) const {   // device time between two recorded events
+        HIP_TRY(hipEventElapsedTime(ms, ev[a], ev[b]));
+        return 0;
+    }
+    ~StreamOwner() {
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
 };
-static int ext_check_params(int kind, Gaps gaps, SizeRange size, int32_t x_drop, uint32_t mode) {   // ba_extend_batch_create's own arguments
-    if (kind == BA_KIND_PROFILE_) return fail("extension batches take a sequence matrix: profile batches cannot be extended");
+
+// ------------------------------------------------------------------ spliced batches: what extension and chain batches share
+// Both are made of ordinary batches (batch_build: same planning, kernels and re-runs) over pieces that k_pack_images cuts out of the
+// caller's bytes on the device -- uploaded once, no slice copied on the host --, and a splice that joins the pieces' results and CIGAR
+// runs per unit (seed, chain) on the device, in the caller's order.
+constexpr uint32_t NO_PIECE = 0xffffffffu;   // in an index of pieces: the piece is empty and was not aligned
+static_assert(ba::EXT_NO_SIDE == NO_PIECE && ba::CHAIN_NO_PIECE == NO_PIECE, "EXT_NO_SIDE and CHAIN_NO_PIECE must both be 0xffffffff");
+struct PieceSet {   // the pairs of one inner batch (host addresses into the caller's pool; nothing is copied)
+    std::vector<const uint8_t*> src;   // 2 per piece (query, reference): first byte of the slice
+    std::vector<uint32_t> len;         // 2 per piece
+    std::vector<uint8_t> flags;        // 2 per piece: ba::IMG_*
+    std::vector<uint32_t> owner;       // per piece: its seed or chain
+    size_t size() const { return owner.size(); }
+    uint32_t add(size_t u, const uint8_t* qs, uint64_t ql, uint8_t qf, const uint8_t* rs, uint64_t rl, uint8_t rf) {
+        owner.push_back((uint32_t)u);
+        src.push_back(qs); len.push_back((uint32_t)ql); flags.push_back(qf);
+        src.push_back(rs); len.push_back((uint32_t)rl); flags.push_back(rf);
+        return (uint32_t)owner.size() - 1;
+    }
+};
+struct SplicedSet {   // a planned set: the extent of its sequences in the caller's pool, the size of the units' own images (seeds, anchors)
+    const uint8_t* lo = nullptr; const uint8_t* hi = nullptr;
+    uint64_t bytes = 0, own_bytes = 0;
+    // unit u (`noun`: "seed", "chain") on strand st: the strand checked, its sequences q and r added to the extent
+    int add(int kind, const char* noun, size_t u, uint8_t st, const uint8_t* q, uint64_t Q, const uint8_t* r, uint64_t R) {
+        if (st > 1) return fail("%s %zu: strand must be 0 or 1", noun, u);
+        if (st && kind != BA_KIND_NUC) return fail("%s %zu: strand needs a NucMatrix batch (reverse complement is nucleotide-only)", noun, u);
+        for (const uint8_t* x : {q, r}) if (!lo || x < lo) lo = x;
+        if (!hi || q + Q > hi) hi = q + Q;
+        if (r + R > hi) hi = r + R;
+        return 0;
+    }
+    uint64_t own_image(uint64_t L) {   // -> the offset of one more own image of L bytes
+        const uint64_t at = own_bytes;
+        own_bytes += (1 + L + 3) & ~(uint64_t)3;
+        return at;
+    }
+    uint64_t close(const uint8_t* pool) {   // after the last unit -> the offset of `lo` in the caller's pool
+        bytes = (uint64_t)(hi - lo);
+        return (uint64_t)(lo - pool);
+    }
+};
+struct Spliced : StreamOwner {
+    int kind = 0; uint32_t mode = 0, n = 0;
+    uint64_t cap_n = 0, cap_raw = 0, cap_own = 0, runs_cap = 0, total_runs = 0;
+    DevBuf raw, matrix, err;
+    DevBuf score, left_score, right_score, q_start, r_start, q_end, r_end, cells, status, cigar_len, out_off, runs;
+    float pack_ms = 0, splice_ms = 0;
+    bool ran = false;
+};
+}  // namespace
+// ba_*_batch_create's own arguments. what: "extension" / "chain"; the two sentences that differ are passed in.
+static int spliced_check_params(const char* what, const char* cannot_be, const char* x_drop_why, int kind, Gaps gaps, SizeRange size, int32_t x_drop,
+                                uint32_t mode) {
+    if (kind == BA_KIND_PROFILE_) return fail("%s batches take a sequence matrix: profile batches cannot be %s", what, cannot_be);
     if (kind < 0 || kind > 2) return fail("unknown matrix kind %d", kind);
-    if (!(mode & BA_X_DROP)) return fail("extension batches need BA_X_DROP: a side ends where its score drops");
+    if (!(mode & BA_X_DROP)) return fail("%s batches need BA_X_DROP: %s", what, x_drop_why);
     if (mode & (BA_LOCAL_START | BA_FREE_QUERY_START_GAPS | BA_FREE_QUERY_END_GAPS))
-        return fail("extension batches take BA_X_DROP, BA_TRACE and BA_CIGAR_EQ only: LOCAL_START and FREE_QUERY_* are rejected");
+        return fail("%s batches take BA_X_DROP, BA_TRACE and BA_CIGAR_EQ only: LOCAL_START and FREE_QUERY_* are rejected", what);
     const size_t min_size = size.min < 16 ? 16 : size.min, max_size = size.max < 16 ? 16 : size.max;   // (as batch_build)
     std::string why;
     if (check_align_params(false, gaps, min_size, max_size, x_drop, mode, &why)) return fail("%s", why.c_str());
     if (min_size > max_size) return fail("min block size exceeds max block size");
     return 0;
 }
+// create, before the object's own buffers: the capacities are this set's; the caller's bytes, the pool of the units' own images, the error word
+static int spliced_create_head(Spliced* e, const SplicedSet& S, size_t n, DevBuf& own_pool) {
+    e->cap_n = n; e->cap_raw = S.bytes; e->cap_own = S.own_bytes;
+    return e->raw.alloc(S.bytes) || own_pool.alloc(S.own_bytes + 64) || e->err.alloc(8);
+}
+// create, after them: the last shared buffers and the matrix (1024 bytes, as batch_build lays it out)
+static int spliced_create_tail(Spliced* e, size_t n, const void* matrix) {
+    if (e->cells.alloc(n * 8) || e->out_off.alloc((n + 1) * 8) || e->matrix.alloc(1024)) return 1;
+    int8_t tmp[1024] = {0};
+    if (e->kind == BA_KIND_BYTES) { const ByteMatrix* bm = (const ByteMatrix*)matrix; tmp[0] = bm->match_score; tmp[1] = bm->mismatch_score; }
+    else memcpy(tmp, matrix, e->kind == BA_KIND_AA ? 27 * 32 : 8 * 16);
+    return h2d(e->matrix, tmp, 1024);
+}
+// reload: what the set may not exceed. They return before anything is cleared: the earlier set stays loaded.
+static int over_count(const char* nouns, size_t n, uint64_t cap) {
+    return n > cap ? fail("reload: %zu %s exceed the batch's capacity of %llu", n, nouns, (unsigned long long)cap) : 0;
+}
+static int over_bytes(const Spliced* e, const SplicedSet& S, const char* own) {
+    if (S.bytes > e->cap_raw) return fail("reload: %llu sequence bytes exceed the batch's capacity of %llu", (unsigned long long)S.bytes, (unsigned long long)e->cap_raw);
+    if (S.own_bytes > e->cap_own) return fail("reload: the %s (%llu image bytes) exceed the batch's capacity of %llu", own, (unsigned long long)S.own_bytes, (unsigned long long)e->cap_own);
+    return 0;
+}
+static int no_inner(const char* pieces, const PieceSet& P, const std::unique_ptr<BaBatch>& inner) {
+    return P.size() && !inner ? fail("reload: the set has %s to align, and the batch was created with none", pieces) : 0;
+}
+// The pieces of one inner batch into it (built on create, reloaded after); `side`: the pieces' indices -> their positions in its device
+// order. what: what a piece belongs to ("seed", "chain"), for the message about a byte outside the alphabet.
+static int spliced_load_pieces(Spliced* e, std::unique_ptr<BaBatch>& inner, const PieceSet& P, const uint8_t* lo, const char* what, const void* matrix,
+                               Gaps gaps, SizeRange size, int32_t x_drop, uint32_t mode, bool create, std::vector<uint32_t>& side) {
+    const size_t np = P.size();
+    if (!np) return 0;
+    float ms = 0;
+    ExtImages X;
+    X.host_base = lo; X.dev_base = e->raw.as<uint8_t>(); X.flags = P.flags.data(); X.seed_of = P.owner.data(); X.pack_ms = &ms; X.what = what;
+    auto get = [&](size_t p, int w, const uint8_t** ptr, size_t* len) { *ptr = P.src[2 * p + w]; *len = P.len[2 * p + w]; };
+    if (create) {
+        inner.reset(batch_build(e->kind, matrix, gaps, size, x_drop, mode, np, false, get, NoProfiles(), &X));
+        if (!inner) return 1;
+    } else if (batch_reload(inner.get(), np, false, get, NoProfiles(), &X)) return 1;
+    e->pack_ms += ms;
+    if (!inner->h_order.empty()) {
+        std::vector<uint32_t> pos(np);
+        for (uint32_t d = 0; d < np; d++) pos[inner->h_order[d]] = d;
+        for (uint32_t& x : side) if (x != NO_PIECE) x = pos[x];
+    }
+    return 0;
+}
+// The units' own images (n seeds or anchors; their six arrays are on the device): k_pack_images timed, its time added to pack_ms
+// -> *err: the kernel's error word, ~0 if every byte is in the alphabet
+static int spliced_pack_own(Spliced* e, const DevBuf& raw_q, const DevBuf& raw_r, const DevBuf& flags, const DevBuf& img_q, const DevBuf& img_r,
+                            const DevBuf& len, const DevBuf& pool, size_t n, unsigned long long* err) {
+    HIP_TRY(hipMemset(e->err.p, 0xff, 8));
+    HIP_TRY(hipEventRecord(e->ev[0], e->stream));
+    HIP_TRY(ba_launch_pack_images(e->stream, seq_kind(e->kind), e->raw.as<uint8_t>(), raw_q.as<uint64_t>(), raw_r.as<uint64_t>(), flags.as<uint8_t>(),
+                                  img_q.as<uint64_t>(), len.as<uint32_t>(), img_r.as<uint64_t>(), len.as<uint32_t>(), pool.as<uint8_t>(), 0, (uint32_t)n,
+                                  e->err.as<unsigned long long>()));
+    HIP_TRY(hipEventRecord(e->ev[1], e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    float ms = 0;
+    if (e->elapsed(0, 1, &ms)) return 1;
+    e->pack_ms += ms;
+    return d2h(e->err, err, 1);
+}
+// The splice behind the fills: `results` launched and timed; with TRACE the total of the runs read, `runs` grown to it, `gather` launched
+// and timed (it reads e->runs afresh: the buffer may have moved).
+template <class Results, class Gather>
+static int spliced_splice(Spliced* e, Results results, Gather gather) {
+    HIP_TRY(hipEventRecord(e->ev[0], e->stream));
+    HIP_TRY(results());
+    HIP_TRY(hipEventRecord(e->ev[1], e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (e->elapsed(0, 1, &e->splice_ms)) return 1;
+    if (e->mode & BA_TRACE) {
+        uint64_t total = 0;
+        HIP_TRY(hipMemcpy(&total, e->out_off.as<uint64_t>() + e->n, 8, hipMemcpyDeviceToHost));
+        if (total > e->runs_cap) {
+            if (e->runs.alloc(total * 4)) return 1;
+            e->runs_cap = total;
+        }
+        HIP_TRY(hipEventRecord(e->ev[2], e->stream));
+        HIP_TRY(gather());
+        HIP_TRY(hipEventRecord(e->ev[3], e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        float ms = 0;
+        if (e->elapsed(2, 3, &ms)) return 1;
+        e->splice_ms += ms;
+        e->total_runs = total;
+    }
+    e->ran = true;
+    return 0;
+}
+// ba_*_batch_results and ba_*_batch_cigars. call: "extend_batch" / "chain_batch".
+static int spliced_results(Spliced* e, const char* call, int32_t* score, uint32_t* q_start, uint32_t* r_start, uint32_t* q_end, uint32_t* r_end,
+                           int32_t* left_score, int32_t* right_score, uint64_t* cells, uint32_t* cigar_len, uint32_t* status) {
+    if (!e) return fail("null batch");
+    if (!e->ran) return fail("ba_%s_run has not been called", call);
+    HIP_TRY(hipSetDevice(e->device));
+    if (d2h(e->score, score, e->n) || d2h(e->q_start, q_start, e->n) || d2h(e->r_start, r_start, e->n) || d2h(e->q_end, q_end, e->n) ||
+        d2h(e->r_end, r_end, e->n) || d2h(e->left_score, left_score, e->n) || d2h(e->right_score, right_score, e->n) ||
+        d2h(e->cells, cells, e->n) || d2h(e->cigar_len, cigar_len, e->n) || d2h(e->status, status, e->n)) return 1;
+    return 0;
+}
+static int spliced_cigars(Spliced* e, const char* call, uint32_t* runs, uint64_t capacity) {
+    if (!e) return fail("null batch");
+    if (!(e->mode & BA_TRACE)) return fail("batch was created without BA_TRACE");
+    if (!e->ran) return fail("ba_%s_run has not been called", call);
+    if (e->total_runs > capacity) return fail("cigar buffer too small: need %llu entries", (unsigned long long)e->total_runs);
+    if (!e->total_runs) return 0;
+    if (!runs) return fail("null argument");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipMemcpy(runs, e->runs.p, e->total_runs * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ------------------------------------------------------------------ seed-and-extend batches (ba_extend_batch_*)
+// One seed = one result: X-drop alignment leftwards from the seed (reversed prefixes) and rightwards from its end. Every non-empty side of
+// every seed is a pair of ONE ordinary batch, the seeds' own images are packed beside them; the splice (ba_extend.hip) then scores the
+// seeds and joins both sides' results and CIGAR runs per seed.
+struct ExtSet : SplicedSet {   // a seed set cut into sides
+    PieceSet sides;
+    std::vector<uint32_t> side;                        // 2 per seed (left, right): index of the side, or NO_PIECE
+    std::vector<uint64_t> s_raw_q, s_raw_r, s_img_q, s_img_r;   // the seeds' own images: source offsets in the upload, offsets in the seed pool
+    std::vector<uint8_t> s_flags;                      // 2 per seed
+    // per seed, the whole query and reference: source offsets in the upload, lengths, strand (ba_extend_batch_text renders from them)
+    std::vector<uint64_t> t_raw_q, t_raw_r;
+    std::vector<uint32_t> t_ql, t_rl;
+    std::vector<uint8_t> t_strand;
+};
 // Check a seed set (the mode and the matrix kind are checked already) and cut it into sides.
 static int ext_plan(int kind, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len,
                     const uint32_t* q_seed, const uint32_t* r_seed, const uint32_t* seed_len, const uint8_t* strand, size_t n, ExtSet& S) {
@@ -1536,7 +1724,6 @@ static int ext_plan(int kind, const uint8_t* pool, const uint64_t* q_off, const 
     S.t_raw_q.resize(n); S.t_raw_r.resize(n); S.t_ql.assign(q_len, q_len + n); S.t_rl.assign(r_len, r_len + n);
     S.t_strand.assign(n, 0);
     if (strand) S.t_strand.assign(strand, strand + n);
-    const uint8_t* hi = nullptr;
     for (size_t p = 0; p < n; p++) {
         const uint64_t Q = q_len[p], R = r_len[p], s = q_seed[p], t = r_seed[p], L = seed_len[p];
         if (L == 0) return fail("seed %zu: seed_len must be at least 1", p);
@@ -1544,18 +1731,10 @@ static int ext_plan(int kind, const uint8_t* pool, const uint64_t* q_off, const 
             return fail("seed %zu: the seed (query %llu + %llu, reference %llu + %llu) runs past the end of its sequences (%llu, %llu)", p,
                         (unsigned long long)s, (unsigned long long)L, (unsigned long long)t, (unsigned long long)L, (unsigned long long)Q, (unsigned long long)R);
         const uint8_t st = strand ? strand[p] : 0;
-        if (st > 1) return fail("seed %zu: strand must be 0 or 1", p);
-        if (st && kind != BA_KIND_NUC) return fail("seed %zu: strand needs a NucMatrix batch (reverse complement is nucleotide-only)", p);
         const uint8_t* q = pool + q_off[p]; const uint8_t* r = pool + r_off[p];
-        for (const uint8_t* x : {q, r}) if (!S.lo || x < S.lo) S.lo = x;
-        if (!hi || q + Q > hi) hi = q + Q;
-        if (r + R > hi) hi = r + R;
+        if (S.add(kind, "seed", p, st, q, Q, r, R)) return 1;
         auto add_side = [&](int w, const uint8_t* qs, uint64_t ql, uint8_t qf, const uint8_t* rs, uint64_t rl, uint8_t rf) {
-            if (!ql || !rl) { S.side[2 * p + w] = ba::EXT_NO_SIDE; return; }
-            S.side[2 * p + w] = (uint32_t)S.seed_of.size();
-            S.seed_of.push_back((uint32_t)p);
-            S.src.push_back(qs); S.len.push_back((uint32_t)ql); S.flags.push_back(qf);
-            S.src.push_back(rs); S.len.push_back((uint32_t)rl); S.flags.push_back(rf);
+            S.side[2 * p + w] = ql && rl ? S.sides.add(p, qs, ql, qf, rs, rl, rf) : NO_PIECE;
         };
         // (minus strand: q is the reverse complement of the caller's bytes; the seed's frame is that of q)
         if (st) add_side(0, q + (Q - s), s, ba::IMG_COMPLEMENT, r, t, ba::IMG_REVERSE);
@@ -1564,24 +1743,18 @@ static int ext_plan(int kind, const uint8_t* pool, const uint64_t* q_off, const 
         else add_side(1, q + s + L, Q - s - L, 0, r + t + L, R - t - L, 0);
         S.s_raw_q[p] = (uint64_t)((st ? q + (Q - s - L) : q + s) - pool); S.s_raw_r[p] = (uint64_t)(r + t - pool);   // (made relative to lo below)
         S.s_flags[2 * p] = st ? (ba::IMG_REVERSE | ba::IMG_COMPLEMENT) : 0; S.s_flags[2 * p + 1] = 0;
-        S.s_img_q[p] = S.seed_bytes; S.seed_bytes += (1 + L + 3) & ~(uint64_t)3;
-        S.s_img_r[p] = S.seed_bytes; S.seed_bytes += (1 + L + 3) & ~(uint64_t)3;
+        S.s_img_q[p] = S.own_image(L); S.s_img_r[p] = S.own_image(L);
         S.t_raw_q[p] = q_off[p]; S.t_raw_r[p] = r_off[p];   // (made relative to lo below)
     }
-    const uint64_t base = (uint64_t)(S.lo - pool);
+    const uint64_t base = S.close(pool);
     for (size_t p = 0; p < n; p++) { S.s_raw_q[p] -= base; S.s_raw_r[p] -= base; S.t_raw_q[p] -= base; S.t_raw_r[p] -= base; }
-    S.bytes = (uint64_t)(hi - S.lo);
-    if (S.seed_of.size() > 0x7fffffffu) return fail("too many sides");
+    if (S.sides.size() > 0x7fffffffu) return fail("too many sides");
     return 0;
 }
-struct BaExtendBatch {
-    int device = 0, kind = 0; uint32_t mode = 0;
+struct BaExtendBatch : Spliced {
     std::unique_ptr<BaBatch> inner;   // the sides of the loaded set; null if the batch was created with none (nothing to fill)
-    uint32_t n = 0, n_sides = 0;
-    uint64_t cap_n = 0, cap_raw = 0, cap_seed = 0, runs_cap = 0, total_runs = 0;
-    hipStream_t stream = nullptr; hipEvent_t ev[4] = {};
-    DevBuf raw, seed_pool, seed_q, seed_r, seed_raw_q, seed_raw_r, seed_flags, seed_len, q_seed, r_seed, side, matrix, err;
-    DevBuf score, left_score, right_score, q_start, r_start, q_end, r_end, cells, status, cigar_len, join, out_off, runs;
+    uint32_t n_sides = 0;
+    DevBuf seed_pool, seed_q, seed_r, seed_raw_q, seed_raw_r, seed_flags, seed_len, q_seed, r_seed, side, join;
     DevBuf stats;   // per-seed statistics (ba_extend_batch_stats), allocated on the first call
     // alignment strings (ba_extend_batch_text): the sequences' source offsets, lengths and strands of the loaded set (host copies, uploaded by
     // the first text call after a load) and their device buffers, allocated on the first call
@@ -1592,8 +1765,7 @@ struct BaExtendBatch {
     DevBuf t_raw_q, t_raw_r, t_ql, t_rl, t_strand;
     TextState text;
     uint64_t runs_done = 0;
-    float fill_ms = 0, pack_ms = 0, splice_ms = 0;
-    bool ran = false;
+    float fill_ms = 0;
     // optimal paths (ba_extend_batch_exact_paths): the requested seeds, their run counts, offsets and joined runs on the device, and the
     // request they belong to with its records, kept for the second call of the two-call pattern (a load drops it)
     DevBuf xp_sel, xp_nrun, xp_off, xp_runs, xp_seed, xp_no_off;   // (xp_seed: the seeds' ungapped scores; xp_no_off: zero offsets for a set without sides)
@@ -1616,77 +1788,31 @@ struct BaExtendBatch {
         ep.join = join.as<uint32_t>(); ep.out_off = out_off.as<uint64_t>(); ep.runs = runs.as<uint32_t>();
         return ep;
     }
-    ~BaExtendBatch() {
-        inner.reset();
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 // Load a planned set into the batch: the caller's bytes once to the device, the sides into the inner batch (built on create, reloaded
 // after), the seeds' own images. `create`: size every buffer for this set; otherwise the set must fit them.
 static int ext_load(BaExtendBatch* e, const ExtSet& S, size_t n, const void* matrix, Gaps gaps, SizeRange size, int32_t x_drop,
                     const uint32_t* q_seed, const uint32_t* r_seed, const uint32_t* seed_len, bool create) {
-    const size_t n_sides = S.seed_of.size();
     if (create) {
-        e->cap_n = n; e->cap_raw = S.bytes; e->cap_seed = S.seed_bytes;
-        if (e->raw.alloc(S.bytes) || e->seed_pool.alloc(S.seed_bytes + 64) || e->err.alloc(8)) return 1;
+        if (spliced_create_head(e, S, n, e->seed_pool)) return 1;
         DevBuf* per_seed4[] = {&e->seed_len, &e->q_seed, &e->r_seed, &e->score, &e->left_score, &e->right_score, &e->q_start, &e->r_start,
                                &e->q_end, &e->r_end, &e->status, &e->cigar_len, &e->join};
         for (DevBuf* d : per_seed4) if (d->alloc(n * 4)) return 1;
         if (e->seed_q.alloc(n * 8) || e->seed_r.alloc(n * 8) || e->seed_raw_q.alloc(n * 8) || e->seed_raw_r.alloc(n * 8) || e->seed_flags.alloc(2 * n) ||
-            e->side.alloc(2 * n * 4) || e->cells.alloc(n * 8) || e->out_off.alloc((n + 1) * 8) || e->matrix.alloc(1024)) return 1;
-        int8_t tmp[1024] = {0};
-        if (e->kind == BA_KIND_BYTES) { const ByteMatrix* bm = (const ByteMatrix*)matrix; tmp[0] = bm->match_score; tmp[1] = bm->mismatch_score; }
-        else memcpy(tmp, matrix, e->kind == BA_KIND_AA ? 27 * 32 : 8 * 16);
-        HIP_TRY(hipMemcpy(e->matrix.p, tmp, 1024, hipMemcpyHostToDevice));
-    } else {
-        if (n > e->cap_n) return fail("reload: %zu seeds exceed the batch's capacity of %llu", n, (unsigned long long)e->cap_n);
-        if (S.bytes > e->cap_raw) return fail("reload: %llu sequence bytes exceed the batch's capacity of %llu", (unsigned long long)S.bytes, (unsigned long long)e->cap_raw);
-        if (S.seed_bytes > e->cap_seed) return fail("reload: the seeds (%llu image bytes) exceed the batch's capacity of %llu", (unsigned long long)S.seed_bytes, (unsigned long long)e->cap_seed);
-        if (n_sides && !e->inner) return fail("reload: the set has sides to align, and the batch was created with none");
-    }
+            e->side.alloc(2 * n * 4) || spliced_create_tail(e, n, matrix)) return 1;
+    } else if (over_count("seeds", n, e->cap_n) || over_bytes(e, S, "seeds") || no_inner("sides", S.sides, e->inner)) return 1;
     e->n = 0; e->ran = false; e->pack_ms = 0; e->xp_valid = false;   // (a failure from here on leaves no seeds loaded)
-    HIP_TRY(hipMemcpy(e->raw.p, S.lo, S.bytes, hipMemcpyHostToDevice));
-    ExtImages X;
-    X.host_base = S.lo; X.dev_base = e->raw.as<uint8_t>(); X.flags = S.flags.data(); X.seed_of = S.seed_of.data(); X.pack_ms = &e->pack_ms;
-    auto get = [&](size_t p, int w, const uint8_t** ptr, size_t* len) { *ptr = S.src[2 * p + w]; *len = S.len[2 * p + w]; };
-    if (n_sides) {
-        if (create) {
-            e->inner.reset(batch_build(e->kind, matrix, gaps, size, x_drop, e->mode, n_sides, false, get, NoProfiles(), &X));
-            if (!e->inner) return 1;
-        } else if (batch_reload(e->inner.get(), n_sides, false, get, NoProfiles(), &X)) return 1;
-    }
-    // sides -> their positions in the inner batch's device order
+    if (h2d(e->raw, S.lo, S.bytes)) return 1;
     std::vector<uint32_t> side(S.side);
-    if (n_sides && !e->inner->h_order.empty()) {
-        std::vector<uint32_t> pos(n_sides);
-        for (uint32_t d = 0; d < n_sides; d++) pos[e->inner->h_order[d]] = d;
-        for (uint32_t& x : side) if (x != ba::EXT_NO_SIDE) x = pos[x];
-    }
-    HIP_TRY(hipMemcpy(e->side.p, side.data(), 2 * n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->q_seed.p, q_seed, n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->r_seed.p, r_seed, n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->seed_len.p, seed_len, n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->seed_q.p, S.s_img_q.data(), n * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->seed_r.p, S.s_img_r.data(), n * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->seed_raw_q.p, S.s_raw_q.data(), n * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->seed_raw_r.p, S.s_raw_r.data(), n * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->seed_flags.p, S.s_flags.data(), 2 * n, hipMemcpyHostToDevice));
+    if (spliced_load_pieces(e, e->inner, S.sides, S.lo, "seed", matrix, gaps, size, x_drop, e->mode, create, side)) return 1;
+    if (h2d(e->side, side.data(), 2 * n) || h2d(e->q_seed, q_seed, n) || h2d(e->r_seed, r_seed, n) || h2d(e->seed_len, seed_len, n) ||
+        h2d(e->seed_q, S.s_img_q.data(), n) || h2d(e->seed_r, S.s_img_r.data(), n) || h2d(e->seed_raw_q, S.s_raw_q.data(), n) ||
+        h2d(e->seed_raw_r, S.s_raw_r.data(), n) || h2d(e->seed_flags, S.s_flags.data(), 2 * n)) return 1;
     HIP_TRY(hipMemset(e->cigar_len.p, 0, n * 4));
-    HIP_TRY(hipMemset(e->err.p, 0xff, 8));
-    HIP_TRY(hipEventRecord(e->ev[0], e->stream));
-    HIP_TRY(ba_launch_pack_images(e->stream, seq_kind(e->kind), e->raw.as<uint8_t>(), e->seed_raw_q.as<uint64_t>(), e->seed_raw_r.as<uint64_t>(),
-                                  e->seed_flags.as<uint8_t>(), e->seed_q.as<uint64_t>(), e->seed_len.as<uint32_t>(), e->seed_r.as<uint64_t>(),
-                                  e->seed_len.as<uint32_t>(), e->seed_pool.as<uint8_t>(), 0, (uint32_t)n, e->err.as<unsigned long long>()));
-    HIP_TRY(hipEventRecord(e->ev[1], e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e->ev[0], e->ev[1]));
-    e->pack_ms += ms;
     unsigned long long err = 0;
-    HIP_TRY(hipMemcpy(&err, e->err.p, 8, hipMemcpyDeviceToHost));
+    if (spliced_pack_own(e, e->seed_raw_q, e->seed_raw_r, e->seed_flags, e->seed_q, e->seed_r, e->seed_len, e->seed_pool, n, &err)) return 1;
     if (err != ~0ull) return fail("seed %llu: byte 0x%02x is outside the matrix alphabet", err >> 8, (unsigned)(err & 0xff));
-    e->n = (uint32_t)n; e->n_sides = (uint32_t)n_sides;
+    e->n = (uint32_t)n; e->n_sides = (uint32_t)S.sides.size();
     e->h_t_raw_q = S.t_raw_q; e->h_t_raw_r = S.t_raw_r; e->h_t_ql = S.t_ql; e->h_t_rl = S.t_rl; e->h_t_strand = S.t_strand;
     e->t_uploaded = false;
     return 0;
@@ -1695,43 +1821,16 @@ static int ext_load(BaExtendBatch* e, const ExtSet& S, size_t n, const void* mat
 // ------------------------------------------------------------------ anchor-chain batches (ba_chain_batch_*)
 // One chain of colinear anchors = one result: X-drop extension leftwards from the first anchor and rightwards from the last one, as for a
 // seed; a global alignment of the slices between consecutive anchors; the anchors themselves ungapped. The ends of every chain are the pairs
-// of ONE X-drop batch, the gaps with two non-empty slices the pairs of ONE global batch (batch_build over device-cut images, as the sides of
-// an extension batch: the caller's bytes are uploaded once); the segmented splice (ba_chain.hip) scores the anchors, makes the runs of the
-// gaps with one empty slice and joins everything per chain on the device, in the caller's order.
-struct ChainPieceSet {   // the pairs of one inner batch (host addresses into the caller's pool; nothing is copied)
-    std::vector<const uint8_t*> src;   // 2 per piece (query, reference): first byte of the slice
-    std::vector<uint32_t> len;         // 2 per piece
-    std::vector<uint8_t> flags;        // 2 per piece: ba::IMG_*
-    std::vector<uint32_t> chain_of;    // per piece
-    size_t size() const { return chain_of.size(); }
-    uint32_t add(size_t c, const uint8_t* qs, uint64_t ql, uint8_t qf, const uint8_t* rs, uint64_t rl, uint8_t rf) {
-        chain_of.push_back((uint32_t)c);
-        src.push_back(qs); len.push_back((uint32_t)ql); flags.push_back(qf);
-        src.push_back(rs); len.push_back((uint32_t)rl); flags.push_back(rf);
-        return (uint32_t)chain_of.size() - 1;
-    }
-};
-struct ChainSet {   // a set of chains cut into pieces
-    const uint8_t* lo = nullptr; uint64_t bytes = 0;   // extent of the chains' sequences in the caller's pool
-    ChainPieceSet ends, gaps;
-    std::vector<uint32_t> end_side;                    // 2 per chain (left, right): index of the end in `ends`, or ba::CHAIN_NO_PIECE
-    std::vector<uint32_t> gap_side;                    // per anchor: index in `gaps` of the gap behind it, or ba::CHAIN_NO_PIECE
+// of ONE X-drop batch, the gaps with two non-empty slices the pairs of ONE global batch; the segmented splice (ba_chain.hip) scores the
+// anchors, makes the runs of the gaps with one empty slice and joins everything per chain.
+struct ChainSet : SplicedSet {   // a set of chains cut into pieces
+    PieceSet ends, gaps;
+    std::vector<uint32_t> end_side;                    // 2 per chain (left, right): index of the end in `ends`, or NO_PIECE
+    std::vector<uint32_t> gap_side;                    // per anchor: index in `gaps` of the gap behind it, or NO_PIECE
     std::vector<uint64_t> a_raw_q, a_raw_r, a_img_q, a_img_r;   // the anchors' own images: source offsets in the upload, offsets in the anchor pool
     std::vector<uint8_t> a_flags;                      // 2 per anchor
-    uint64_t anchor_bytes = 0, n_anchors = 0;
+    uint64_t n_anchors = 0;
 };
-static int chain_check_params(int kind, Gaps gaps, SizeRange size, int32_t x_drop, uint32_t mode) {   // ba_chain_batch_create's own arguments
-    if (kind == BA_KIND_PROFILE_) return fail("chain batches take a sequence matrix: profile batches cannot be chained");
-    if (kind < 0 || kind > 2) return fail("unknown matrix kind %d", kind);
-    if (!(mode & BA_X_DROP)) return fail("chain batches need BA_X_DROP: the ends of a chain end where their score drops");
-    if (mode & (BA_LOCAL_START | BA_FREE_QUERY_START_GAPS | BA_FREE_QUERY_END_GAPS))
-        return fail("chain batches take BA_X_DROP, BA_TRACE and BA_CIGAR_EQ only: LOCAL_START and FREE_QUERY_* are rejected");
-    const size_t min_size = size.min < 16 ? 16 : size.min, max_size = size.max < 16 ? 16 : size.max;   // (as batch_build)
-    std::string why;
-    if (check_align_params(false, gaps, min_size, max_size, x_drop, mode, &why)) return fail("%s", why.c_str());
-    if (min_size > max_size) return fail("min block size exceeds max block size");
-    return 0;
-}
 // Check a set of chains (the mode and the matrix kind are checked already) and cut it into ends, gaps and anchors.
 static int chain_plan(int kind, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len,
                       const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor, const uint32_t* anchor_len, const uint8_t* strand,
@@ -1748,18 +1847,13 @@ static int chain_plan(int kind, const uint8_t* pool, const uint64_t* q_off, cons
     if (na > (1u << 28)) return fail("a chain batch must hold at most 2^28 anchors");   // (k_pack_images: two workgroups per anchor)
     S = ChainSet();
     S.n_anchors = na;
-    S.end_side.resize(2 * n); S.gap_side.assign(na, ba::CHAIN_NO_PIECE);
+    S.end_side.resize(2 * n); S.gap_side.assign(na, NO_PIECE);
     S.a_raw_q.resize(na); S.a_raw_r.resize(na); S.a_img_q.resize(na); S.a_img_r.resize(na); S.a_flags.resize(2 * na);
-    const uint8_t* hi = nullptr;
     for (size_t c = 0; c < n; c++) {
         const uint64_t Q = q_len[c], R = r_len[c];
         const uint8_t st = strand ? strand[c] : 0;
-        if (st > 1) return fail("chain %zu: strand must be 0 or 1", c);
-        if (st && kind != BA_KIND_NUC) return fail("chain %zu: strand needs a NucMatrix batch (reverse complement is nucleotide-only)", c);
         const uint8_t* q = pool + q_off[c]; const uint8_t* r = pool + r_off[c];
-        for (const uint8_t* x : {q, r}) if (!S.lo || x < S.lo) S.lo = x;
-        if (!hi || q + Q > hi) hi = q + Q;
-        if (r + R > hi) hi = r + R;
+        if (S.add(kind, "chain", c, st, q, Q, r, R)) return 1;
         // (minus strand: q is the reverse complement of the caller's bytes, and a slice [a, b) of it the reversed, complemented slice
         // [Q - b, Q - a) of those bytes)
         const uint8_t fwd = st ? (ba::IMG_REVERSE | ba::IMG_COMPLEMENT) : 0;
@@ -1783,33 +1877,26 @@ static int chain_plan(int kind, const uint8_t* pool, const uint64_t* q_off, cons
             }
             S.a_raw_q[a] = (uint64_t)(q_slice(s, s + L) - pool); S.a_raw_r[a] = (uint64_t)(r + t - pool);   // (made relative to lo below)
             S.a_flags[2 * a] = fwd; S.a_flags[2 * a + 1] = 0;
-            S.a_img_q[a] = S.anchor_bytes; S.anchor_bytes += (1 + L + 3) & ~(uint64_t)3;
-            S.a_img_r[a] = S.anchor_bytes; S.anchor_bytes += (1 + L + 3) & ~(uint64_t)3;
+            S.a_img_q[a] = S.own_image(L); S.a_img_r[a] = S.own_image(L);
         }
         // the ends: the two sides of a seed (ext_plan), left of the first anchor and right of the last one
         const uint64_t s = q_anchor[a0], t = r_anchor[a0], al = a0 + K - 1, eq = (uint64_t)q_anchor[al] + anchor_len[al], er = (uint64_t)r_anchor[al] + anchor_len[al];
-        S.end_side[2 * c] = (s && t) ? S.ends.add(c, st ? q + (Q - s) : q, s, st ? ba::IMG_COMPLEMENT : ba::IMG_REVERSE, r, t, ba::IMG_REVERSE) : ba::CHAIN_NO_PIECE;
-        S.end_side[2 * c + 1] = (Q - eq && R - er) ? S.ends.add(c, q_slice(eq, Q), Q - eq, fwd, r + er, R - er, 0) : ba::CHAIN_NO_PIECE;
+        S.end_side[2 * c] = (s && t) ? S.ends.add(c, st ? q + (Q - s) : q, s, st ? ba::IMG_COMPLEMENT : ba::IMG_REVERSE, r, t, ba::IMG_REVERSE) : NO_PIECE;
+        S.end_side[2 * c + 1] = (Q - eq && R - er) ? S.ends.add(c, q_slice(eq, Q), Q - eq, fwd, r + er, R - er, 0) : NO_PIECE;
     }
-    const uint64_t base = (uint64_t)(S.lo - pool);
+    const uint64_t base = S.close(pool);
     for (uint64_t a = 0; a < na; a++) { S.a_raw_q[a] -= base; S.a_raw_r[a] -= base; }
-    S.bytes = (uint64_t)(hi - S.lo);
     if (S.ends.size() > 0x7fffffffu || S.gaps.size() > 0x7fffffffu) return fail("too many pieces");
     return 0;
 }
-struct BaChainBatch {
-    int device = 0, kind = 0; uint32_t mode = 0;
+struct BaChainBatch : Spliced {
     int gap_open = 0, gap_extend = 0;
     std::unique_ptr<BaBatch> ends, gaps;   // the X-drop batch of the ends, the global batch of the gaps; null if the batch was created without such pieces
-    uint32_t n = 0, n_anchors = 0, n_ends = 0, n_gaps = 0;
-    uint64_t cap_n = 0, cap_anchors = 0, cap_raw = 0, cap_anchor_bytes = 0, runs_cap = 0, total_runs = 0;
-    hipStream_t stream = nullptr; hipEvent_t ev[4] = {};
-    DevBuf raw, anchor_pool, anchor_q, anchor_r, anchor_raw_q, anchor_raw_r, anchor_flags, anchor_len, q_anchor, r_anchor, anchor_first, end_side, gap_side,
-           matrix, err;
+    uint32_t n_anchors = 0, n_ends = 0, n_gaps = 0;
+    uint64_t cap_anchors = 0;
+    DevBuf anchor_pool, anchor_q, anchor_r, anchor_raw_q, anchor_raw_r, anchor_flags, anchor_len, q_anchor, r_anchor, anchor_first, end_side, gap_side;
     DevBuf a_score, a_nrun, a_ops, a_flen, a_llen;
-    DevBuf score, left_score, right_score, q_start, r_start, q_end, r_end, cells, status, cigar_len, out_off, runs;
-    float ends_ms = 0, gaps_ms = 0, pack_ms = 0, splice_ms = 0;
-    bool ran = false;
+    float ends_ms = 0, gaps_ms = 0;
     static ba::ChainPieces pieces(const BaBatch* b) {
         ba::ChainPieces pc{};
         if (!b) return pc;
@@ -1834,61 +1921,25 @@ struct BaChainBatch {
         cp.out_off = out_off.as<uint64_t>(); cp.runs = runs.as<uint32_t>();
         return cp;
     }
-    ~BaChainBatch() {
-        ends.reset(); gaps.reset();
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
-// The pieces of one inner batch into it (built on create, reloaded after); `side`: the pieces' indices -> their positions in its device order.
-static int chain_load_pieces(BaChainBatch* e, std::unique_ptr<BaBatch>& inner, const ChainPieceSet& P, const uint8_t* lo, const void* matrix, Gaps gaps,
-                             SizeRange size, int32_t x_drop, uint32_t mode, bool create, std::vector<uint32_t>& side) {
-    const size_t np = P.size();
-    if (!np) return 0;
-    float ms = 0;
-    ExtImages X;
-    X.host_base = lo; X.dev_base = e->raw.as<uint8_t>(); X.flags = P.flags.data(); X.seed_of = P.chain_of.data(); X.pack_ms = &ms; X.what = "chain";
-    auto get = [&](size_t p, int w, const uint8_t** ptr, size_t* len) { *ptr = P.src[2 * p + w]; *len = P.len[2 * p + w]; };
-    if (create) {
-        inner.reset(batch_build(e->kind, matrix, gaps, size, x_drop, mode, np, false, get, NoProfiles(), &X));
-        if (!inner) return 1;
-    } else if (batch_reload(inner.get(), np, false, get, NoProfiles(), &X)) return 1;
-    e->pack_ms += ms;
-    if (!inner->h_order.empty()) {
-        std::vector<uint32_t> pos(np);
-        for (uint32_t d = 0; d < np; d++) pos[inner->h_order[d]] = d;
-        for (uint32_t& x : side) if (x != ba::CHAIN_NO_PIECE) x = pos[x];
-    }
-    return 0;
-}
 // Load a planned set into the batch: the caller's bytes once to the device, the ends and the gaps into their inner batches, the anchors'
 // own images. `create`: size every buffer for this set; otherwise the set must fit them.
 static int chain_load(BaChainBatch* e, const ChainSet& S, size_t n, const void* matrix, Gaps gaps, SizeRange size, int32_t x_drop,
                       const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor, const uint32_t* anchor_len, bool create) {
     const size_t na = S.n_anchors;
     if (create) {
-        e->cap_n = n; e->cap_anchors = na; e->cap_raw = S.bytes; e->cap_anchor_bytes = S.anchor_bytes;
-        if (e->raw.alloc(S.bytes) || e->anchor_pool.alloc(S.anchor_bytes + 64) || e->err.alloc(8)) return 1;
+        e->cap_anchors = na;
+        if (spliced_create_head(e, S, n, e->anchor_pool)) return 1;
         DevBuf* per_chain4[] = {&e->score, &e->left_score, &e->right_score, &e->q_start, &e->r_start, &e->q_end, &e->r_end, &e->status, &e->cigar_len};
         for (DevBuf* d : per_chain4) if (d->alloc(n * 4)) return 1;
         DevBuf* per_anchor4[] = {&e->anchor_len, &e->q_anchor, &e->r_anchor, &e->gap_side, &e->a_score, &e->a_nrun, &e->a_ops, &e->a_flen, &e->a_llen};
         for (DevBuf* d : per_anchor4) if (d->alloc(na * 4)) return 1;
         if (e->anchor_q.alloc(na * 8) || e->anchor_r.alloc(na * 8) || e->anchor_raw_q.alloc(na * 8) || e->anchor_raw_r.alloc(na * 8) || e->anchor_flags.alloc(2 * na) ||
-            e->anchor_first.alloc((n + 1) * 8) || e->end_side.alloc(2 * n * 4) || e->cells.alloc(n * 8) || e->out_off.alloc((n + 1) * 8) || e->matrix.alloc(1024)) return 1;
-        int8_t tmp[1024] = {0};
-        if (e->kind == BA_KIND_BYTES) { const ByteMatrix* bm = (const ByteMatrix*)matrix; tmp[0] = bm->match_score; tmp[1] = bm->mismatch_score; }
-        else memcpy(tmp, matrix, e->kind == BA_KIND_AA ? 27 * 32 : 8 * 16);
-        HIP_TRY(hipMemcpy(e->matrix.p, tmp, 1024, hipMemcpyHostToDevice));
-    } else {
-        if (n > e->cap_n) return fail("reload: %zu chains exceed the batch's capacity of %llu", n, (unsigned long long)e->cap_n);
-        if (na > e->cap_anchors) return fail("reload: %zu anchors exceed the batch's capacity of %llu", na, (unsigned long long)e->cap_anchors);
-        if (S.bytes > e->cap_raw) return fail("reload: %llu sequence bytes exceed the batch's capacity of %llu", (unsigned long long)S.bytes, (unsigned long long)e->cap_raw);
-        if (S.anchor_bytes > e->cap_anchor_bytes) return fail("reload: the anchors (%llu image bytes) exceed the batch's capacity of %llu", (unsigned long long)S.anchor_bytes, (unsigned long long)e->cap_anchor_bytes);
-        if (S.ends.size() && !e->ends) return fail("reload: the set has ends to align, and the batch was created with none");
-        if (S.gaps.size() && !e->gaps) return fail("reload: the set has gaps to align, and the batch was created with none");
-    }
+            e->anchor_first.alloc((n + 1) * 8) || e->end_side.alloc(2 * n * 4) || spliced_create_tail(e, n, matrix)) return 1;
+    } else if (over_count("chains", n, e->cap_n) || over_count("anchors", na, e->cap_anchors) || over_bytes(e, S, "anchors") ||
+               no_inner("ends", S.ends, e->ends) || no_inner("gaps", S.gaps, e->gaps)) return 1;
     e->n = 0; e->ran = false; e->pack_ms = 0;   // (a failure from here on leaves no chains loaded)
-    HIP_TRY(hipMemcpy(e->raw.p, S.lo, S.bytes, hipMemcpyHostToDevice));
+    if (h2d(e->raw, S.lo, S.bytes)) return 1;
     std::vector<uint32_t> end_side(S.end_side), gap_side(S.gap_side);
     {
         // both inner batches live together: the first one plans with half of the free memory (as the ranges of ba_sized_batch_create share it)
@@ -1898,34 +1949,17 @@ static int chain_load(BaChainBatch* e, const ChainSet& S, size_t n, const void* 
             (void)hipMemGetInfo(&free_b, &total_b);
             g_mem_cap = std::max<uint64_t>((uint64_t)((double)free_b * 0.95 * 0.5), 3ull << 30);
         }
-        if (chain_load_pieces(e, e->ends, S.ends, S.lo, matrix, gaps, size, x_drop, e->mode, create, end_side)) return 1;
+        if (spliced_load_pieces(e, e->ends, S.ends, S.lo, "chain", matrix, gaps, size, x_drop, e->mode, create, end_side)) return 1;
         g_mem_cap = ~0ull;
-        if (chain_load_pieces(e, e->gaps, S.gaps, S.lo, matrix, gaps, size, 0, e->mode & ~(uint32_t)BA_X_DROP, create, gap_side)) return 1;
+        if (spliced_load_pieces(e, e->gaps, S.gaps, S.lo, "chain", matrix, gaps, size, 0, e->mode & ~(uint32_t)BA_X_DROP, create, gap_side)) return 1;
     }
-    HIP_TRY(hipMemcpy(e->end_side.p, end_side.data(), 2 * n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->gap_side.p, gap_side.data(), na * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->anchor_first.p, anchor_first, (n + 1) * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->q_anchor.p, q_anchor, na * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->r_anchor.p, r_anchor, na * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->anchor_len.p, anchor_len, na * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->anchor_q.p, S.a_img_q.data(), na * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->anchor_r.p, S.a_img_r.data(), na * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->anchor_raw_q.p, S.a_raw_q.data(), na * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->anchor_raw_r.p, S.a_raw_r.data(), na * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->anchor_flags.p, S.a_flags.data(), 2 * na, hipMemcpyHostToDevice));
+    if (h2d(e->end_side, end_side.data(), 2 * n) || h2d(e->gap_side, gap_side.data(), na) || h2d(e->anchor_first, anchor_first, n + 1) ||
+        h2d(e->q_anchor, q_anchor, na) || h2d(e->r_anchor, r_anchor, na) || h2d(e->anchor_len, anchor_len, na) ||
+        h2d(e->anchor_q, S.a_img_q.data(), na) || h2d(e->anchor_r, S.a_img_r.data(), na) || h2d(e->anchor_raw_q, S.a_raw_q.data(), na) ||
+        h2d(e->anchor_raw_r, S.a_raw_r.data(), na) || h2d(e->anchor_flags, S.a_flags.data(), 2 * na)) return 1;
     HIP_TRY(hipMemset(e->cigar_len.p, 0, n * 4));
-    HIP_TRY(hipMemset(e->err.p, 0xff, 8));
-    HIP_TRY(hipEventRecord(e->ev[0], e->stream));
-    HIP_TRY(ba_launch_pack_images(e->stream, seq_kind(e->kind), e->raw.as<uint8_t>(), e->anchor_raw_q.as<uint64_t>(), e->anchor_raw_r.as<uint64_t>(),
-                                  e->anchor_flags.as<uint8_t>(), e->anchor_q.as<uint64_t>(), e->anchor_len.as<uint32_t>(), e->anchor_r.as<uint64_t>(),
-                                  e->anchor_len.as<uint32_t>(), e->anchor_pool.as<uint8_t>(), 0, (uint32_t)na, e->err.as<unsigned long long>()));
-    HIP_TRY(hipEventRecord(e->ev[1], e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e->ev[0], e->ev[1]));
-    e->pack_ms += ms;
     unsigned long long err = 0;
-    HIP_TRY(hipMemcpy(&err, e->err.p, 8, hipMemcpyDeviceToHost));
+    if (spliced_pack_own(e, e->anchor_raw_q, e->anchor_raw_r, e->anchor_flags, e->anchor_q, e->anchor_r, e->anchor_len, e->anchor_pool, na, &err)) return 1;
     if (err != ~0ull) {
         const uint64_t a = err >> 8;
         const size_t c = (size_t)(std::upper_bound(anchor_first, anchor_first + n + 1, a) - anchor_first) - 1;
@@ -2777,13 +2811,12 @@ BaExtendBatch* ba_extend_batch_create(int kind, const void* matrix, Gaps gaps, S
                                       const uint32_t* q_seed, const uint32_t* r_seed, const uint32_t* seed_len, const uint8_t* strand, uintptr_t n_seeds) {
     ExtSet S;   // every argument is checked before the device is touched
     if (!matrix) { fail("null argument"); return nullptr; }
-    if (ext_check_params(kind, gaps, size, x_drop, mode) || ext_plan(kind, pool, q_off, q_len, r_off, r_len, q_seed, r_seed, seed_len, strand, n_seeds, S)) return nullptr;
+    if (spliced_check_params("extension", "extended", "a side ends where its score drops", kind, gaps, size, x_drop, mode) ||
+        ext_plan(kind, pool, q_off, q_len, r_off, r_len, q_seed, r_seed, seed_len, strand, n_seeds, S)) return nullptr;
     if (ensure_device()) return nullptr;
     std::unique_ptr<BaExtendBatch> e(new BaExtendBatch);
     e->device = g_device; e->kind = kind; e->mode = mode;
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { fail("hipStreamCreate failed"); return nullptr; }
-    for (hipEvent_t& ev : e->ev) if (hipEventCreate(&ev) != hipSuccess) { fail("hipEventCreate failed"); return nullptr; }
-    if (ext_load(e.get(), S, n_seeds, matrix, gaps, size, x_drop, q_seed, r_seed, seed_len, true)) return nullptr;
+    if (e->open(4) || ext_load(e.get(), S, n_seeds, matrix, gaps, size, x_drop, q_seed, r_seed, seed_len, true)) return nullptr;
     return e.release();
 }
 int ba_extend_batch_reload(BaExtendBatch* e, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len,
@@ -2801,54 +2834,17 @@ int ba_extend_batch_run(BaExtendBatch* e, float* kernel_ms) {
     e->ran = false; e->fill_ms = 0; e->splice_ms = 0; e->total_runs = 0;
     if (e->n_sides && batch_run(e->inner.get(), &e->fill_ms)) return 1;   // (re-runs included: the splice reads final results only)
     ba::ExtendParams ep = e->params();
-    HIP_TRY(hipEventRecord(e->ev[0], e->stream));
-    HIP_TRY(ba_launch_extend_results(e->stream, &ep));
-    HIP_TRY(hipEventRecord(e->ev[1], e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipEventElapsedTime(&e->splice_ms, e->ev[0], e->ev[1]));
-    if (e->mode & BA_TRACE) {
-        uint64_t total = 0;
-        HIP_TRY(hipMemcpy(&total, e->out_off.as<uint64_t>() + e->n, 8, hipMemcpyDeviceToHost));
-        if (total > e->runs_cap) {
-            if (e->runs.alloc(total * 4)) return 1;
-            e->runs_cap = total;
-        }
-        ep.runs = e->runs.as<uint32_t>();
-        HIP_TRY(hipEventRecord(e->ev[2], e->stream));
-        HIP_TRY(ba_launch_extend_gather(e->stream, &ep));
-        HIP_TRY(hipEventRecord(e->ev[3], e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, e->ev[2], e->ev[3]));
-        e->splice_ms += ms;
-        e->total_runs = total;
-    }
-    e->ran = true;
+    if (spliced_splice(e, [&] { return ba_launch_extend_results(e->stream, &ep); },   // (the launcher ends with its own offsets kernel)
+                       [&] { ep.runs = e->runs.as<uint32_t>(); return ba_launch_extend_gather(e->stream, &ep); })) return 1;
     e->runs_done++;
     if (kernel_ms) *kernel_ms = e->fill_ms;
     return 0;
 }
 int ba_extend_batch_results(BaExtendBatch* e, int32_t* score, uint32_t* q_start, uint32_t* r_start, uint32_t* q_end, uint32_t* r_end,
                             int32_t* left_score, int32_t* right_score, uint64_t* cells, uint32_t* cigar_len, uint32_t* status) {
-    if (!e) return fail("null batch");
-    if (!e->ran) return fail("ba_extend_batch_run has not been called");
-    HIP_TRY(hipSetDevice(e->device));
-    if (d2h(e->score, score, e->n) || d2h(e->q_start, q_start, e->n) || d2h(e->r_start, r_start, e->n) || d2h(e->q_end, q_end, e->n) ||
-        d2h(e->r_end, r_end, e->n) || d2h(e->left_score, left_score, e->n) || d2h(e->right_score, right_score, e->n) ||
-        d2h(e->cells, cells, e->n) || d2h(e->cigar_len, cigar_len, e->n) || d2h(e->status, status, e->n)) return 1;
-    return 0;
+    return spliced_results(e, "extend_batch", score, q_start, r_start, q_end, r_end, left_score, right_score, cells, cigar_len, status);
 }
-int ba_extend_batch_cigars(BaExtendBatch* e, uint32_t* runs, uint64_t capacity) {
-    if (!e) return fail("null batch");
-    if (!(e->mode & BA_TRACE)) return fail("batch was created without BA_TRACE");
-    if (!e->ran) return fail("ba_extend_batch_run has not been called");
-    if (e->total_runs > capacity) return fail("cigar buffer too small: need %llu entries", (unsigned long long)e->total_runs);
-    if (!e->total_runs) return 0;
-    if (!runs) return fail("null argument");
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipMemcpy(runs, e->runs.p, e->total_runs * 4, hipMemcpyDeviceToHost));
-    return 0;
-}
+int ba_extend_batch_cigars(BaExtendBatch* e, uint32_t* runs, uint64_t capacity) { return spliced_cigars(e, "extend_batch", runs, capacity); }
 int ba_extend_batch_times(BaExtendBatch* e, float* fill_ms, float* pack_ms, float* splice_ms) {
     if (!e) return fail("null batch");
     if (fill_ms) *fill_ms = e->fill_ms;
@@ -2889,11 +2885,8 @@ int ba_extend_batch_text(BaExtendBatch* e, uint32_t what, uint64_t* offsets, cha
     if (!e->t_strand.p && (e->t_raw_q.alloc(e->cap_n * 8) || e->t_raw_r.alloc(e->cap_n * 8) || e->t_ql.alloc(e->cap_n * 4) || e->t_rl.alloc(e->cap_n * 4) ||
                           e->t_strand.alloc(e->cap_n))) return 1;
     if (!e->t_uploaded) {
-        HIP_TRY(hipMemcpy(e->t_raw_q.p, e->h_t_raw_q.data(), (size_t)e->n * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(e->t_raw_r.p, e->h_t_raw_r.data(), (size_t)e->n * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(e->t_ql.p, e->h_t_ql.data(), (size_t)e->n * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(e->t_rl.p, e->h_t_rl.data(), (size_t)e->n * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(e->t_strand.p, e->h_t_strand.data(), (size_t)e->n, hipMemcpyHostToDevice));
+        if (h2d(e->t_raw_q, e->h_t_raw_q.data(), e->n) || h2d(e->t_raw_r, e->h_t_raw_r.data(), e->n) || h2d(e->t_ql, e->h_t_ql.data(), e->n) ||
+            h2d(e->t_rl, e->h_t_rl.data(), e->n) || h2d(e->t_strand, e->h_t_strand.data(), e->n)) return 1;
         e->t_uploaded = true;
     }
     ba::TextParams tp{};
@@ -2911,14 +2904,12 @@ BaChainBatch* ba_chain_batch_create(int kind, const void* matrix, Gaps gaps, Siz
                                     const uint32_t* q_anchor, const uint32_t* r_anchor, const uint32_t* anchor_len, const uint8_t* strand, uintptr_t n_chains) {
     ChainSet S;   // every argument is checked before the device is touched
     if (!matrix) { fail("null argument"); return nullptr; }
-    if (chain_check_params(kind, gaps, size, x_drop, mode) ||
+    if (spliced_check_params("chain", "chained", "the ends of a chain end where their score drops", kind, gaps, size, x_drop, mode) ||
         chain_plan(kind, pool, q_off, q_len, r_off, r_len, anchor_first, q_anchor, r_anchor, anchor_len, strand, n_chains, S)) return nullptr;
     if (ensure_device()) return nullptr;
     std::unique_ptr<BaChainBatch> e(new BaChainBatch);
     e->device = g_device; e->kind = kind; e->mode = mode; e->gap_open = gaps.open; e->gap_extend = gaps.extend;
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { fail("hipStreamCreate failed"); return nullptr; }
-    for (hipEvent_t& ev : e->ev) if (hipEventCreate(&ev) != hipSuccess) { fail("hipEventCreate failed"); return nullptr; }
-    if (chain_load(e.get(), S, n_chains, matrix, gaps, size, x_drop, anchor_first, q_anchor, r_anchor, anchor_len, true)) return nullptr;
+    if (e->open(4) || chain_load(e.get(), S, n_chains, matrix, gaps, size, x_drop, anchor_first, q_anchor, r_anchor, anchor_len, true)) return nullptr;
     return e.release();
 }
 int ba_chain_batch_reload(BaChainBatch* e, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len,
@@ -2940,54 +2931,19 @@ int ba_chain_batch_run(BaChainBatch* e, float* kernel_ms) {
     if (e->n_ends && batch_run(e->ends.get(), &e->ends_ms)) return 1;
     if (e->n_gaps && batch_run(e->gaps.get(), &e->gaps_ms)) return 1;
     ba::ChainParams cp = e->params();
-    HIP_TRY(hipEventRecord(e->ev[0], e->stream));
-    HIP_TRY(ba_launch_chain_results(e->stream, &cp));
-    if (e->mode & BA_TRACE) HIP_TRY(ba_launch_offsets(e->stream, cp.cigar_len, cp.out_off, cp.n));
-    HIP_TRY(hipEventRecord(e->ev[1], e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipEventElapsedTime(&e->splice_ms, e->ev[0], e->ev[1]));
-    if (e->mode & BA_TRACE) {
-        uint64_t total = 0;
-        HIP_TRY(hipMemcpy(&total, e->out_off.as<uint64_t>() + e->n, 8, hipMemcpyDeviceToHost));
-        if (total > e->runs_cap) {
-            if (e->runs.alloc(total * 4)) return 1;
-            e->runs_cap = total;
-        }
-        cp.runs = e->runs.as<uint32_t>();
-        HIP_TRY(hipEventRecord(e->ev[2], e->stream));
-        HIP_TRY(ba_launch_chain_gather(e->stream, &cp));
-        HIP_TRY(hipEventRecord(e->ev[3], e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, e->ev[2], e->ev[3]));
-        e->splice_ms += ms;
-        e->total_runs = total;
-    }
-    e->ran = true;
+    auto results = [&]() -> hipError_t {   // ... and, for the gather, the offsets of the chains' runs
+        const hipError_t r = ba_launch_chain_results(e->stream, &cp);
+        return r != hipSuccess || !(e->mode & BA_TRACE) ? r : ba_launch_offsets(e->stream, cp.cigar_len, cp.out_off, cp.n);
+    };
+    if (spliced_splice(e, results, [&] { cp.runs = e->runs.as<uint32_t>(); return ba_launch_chain_gather(e->stream, &cp); })) return 1;
     if (kernel_ms) *kernel_ms = e->ends_ms + e->gaps_ms;
     return 0;
 }
 int ba_chain_batch_results(BaChainBatch* e, int32_t* score, uint32_t* q_start, uint32_t* r_start, uint32_t* q_end, uint32_t* r_end,
                            int32_t* left_score, int32_t* right_score, uint64_t* cells, uint32_t* cigar_len, uint32_t* status) {
-    if (!e) return fail("null batch");
-    if (!e->ran) return fail("ba_chain_batch_run has not been called");
-    HIP_TRY(hipSetDevice(e->device));
-    if (d2h(e->score, score, e->n) || d2h(e->q_start, q_start, e->n) || d2h(e->r_start, r_start, e->n) || d2h(e->q_end, q_end, e->n) ||
-        d2h(e->r_end, r_end, e->n) || d2h(e->left_score, left_score, e->n) || d2h(e->right_score, right_score, e->n) ||
-        d2h(e->cells, cells, e->n) || d2h(e->cigar_len, cigar_len, e->n) || d2h(e->status, status, e->n)) return 1;
-    return 0;
+    return spliced_results(e, "chain_batch", score, q_start, r_start, q_end, r_end, left_score, right_score, cells, cigar_len, status);
 }
-int ba_chain_batch_cigars(BaChainBatch* e, uint32_t* runs, uint64_t capacity) {
-    if (!e) return fail("null batch");
-    if (!(e->mode & BA_TRACE)) return fail("batch was created without BA_TRACE");
-    if (!e->ran) return fail("ba_chain_batch_run has not been called");
-    if (e->total_runs > capacity) return fail("cigar buffer too small: need %llu entries", (unsigned long long)e->total_runs);
-    if (!e->total_runs) return 0;
-    if (!runs) return fail("null argument");
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipMemcpy(runs, e->runs.p, e->total_runs * 4, hipMemcpyDeviceToHost));
-    return 0;
-}
+int ba_chain_batch_cigars(BaChainBatch* e, uint32_t* runs, uint64_t capacity) { return spliced_cigars(e, "chain_batch", runs, capacity); }
 int ba_chain_batch_times(BaChainBatch* e, float* ends_ms, float* gaps_ms, float* pack_ms, float* splice_ms) {
     if (!e) return fail("null batch");
     if (ends_ms) *ends_ms = e->ends_ms;
@@ -3002,12 +2958,10 @@ void ba_chain_batch_destroy(BaChainBatch* e) { delete e; }
 // From a problem's raw hits to its best chains, in ba_chain_batch_create's layout (ba_chaining.hip; the rule: INTEGRATION.md, "Chaining
 // anchors"). The host checks the arguments, orders the problems longest first and sizes the buffers; the recurrence, the picking and the
 // gather are the device's.
-struct BaChaining {
-    int device = 0;
+struct BaChaining : StreamOwner {
     BaChainingParams P{};
     uint32_t n = 0, ring = 0;
     uint64_t n_anchors = 0, cap_n = 0, cap_anchors = 0, chains_cap = 0, total_chains = 0, total_kept = 0;
-    hipStream_t stream = nullptr; hipEvent_t ev[4] = {};
     DevBuf anchor_first, q_anchor, r_anchor, anchor_len, order, counter, f, pred, gain, mark, pos, cand_len, cand_score, n_chains, n_kept, chain_off, kept_off;
     DevBuf chain_problem, chain_rank, chain_score, out_first, out_q, out_r, out_len, out_src;
     float fill_ms = 0, pick_ms = 0, gather_ms = 0;
@@ -3025,10 +2979,6 @@ struct BaChaining {
         cp.out_first = out_first.as<uint64_t>(); cp.out_q = out_q.as<uint32_t>(); cp.out_r = out_r.as<uint32_t>(); cp.out_len = out_len.as<uint32_t>();
         cp.out_src = out_src.as<uint32_t>();
         return cp;
-    }
-    ~BaChaining() {
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
     }
 };
 static int chaining_check_params(const BaChainingParams& P) {
@@ -3090,8 +3040,7 @@ static int chaining_load(BaChaining* e, const uint64_t* anchor_first, const uint
         if (na > e->cap_anchors) return fail("reload: %llu anchors exceed the batch's capacity of %llu", (unsigned long long)na, (unsigned long long)e->cap_anchors);
     }
     e->n = 0; e->ran = false;   // (a failure from here on leaves no problems loaded)
-    HIP_TRY(hipMemcpy(e->anchor_first.p, anchor_first, (n + 1) * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->order.p, order.data(), n * 4, hipMemcpyHostToDevice));
+    if (h2d(e->anchor_first, anchor_first, n + 1) || h2d(e->order, order.data(), n)) return 1;
     if (na) {
         if (from == hipMemcpyDeviceToDevice) {
             // on the batch's own stream, which its kernels follow, and waited for: a device-to-device hipMemcpy need not have finished when it
@@ -3100,11 +3049,7 @@ static int chaining_load(BaChaining* e, const uint64_t* anchor_first, const uint
             HIP_TRY(hipMemcpyAsync(e->r_anchor.p, r_anchor, na * 4, from, e->stream));
             HIP_TRY(hipMemcpyAsync(e->anchor_len.p, anchor_len, na * 4, from, e->stream));
             HIP_TRY(hipStreamSynchronize(e->stream));
-        } else {
-            HIP_TRY(hipMemcpy(e->q_anchor.p, q_anchor, na * 4, from));
-            HIP_TRY(hipMemcpy(e->r_anchor.p, r_anchor, na * 4, from));
-            HIP_TRY(hipMemcpy(e->anchor_len.p, anchor_len, na * 4, from));
-        }
+        } else if (h2d(e->q_anchor, q_anchor, na) || h2d(e->r_anchor, r_anchor, na) || h2d(e->anchor_len, anchor_len, na)) return 1;
     }
     e->n = (uint32_t)n; e->n_anchors = na;
     return 0;
@@ -3119,9 +3064,7 @@ BaChaining* ba_chaining_create(const BaChainingParams* params, const uint64_t* a
     e->device = g_device; e->P = *params;
     e->ring = 128;
     while (e->ring < params->lookback + 64u) e->ring <<= 1;
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { fail("hipStreamCreate failed"); return nullptr; }
-    for (hipEvent_t& ev : e->ev) if (hipEventCreate(&ev) != hipSuccess) { fail("hipEventCreate failed"); return nullptr; }
-    if (chaining_load(e.get(), anchor_first, q_anchor, r_anchor, anchor_len, n_problems, order, true)) return nullptr;
+    if (e->open(4) || chaining_load(e.get(), anchor_first, q_anchor, r_anchor, anchor_len, n_problems, order, true)) return nullptr;
     return e.release();
 }
 int ba_chaining_reload(BaChaining* e, const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor, const uint32_t* anchor_len,
@@ -3147,8 +3090,7 @@ int ba_chaining_run(BaChaining* e, float* kernel_ms) {
     HIP_TRY(ba_launch_offsets(e->stream, cp.n_kept, e->kept_off.as<uint64_t>(), cp.n));
     HIP_TRY(hipEventRecord(e->ev[2], e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipEventElapsedTime(&e->fill_ms, e->ev[0], e->ev[1]));
-    HIP_TRY(hipEventElapsedTime(&e->pick_ms, e->ev[1], e->ev[2]));
+    if (e->elapsed(0, 1, &e->fill_ms) || e->elapsed(1, 2, &e->pick_ms)) return 1;
     uint64_t chains = 0, kept = 0;
     HIP_TRY(hipMemcpy(&chains, e->chain_off.as<uint64_t>() + e->n, 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(&kept, e->kept_off.as<uint64_t>() + e->n, 8, hipMemcpyDeviceToHost));
@@ -3163,7 +3105,7 @@ int ba_chaining_run(BaChaining* e, float* kernel_ms) {
     HIP_TRY(ba_launch_chaining_gather(e->stream, &cp));
     HIP_TRY(hipEventRecord(e->ev[3], e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipEventElapsedTime(&e->gather_ms, e->ev[2], e->ev[3]));
+    if (e->elapsed(2, 3, &e->gather_ms)) return 1;
     e->total_chains = chains; e->total_kept = kept;
     e->ran = true;
     if (kernel_ms) *kernel_ms = e->fill_ms + e->pick_ms + e->gather_ms;
@@ -3220,12 +3162,10 @@ struct IndexData {   // a reference index on the device (ba_ref_index_*): shared
     uint64_t ref_len = 0, n_entries = 0;
     DevBuf key, table;   // n_entries keys code << 32 | pos, ascending; (1 << prefix_bits) + 1 bounds
 };
-struct BaSeeding {
-    int device = 0;
+struct BaSeeding : StreamOwner {
     BaSeedingParams P{};
     uint32_t n = 0;
     uint64_t cap_n = 0, cap_raw = 0, seeds_cap = 0, q_seeds_cap = 0, hits_cap = 0, n_q_seeds = 0, n_seeds = 0, n_hits = 0;
-    hipStream_t stream = nullptr; hipEvent_t ev[9] = {};
     DevBuf raw, seq_off, seq_len, seq_rc, seq_order, sort_order, match_order, counter, seed_cnt, seed_first, seed_pos, seed_code, q_key, hit_cnt, hit_first,
            q_hit, r_hit, hit_len;
     std::shared_ptr<const IndexData> index;   // an indexed seeder (ba_seeding_create_indexed): every problem's reference is the index's
@@ -3253,10 +3193,6 @@ struct BaSeeding {
         sp.hit_cnt = hit_cnt.as<uint32_t>(); sp.hit_first = hit_first.as<uint64_t>();
         sp.q_hit = q_hit.as<uint32_t>(); sp.r_hit = r_hit.as<uint32_t>(); sp.hit_len = hit_len.as<uint32_t>();
         return sp;
-    }
-    ~BaSeeding() {
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
     }
 };
 static int seeding_check_params(const BaSeedingParams& P) {
@@ -3311,13 +3247,9 @@ static int seeding_load(BaSeeding* e, const SeedingSet& S, size_t n, bool create
         if (S.bytes > e->cap_raw) return fail("reload: %llu sequence bytes exceed the batch's capacity of %llu", (unsigned long long)S.bytes, (unsigned long long)e->cap_raw);
     }
     e->n = 0; e->ran = false;   // (a failure from here on leaves no problems loaded)
-    if (S.bytes) HIP_TRY(hipMemcpy(e->raw.p, S.lo, S.bytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->seq_off.p, S.off.data(), 2 * n * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->seq_len.p, S.len.data(), 2 * n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->seq_rc.p, S.rc.data(), 2 * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->seq_order.p, S.seq_order.data(), 2 * n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->sort_order.p, S.sort_order.data(), n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->match_order.p, S.match_order.data(), n * 4, hipMemcpyHostToDevice));
+    if ((S.bytes && h2d(e->raw, S.lo, S.bytes)) || h2d(e->seq_off, S.off.data(), 2 * n) || h2d(e->seq_len, S.len.data(), 2 * n) ||
+        h2d(e->seq_rc, S.rc.data(), 2 * n) || h2d(e->seq_order, S.seq_order.data(), 2 * n) || h2d(e->sort_order, S.sort_order.data(), n) ||
+        h2d(e->match_order, S.match_order.data(), n)) return 1;
     e->n = (uint32_t)n;
     return 0;
 }
@@ -3329,9 +3261,7 @@ BaSeeding* ba_seeding_create(const BaSeedingParams* params, const uint8_t* pool,
     if (ensure_device()) return nullptr;
     std::unique_ptr<BaSeeding> e(new BaSeeding);
     e->device = g_device; e->P = *params;
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { fail("hipStreamCreate failed"); return nullptr; }
-    for (hipEvent_t& ev : e->ev) if (hipEventCreate(&ev) != hipSuccess) { fail("hipEventCreate failed"); return nullptr; }
-    if (seeding_load(e.get(), S, n_problems, true)) return nullptr;
+    if (e->open(9) || seeding_load(e.get(), S, n_problems, true)) return nullptr;
     return e.release();
 }
 int ba_seeding_reload(BaSeeding* e, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len,
@@ -3411,13 +3341,11 @@ int ba_seeding_run(BaSeeding* e, float* kernel_ms) {
     HIP_TRY(hipEventRecord(e->ev[8], e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     float a = 0, b = 0;
-    HIP_TRY(hipEventElapsedTime(&a, e->ev[0], e->ev[1]));
-    HIP_TRY(hipEventElapsedTime(&b, e->ev[2], e->ev[3]));
+    if (e->elapsed(0, 1, &a) || e->elapsed(2, 3, &b)) return 1;
     e->sketch_ms = a + b;
-    HIP_TRY(hipEventElapsedTime(&e->sort_ms, e->ev[3], e->ev[4]));
-    if (e->index) { HIP_TRY(hipEventElapsedTime(&a, e->ev[7], e->ev[8])); e->sort_ms += a; }   // the sort of the hits
-    HIP_TRY(hipEventElapsedTime(&a, e->ev[4], e->ev[5]));
-    HIP_TRY(hipEventElapsedTime(&b, e->ev[6], e->ev[7]));
+    if (e->elapsed(3, 4, &e->sort_ms)) return 1;
+    if (e->index) { if (e->elapsed(7, 8, &a)) return 1; e->sort_ms += a; }   // the sort of the hits
+    if (e->elapsed(4, 5, &a) || e->elapsed(6, 7, &b)) return 1;
     e->match_ms = a + b;
     e->n_q_seeds = q_seeds; e->n_seeds = seeds; e->n_hits = hits;
     e->ran = true;
@@ -3490,10 +3418,8 @@ BaChaining* ba_chaining_create_seeded(const BaChainingParams* params, BaSeeding*
     e->device = s->device; e->P = *params;
     e->ring = 128;
     while (e->ring < params->lookback + 64u) e->ring <<= 1;
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { fail("hipStreamCreate failed"); return nullptr; }
-    for (hipEvent_t& ev : e->ev) if (hipEventCreate(&ev) != hipSuccess) { fail("hipEventCreate failed"); return nullptr; }
-    if (chaining_load(e.get(), first.data(), s->q_hit.as<uint32_t>(), s->r_hit.as<uint32_t>(), s->hit_len.as<uint32_t>(), n, order, true,
-                      hipMemcpyDeviceToDevice)) return nullptr;
+    if (e->open(4) || chaining_load(e.get(), first.data(), s->q_hit.as<uint32_t>(), s->r_hit.as<uint32_t>(), s->hit_len.as<uint32_t>(), n, order, true,
+                                    hipMemcpyDeviceToDevice)) return nullptr;
     return e.release();
 }
 
@@ -3504,26 +3430,19 @@ struct BaRefIndex {
     std::shared_ptr<IndexData> d;
     float sketch_ms = 0, sort_ms = 0, table_ms = 0;
 };
-struct IndexBuildTools {   // the stream and the events of one build
-    hipStream_t stream = nullptr; hipEvent_t ev[6] = {};
-    ~IndexBuildTools() {
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
 static int index_build(BaRefIndex* x, const uint8_t* ref) {
     IndexData& D = *x->d;
     const uint32_t len = (uint32_t)D.ref_len, k = D.k, w = D.w;
     const uint32_t nk = len >= k ? len - k + 1u : 0u, nw = nk == 0u ? 0u : nk > w ? nk - w + 1u : 1u;
-    IndexBuildTools T;
+    StreamOwner T;   // the stream and the six events of this build (made below with the build's own error texts, destroyed with T)
     DevBuf raw, counter, span_cnt, span_first, unsorted, temp, longest;
     ba::IndexParams ip{};
     ip.k = k; ip.w = w; ip.len = len; ip.n_windows = nw; ip.n_spans = (nw + ba::INDEX_SPAN - 1u) / ba::INDEX_SPAN; ip.prefix_bits = D.prefix_bits;
     HIP_TRY(hipStreamCreateWithFlags(&T.stream, hipStreamNonBlocking));
-    for (hipEvent_t& ev : T.ev) HIP_TRY(hipEventCreate(&ev));
+    for (int i = 0; i < 6; i++) HIP_TRY(hipEventCreate(&T.ev[i]));
     if (raw.alloc(len) || counter.alloc(4) || span_cnt.alloc((size_t)ip.n_spans * 4) || span_first.alloc(((size_t)ip.n_spans + 1) * 8) || longest.alloc(4) ||
         D.table.alloc(((size_t)(1u << ip.prefix_bits) + 1) * 4)) return 1;
-    if (len) HIP_TRY(hipMemcpy(raw.p, ref, len, hipMemcpyHostToDevice));
+    if (len && h2d(raw, ref, len)) return 1;
     ip.ref = raw.as<uint8_t>(); ip.counter = counter.as<uint32_t>(); ip.span_cnt = span_cnt.as<uint32_t>(); ip.span_first = span_first.as<uint64_t>();
     ip.table = D.table.as<uint32_t>(); ip.longest_run = longest.as<uint32_t>();
     // the sketch: count, scan, emit
@@ -3556,12 +3475,9 @@ static int index_build(BaRefIndex* x, const uint8_t* ref) {
     HIP_TRY(hipMemcpy(&D.longest_run, longest.p, 4, hipMemcpyDeviceToHost));
     D.n_entries = total;
     float a = 0, b = 0;
-    HIP_TRY(hipEventElapsedTime(&a, T.ev[0], T.ev[1]));
-    HIP_TRY(hipEventElapsedTime(&b, T.ev[2], T.ev[3]));
+    if (T.elapsed(0, 1, &a) || T.elapsed(2, 3, &b)) return 1;
     x->sketch_ms = a + b;
-    HIP_TRY(hipEventElapsedTime(&x->sort_ms, T.ev[3], T.ev[4]));
-    HIP_TRY(hipEventElapsedTime(&x->table_ms, T.ev[4], T.ev[5]));
-    return 0;
+    return T.elapsed(3, 4, &x->sort_ms) || T.elapsed(4, 5, &x->table_ms);
 }
 BaRefIndex* ba_ref_index_create(uint32_t k, uint32_t w, const uint8_t* ref, uint64_t ref_len) {
     if (seeding_check_params(BaSeedingParams{k, w, 1})) return nullptr;   // every argument is checked before the device is touched
@@ -3616,9 +3532,7 @@ BaSeeding* ba_seeding_create_indexed(BaRefIndex* x, uint32_t max_occ, uint32_t m
     std::unique_ptr<BaSeeding> e(new BaSeeding);
     e->device = x->d->device; e->P = BaSeedingParams{x->d->k, x->d->w, max_occ};
     e->index = x->d; e->max_ref_occ = max_ref_occ;
-    if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess) { fail("hipStreamCreate failed"); return nullptr; }
-    for (hipEvent_t& ev : e->ev) if (hipEventCreate(&ev) != hipSuccess) { fail("hipEventCreate failed"); return nullptr; }
-    if (seeding_load(e.get(), S, n_problems, true)) return nullptr;
+    if (e->open(9) || seeding_load(e.get(), S, n_problems, true)) return nullptr;
     return e.release();
 }
 int ba_seeding_reload_indexed(BaSeeding* e, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint8_t* strand, uintptr_t n_problems) {
