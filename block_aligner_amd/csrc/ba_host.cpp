@@ -1544,6 +1544,15 @@ struct PieceSet {   // the pairs of one inner batch (host addresses into the cal
 struct SplicedSet {   // a planned set: the extent of its sequences in the caller's pool, the size of the units' own images (seeds, anchors)
     const uint8_t* lo = nullptr; const uint8_t* hi = nullptr;
     uint64_t bytes = 0, own_bytes = 0;
+    // per unit, the whole query and reference: source offsets in the upload, lengths, strand (ba_*_batch_text renders from them)
+    std::vector<uint64_t> t_raw_q, t_raw_r;
+    std::vector<uint32_t> t_ql, t_rl;
+    std::vector<uint8_t> t_strand;
+    void text_sources(const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len, const uint8_t* strand, size_t n) {
+        t_raw_q.assign(q_off, q_off + n); t_raw_r.assign(r_off, r_off + n); t_ql.assign(q_len, q_len + n); t_rl.assign(r_len, r_len + n);   // (made relative to lo by close)
+        t_strand.assign(n, 0);
+        if (strand) t_strand.assign(strand, strand + n);
+    }
     // unit u (`noun`: "seed", "chain") on strand st: the strand checked, its sequences q and r added to the extent
     int add(int kind, const char* noun, size_t u, uint8_t st, const uint8_t* q, uint64_t Q, const uint8_t* r, uint64_t R) {
         if (st > 1) return fail("%s %zu: strand must be 0 or 1", noun, u);
@@ -1560,7 +1569,10 @@ struct SplicedSet {   // a planned set: the extent of its sequences in the calle
     }
     uint64_t close(const uint8_t* pool) {   // after the last unit -> the offset of `lo` in the caller's pool
         bytes = (uint64_t)(hi - lo);
-        return (uint64_t)(lo - pool);
+        const uint64_t base = (uint64_t)(lo - pool);
+        for (uint64_t& x : t_raw_q) x -= base;
+        for (uint64_t& x : t_raw_r) x -= base;
+        return base;
     }
 };
 struct Spliced : StreamOwner {
@@ -1570,6 +1582,21 @@ struct Spliced : StreamOwner {
     DevBuf score, left_score, right_score, q_start, r_start, q_end, r_end, cells, status, cigar_len, out_off, runs;
     float pack_ms = 0, splice_ms = 0;
     bool ran = false;
+    DevBuf stats;   // per-unit statistics (ba_*_batch_stats), allocated on the first call
+    float stats_ms = 0;   // ... the kernels of the last call (the inner batches' k_stats and the combine)
+    // alignment strings (ba_*_batch_text): the sequences' source offsets, lengths and strands of the loaded set (host copies, uploaded by
+    // the first text call after a load) and their device buffers, allocated on the first call
+    std::vector<uint64_t> h_t_raw_q, h_t_raw_r;
+    std::vector<uint32_t> h_t_ql, h_t_rl;
+    std::vector<uint8_t> h_t_strand;
+    bool t_uploaded = false;
+    DevBuf t_raw_q, t_raw_r, t_ql, t_rl, t_strand;
+    TextState text;
+    uint64_t runs_done = 0;
+    void text_loaded(const SplicedSet& S) {   // a set has been loaded: its sequences are what the next text call renders from
+        h_t_raw_q = S.t_raw_q; h_t_raw_r = S.t_raw_r; h_t_ql = S.t_ql; h_t_rl = S.t_rl; h_t_strand = S.t_strand;
+        t_uploaded = false;
+    }
 };
 }  // namespace
 // ba_*_batch_create's own arguments. what: "extension" / "chain"; the two sentences that differ are passed in.
@@ -1709,10 +1736,6 @@ struct ExtSet : SplicedSet {   // a seed set cut into sides
     std::vector<uint32_t> side;                        // 2 per seed (left, right): index of the side, or NO_PIECE
     std::vector<uint64_t> s_raw_q, s_raw_r, s_img_q, s_img_r;   // the seeds' own images: source offsets in the upload, offsets in the seed pool
     std::vector<uint8_t> s_flags;                      // 2 per seed
-    // per seed, the whole query and reference: source offsets in the upload, lengths, strand (ba_extend_batch_text renders from them)
-    std::vector<uint64_t> t_raw_q, t_raw_r;
-    std::vector<uint32_t> t_ql, t_rl;
-    std::vector<uint8_t> t_strand;
 };
 // Check a seed set (the mode and the matrix kind are checked already) and cut it into sides.
 static int ext_plan(int kind, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len,
@@ -1721,9 +1744,7 @@ static int ext_plan(int kind, const uint8_t* pool, const uint64_t* q_off, const 
     if (n == 0 || n > (1u << 28)) return fail("an extension batch must hold between 1 and 2^28 seeds");   // (k_pack_images: two workgroups per side)
     S = ExtSet();
     S.side.resize(2 * n); S.s_raw_q.resize(n); S.s_raw_r.resize(n); S.s_img_q.resize(n); S.s_img_r.resize(n); S.s_flags.resize(2 * n);
-    S.t_raw_q.resize(n); S.t_raw_r.resize(n); S.t_ql.assign(q_len, q_len + n); S.t_rl.assign(r_len, r_len + n);
-    S.t_strand.assign(n, 0);
-    if (strand) S.t_strand.assign(strand, strand + n);
+    S.text_sources(q_off, q_len, r_off, r_len, strand, n);
     for (size_t p = 0; p < n; p++) {
         const uint64_t Q = q_len[p], R = r_len[p], s = q_seed[p], t = r_seed[p], L = seed_len[p];
         if (L == 0) return fail("seed %zu: seed_len must be at least 1", p);
@@ -1744,10 +1765,9 @@ static int ext_plan(int kind, const uint8_t* pool, const uint64_t* q_off, const 
         S.s_raw_q[p] = (uint64_t)((st ? q + (Q - s - L) : q + s) - pool); S.s_raw_r[p] = (uint64_t)(r + t - pool);   // (made relative to lo below)
         S.s_flags[2 * p] = st ? (ba::IMG_REVERSE | ba::IMG_COMPLEMENT) : 0; S.s_flags[2 * p + 1] = 0;
         S.s_img_q[p] = S.own_image(L); S.s_img_r[p] = S.own_image(L);
-        S.t_raw_q[p] = q_off[p]; S.t_raw_r[p] = r_off[p];   // (made relative to lo below)
     }
     const uint64_t base = S.close(pool);
-    for (size_t p = 0; p < n; p++) { S.s_raw_q[p] -= base; S.s_raw_r[p] -= base; S.t_raw_q[p] -= base; S.t_raw_r[p] -= base; }
+    for (size_t p = 0; p < n; p++) { S.s_raw_q[p] -= base; S.s_raw_r[p] -= base; }
     if (S.sides.size() > 0x7fffffffu) return fail("too many sides");
     return 0;
 }
@@ -1755,16 +1775,6 @@ struct BaExtendBatch : Spliced {
     std::unique_ptr<BaBatch> inner;   // the sides of the loaded set; null if the batch was created with none (nothing to fill)
     uint32_t n_sides = 0;
     DevBuf seed_pool, seed_q, seed_r, seed_raw_q, seed_raw_r, seed_flags, seed_len, q_seed, r_seed, side, join;
-    DevBuf stats;   // per-seed statistics (ba_extend_batch_stats), allocated on the first call
-    // alignment strings (ba_extend_batch_text): the sequences' source offsets, lengths and strands of the loaded set (host copies, uploaded by
-    // the first text call after a load) and their device buffers, allocated on the first call
-    std::vector<uint64_t> h_t_raw_q, h_t_raw_r;
-    std::vector<uint32_t> h_t_ql, h_t_rl;
-    std::vector<uint8_t> h_t_strand;
-    bool t_uploaded = false;
-    DevBuf t_raw_q, t_raw_r, t_ql, t_rl, t_strand;
-    TextState text;
-    uint64_t runs_done = 0;
     float fill_ms = 0;
     // optimal paths (ba_extend_batch_exact_paths): the requested seeds, their run counts, offsets and joined runs on the device, and the
     // request they belong to with its records, kept for the second call of the two-call pattern (a load drops it)
@@ -1813,8 +1823,7 @@ static int ext_load(BaExtendBatch* e, const ExtSet& S, size_t n, const void* mat
     if (spliced_pack_own(e, e->seed_raw_q, e->seed_raw_r, e->seed_flags, e->seed_q, e->seed_r, e->seed_len, e->seed_pool, n, &err)) return 1;
     if (err != ~0ull) return fail("seed %llu: byte 0x%02x is outside the matrix alphabet", err >> 8, (unsigned)(err & 0xff));
     e->n = (uint32_t)n; e->n_sides = (uint32_t)S.sides.size();
-    e->h_t_raw_q = S.t_raw_q; e->h_t_raw_r = S.t_raw_r; e->h_t_ql = S.t_ql; e->h_t_rl = S.t_rl; e->h_t_strand = S.t_strand;
-    e->t_uploaded = false;
+    e->text_loaded(S);
     return 0;
 }
 
@@ -1847,6 +1856,7 @@ static int chain_plan(int kind, const uint8_t* pool, const uint64_t* q_off, cons
     if (na > (1u << 28)) return fail("a chain batch must hold at most 2^28 anchors");   // (k_pack_images: two workgroups per anchor)
     S = ChainSet();
     S.n_anchors = na;
+    S.text_sources(q_off, q_len, r_off, r_len, strand, n);
     S.end_side.resize(2 * n); S.gap_side.assign(na, NO_PIECE);
     S.a_raw_q.resize(na); S.a_raw_r.resize(na); S.a_img_q.resize(na); S.a_img_r.resize(na); S.a_flags.resize(2 * na);
     for (size_t c = 0; c < n; c++) {
@@ -1966,6 +1976,7 @@ static int chain_load(BaChainBatch* e, const ChainSet& S, size_t n, const void* 
         return fail("chain %zu, anchor %llu: byte 0x%02x is outside the matrix alphabet", c, (unsigned long long)(a - anchor_first[c]), (unsigned)(err & 0xff));
     }
     e->n = (uint32_t)n; e->n_anchors = (uint32_t)na; e->n_ends = (uint32_t)S.ends.size(); e->n_gaps = (uint32_t)S.gaps.size();
+    e->text_loaded(S);
     return 0;
 }
 
@@ -2458,6 +2469,31 @@ static int batch_text_device(BaBatch* b, uint32_t what, uint64_t* offsets, char*
     return text_kernels(b->text, b->device, b->stream, b->runs_done, tp, b->cap_n, &b->h_order, offsets, text, capacity);
 }
 
+// A spliced batch (ba_extend_batch_text, ba_chain_batch_text; run_call: the name of its run call): the spliced runs (caller's order,
+// out_off / runs) from the unit's start; the oriented query and the reference read from the caller's bytes on the device (raw), by
+// k_pack_images' rule. (The pieces' texts cannot be joined: the equal stretches merge across the seed or the anchors.)
+static int spliced_text(Spliced* e, const char* run_call, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) {
+    if (!e) return fail("null batch");
+    if (!offsets) return fail("null argument: offsets");
+    if (text_check(e->kind, e->mode, what)) return 1;
+    if (!e->ran) return fail("text: the batch has not finished a run (%s)", run_call);
+    HIP_TRY(hipSetDevice(e->device));
+    if (!e->t_strand.p && (e->t_raw_q.alloc(e->cap_n * 8) || e->t_raw_r.alloc(e->cap_n * 8) || e->t_ql.alloc(e->cap_n * 4) || e->t_rl.alloc(e->cap_n * 4) ||
+                          e->t_strand.alloc(e->cap_n))) return 1;
+    if (!e->t_uploaded) {
+        if (h2d(e->t_raw_q, e->h_t_raw_q.data(), e->n) || h2d(e->t_raw_r, e->h_t_raw_r.data(), e->n) || h2d(e->t_ql, e->h_t_ql.data(), e->n) ||
+            h2d(e->t_rl, e->h_t_rl.data(), e->n) || h2d(e->t_strand, e->h_t_strand.data(), e->n)) return 1;
+        e->t_uploaded = true;
+    }
+    ba::TextParams tp{};
+    tp.n = e->n; tp.kind = seq_kind(e->kind); tp.what = what;
+    tp.seq = e->raw.as<uint8_t>(); tp.skip = 0; tp.strand = e->t_strand.as<uint8_t>();
+    tp.q_off = e->t_raw_q.as<uint64_t>(); tp.q_len = e->t_ql.as<uint32_t>(); tp.r_off = e->t_raw_r.as<uint64_t>(); tp.r_len = e->t_rl.as<uint32_t>();
+    tp.q_end = e->q_end.as<uint32_t>(); tp.r_end = e->r_end.as<uint32_t>(); tp.status = e->status.as<uint32_t>();
+    tp.nrun = e->cigar_len.as<uint32_t>(); tp.run_end = e->out_off.as<uint64_t>(); tp.ops = e->runs.as<uint32_t>();
+    return text_kernels(e->text, e->device, e->stream, e->runs_done, tp, e->cap_n, nullptr, offsets, text, capacity);
+}
+
 // ------------------------------------------------------------------ C ABI, Part 2
 extern "C" {
 
@@ -2866,8 +2902,6 @@ int ba_extend_batch_stats(BaExtendBatch* e, BaAlignStats* out) {
     HIP_TRY(hipMemcpy(out, e->stats.p, (size_t)e->n * sizeof(ba::AlignStats), hipMemcpyDeviceToHost));
     return 0;
 }
-// The spliced runs (caller's order, out_off / runs) from the extension's start; the oriented query and the reference read from the caller's
-// bytes on the device (raw), by k_pack_images' rule. (The sides' texts cannot be joined: the equal stretches merge across the seed.)
 int ba_extend_batch_exact(BaExtendBatch* e, int32_t x_drop, const uint32_t* which, uintptr_t n_which, BaExact* left, BaExact* right, int32_t* score) {
     return extend_exact(e, x_drop, which, n_which, left, right, score);
 }
@@ -2877,25 +2911,7 @@ int ba_extend_batch_exact_paths(BaExtendBatch* e, int32_t x_drop, const uint32_t
     return extend_exact_paths(e, x_drop, which, n_which, out, left, right, run_off, runs, runs_cap);
 }
 int ba_extend_batch_text(BaExtendBatch* e, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) {
-    if (!e) return fail("null batch");
-    if (!offsets) return fail("null argument: offsets");
-    if (text_check(e->kind, e->mode, what)) return 1;
-    if (!e->ran) return fail("text: the batch has not finished a run (ba_extend_batch_run)");
-    HIP_TRY(hipSetDevice(e->device));
-    if (!e->t_strand.p && (e->t_raw_q.alloc(e->cap_n * 8) || e->t_raw_r.alloc(e->cap_n * 8) || e->t_ql.alloc(e->cap_n * 4) || e->t_rl.alloc(e->cap_n * 4) ||
-                          e->t_strand.alloc(e->cap_n))) return 1;
-    if (!e->t_uploaded) {
-        if (h2d(e->t_raw_q, e->h_t_raw_q.data(), e->n) || h2d(e->t_raw_r, e->h_t_raw_r.data(), e->n) || h2d(e->t_ql, e->h_t_ql.data(), e->n) ||
-            h2d(e->t_rl, e->h_t_rl.data(), e->n) || h2d(e->t_strand, e->h_t_strand.data(), e->n)) return 1;
-        e->t_uploaded = true;
-    }
-    ba::TextParams tp{};
-    tp.n = e->n; tp.kind = seq_kind(e->kind); tp.what = what;
-    tp.seq = e->raw.as<uint8_t>(); tp.skip = 0; tp.strand = e->t_strand.as<uint8_t>();
-    tp.q_off = e->t_raw_q.as<uint64_t>(); tp.q_len = e->t_ql.as<uint32_t>(); tp.r_off = e->t_raw_r.as<uint64_t>(); tp.r_len = e->t_rl.as<uint32_t>();
-    tp.q_end = e->q_end.as<uint32_t>(); tp.r_end = e->r_end.as<uint32_t>(); tp.status = e->status.as<uint32_t>();
-    tp.nrun = e->cigar_len.as<uint32_t>(); tp.run_end = e->out_off.as<uint64_t>(); tp.ops = e->runs.as<uint32_t>();
-    return text_kernels(e->text, e->device, e->stream, e->runs_done, tp, e->cap_n, nullptr, offsets, text, capacity);
+    return spliced_text(e, "ba_extend_batch_run", what, offsets, text, capacity);
 }
 void ba_extend_batch_destroy(BaExtendBatch* e) { delete e; }
 
@@ -2936,6 +2952,7 @@ int ba_chain_batch_run(BaChainBatch* e, float* kernel_ms) {
         return r != hipSuccess || !(e->mode & BA_TRACE) ? r : ba_launch_offsets(e->stream, cp.cigar_len, cp.out_off, cp.n);
     };
     if (spliced_splice(e, results, [&] { cp.runs = e->runs.as<uint32_t>(); return ba_launch_chain_gather(e->stream, &cp); })) return 1;
+    e->runs_done++;
     if (kernel_ms) *kernel_ms = e->ends_ms + e->gaps_ms;
     return 0;
 }
@@ -2950,6 +2967,38 @@ int ba_chain_batch_times(BaChainBatch* e, float* ends_ms, float* gaps_ms, float*
     if (gaps_ms) *gaps_ms = e->gaps_ms;
     if (pack_ms) *pack_ms = e->pack_ms;
     if (splice_ms) *splice_ms = e->splice_ms;
+    return 0;
+}
+int ba_chain_batch_stats(BaChainBatch* e, BaAlignStats* out) {
+    if (!e) return fail("null batch");
+    if (!out) return fail("null argument");
+    if (!(e->mode & BA_TRACE)) return fail("stats: the batch was created without BA_TRACE (the statistics are computed from the CIGAR runs)");
+    if (!e->ran) return fail("stats: the batch has not finished a run (ba_chain_batch_run)");
+    HIP_TRY(hipSetDevice(e->device));
+    e->stats_ms = 0;
+    // the pieces' records, in the inner batches' device order
+    if (e->n_ends && batch_stats_device(e->ends.get(), false)) return 1;
+    if (e->n_gaps && batch_stats_device(e->gaps.get(), false)) return 1;
+    if (!e->stats.p && e->stats.alloc((size_t)e->cap_n * sizeof(ba::AlignStats))) return 1;
+    const ba::ChainParams cp = e->params();
+    HIP_TRY(hipEventRecord(e->ev[0], e->stream));
+    HIP_TRY(ba_launch_stats_chain(e->stream, &cp, e->n_ends ? e->ends->stats.as<ba::AlignStats>() : nullptr,
+                                  e->n_gaps ? e->gaps->stats.as<ba::AlignStats>() : nullptr, e->stats.as<ba::AlignStats>()));
+    HIP_TRY(hipEventRecord(e->ev[1], e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    float ms = 0;
+    if (e->elapsed(0, 1, &ms)) return 1;
+    e->stats_ms = ms + (e->n_ends ? e->ends->stats_ms : 0) + (e->n_gaps ? e->gaps->stats_ms : 0);
+    HIP_TRY(hipMemcpy(out, e->stats.p, (size_t)e->n * sizeof(ba::AlignStats), hipMemcpyDeviceToHost));
+    return 0;
+}
+int ba_chain_batch_text(BaChainBatch* e, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity) {
+    return spliced_text(e, "ba_chain_batch_run", what, offsets, text, capacity);
+}
+int ba_chain_batch_report_ms(BaChainBatch* e, float* stats_ms, float* text_ms) {
+    if (!e) return fail("null batch");
+    if (stats_ms) *stats_ms = e->stats_ms;
+    if (text_ms) *text_ms = e->text.ms;
     return 0;
 }
 void ba_chain_batch_destroy(BaChainBatch* e) { delete e; }

@@ -91,6 +91,7 @@ hipError_t ba_launch_index_sort(hipStream_t s, const uint64_t* in, uint64_t* out
 // ba_stats.hip
 hipError_t ba_launch_stats(hipStream_t s, const ba::StatsParams* sp);
 hipError_t ba_launch_stats_extend(hipStream_t s, const ba::ExtendParams* ep, const ba::AlignStats* side, ba::AlignStats* out);
+hipError_t ba_launch_stats_chain(hipStream_t s, const ba::ChainParams* cp, const ba::AlignStats* ends, const ba::AlignStats* gaps, ba::AlignStats* out);
 // ba_exact.hip, BA_EXACT_UNIT 0 (ba_launch_exact, ba_launch_exact_seed) and 1 (ba_launch_exact_trace, ba_launch_exact_runs)
 hipError_t ba_launch_exact(hipStream_t s, const ba::ExactParams* xp, uint32_t wgs);
 hipError_t ba_launch_exact_trace(hipStream_t s, const ba::ExactParams* xp, uint32_t waves);

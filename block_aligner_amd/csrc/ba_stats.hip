@@ -150,6 +150,101 @@ __global__ void __launch_bounds__(256) k_stats_extend(const ba::ExtendParams ep,
     out[s] = o;
 }
 
+namespace {
+__device__ __forceinline__ void add_record(const ba::AlignStats& x, uint32_t& cols, uint32_t& mat, uint32_t& mis, uint32_t& pos, uint32_t& ins, uint32_t& del,
+                                           uint32_t& opens, uint32_t& lins, uint32_t& ldel, int& score) {
+    cols += x.columns; mat += x.matches; mis += x.mismatches; pos += x.positives; ins += x.ins; del += x.del; opens += x.gap_opens;
+    lins = max(lins, x.longest_ins); ldel = max(ldel, x.longest_del); score += x.path_score;
+}
+}  // namespace
+
+// Chain batches: one wave per chain at a time, chains in the caller's order, grid-stride. The chain's record = the sum over its 2 K + 1
+// elements (ba_chain.h): the ends' and the aligned gaps' records (the inner batches', by device position) as they are -- counts do not depend
+// on the reversal of the left end --, every anchor's ungapped columns scored from anchor_pool, every gap with one empty slice one I or D run of
+// its length d (one gap open, open + (d - 1) * extend). Counts add, the longest gaps take the maximum, the start is the first anchor's less
+// what the left end consumed. Exact: every gap element lies between two anchors and an anchor always has match-type runs, so a gap run of one
+// element never merges with a gap run of another (the splice's joins only lengthen runs whose counts add anyway: INTEGRATION.md, "Anchor
+// chains"; tests/chain_ref.py asserts gap_merges == 0) -- the number and the lengths of the spliced CIGAR's gap runs are the elements' own.
+// The lanes stride over the anchors 64 at a time, each with the gap behind its anchor; the chunk's columns are spread over the lanes as
+// k_stats spreads a long M run (a prefix sum of anchor_len, column t of the chunk to lane t % 64), so that a long anchor is read by the whole
+// wave. A chain whose status has a failure bit gets an all-zero record.
+__global__ void __launch_bounds__(64 * STATS_WAVES) k_stats_chain(const ba::ChainParams cp, const ba::AlignStats* __restrict__ ends,
+                                                                  const ba::AlignStats* __restrict__ gaps, ba::AlignStats* __restrict__ out) {
+    __shared__ int8_t tab[1024];
+    // per wave, the chunk's anchors: columns of the anchors up to and including anchor k; its images' first bytes in anchor_pool, less the
+    // columns before it (column t of the chunk, in anchor k, is qadj[k] + t against radj[k] + t)
+    __shared__ uint32_t incl_s[STATS_WAVES][64];
+    __shared__ uint64_t qadj_s[STATS_WAVES][64], radj_s[STATS_WAVES][64];
+    for (uint32_t k = threadIdx.x; k < 1024u; k += blockDim.x) tab[k] = cp.matrix[k];   // (the matrix buffer of a spliced batch is 1024 bytes)
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    uint32_t* incl = incl_s[w];
+    uint64_t* qadj = qadj_s[w];
+    uint64_t* radj = radj_s[w];
+    for (uint32_t c = blockIdx.x * STATS_WAVES + w; c < cp.n; c += gridDim.x * STATS_WAVES) {
+        const uint64_t a0 = cp.anchor_first[c];
+        const uint32_t K = (uint32_t)(cp.anchor_first[c + 1] - a0);
+        const uint32_t dl = cp.end_side[2 * c], dr = cp.end_side[2 * c + 1];
+        const bool failed = (cp.status[c] & ba::STATS_FAILED) != 0;
+        uint32_t cols = 0, mat = 0, mis = 0, pos = 0, ins = 0, del = 0, opens = 0, lins = 0, ldel = 0;
+        int score = 0;
+        if (!failed) {
+            if (lane == 0 && dl != ba::CHAIN_NO_PIECE) add_record(ends[dl], cols, mat, mis, pos, ins, del, opens, lins, ldel, score);
+            if (lane == 1 && dr != ba::CHAIN_NO_PIECE) add_record(ends[dr], cols, mat, mis, pos, ins, del, opens, lins, ldel, score);
+        }
+        for (uint32_t base = 0; base < K && !failed; base += 64u) {
+            const uint32_t k = base + lane;
+            const bool in = k < K;
+            const uint64_t a = a0 + k;
+            const uint32_t L = in ? cp.anchor_len[a] : 0u;
+            if (in && k + 1 < K) {   // the gap behind the anchor
+                const uint32_t d = cp.gap_side[a];
+                if (d != ba::CHAIN_NO_PIECE) add_record(gaps[d], cols, mat, mis, pos, ins, del, opens, lins, ldel, score);
+                else {
+                    const uint32_t dq = cp.q_anchor[a + 1] - cp.q_anchor[a] - L, dd = cp.r_anchor[a + 1] - cp.r_anchor[a] - L;   // (one of them is 0)
+                    const uint32_t len = dq | dd;
+                    if (len) {
+                        cols += len; opens++;
+                        score += cp.gap_open + (int)(len - 1u) * cp.gap_extend;
+                        if (dq) { ins += len; lins = max(lins, len); } else { del += len; ldel = max(ldel, len); }
+                    }
+                }
+            }
+            // the anchors of a chain are disjoint on the query: the columns of a chunk are fewer than 2^32
+            const uint32_t sm = wave_incl_sum(L, lane), tm = (uint32_t)__shfl((int)sm, 63, 64);
+            incl[lane] = sm;
+            qadj[lane] = in ? cp.anchor_q[a] + 1 - (sm - L) : 0u;
+            radj[lane] = in ? cp.anchor_r[a] + 1 - (sm - L) : 0u;
+            wave_lds_fence();
+            {
+                uint32_t j = 0, jend = incl[0];
+                uint64_t qa = qadj[0], ra = radj[0];
+                for (uint32_t t = lane; t < tm; t += 64u) {
+                    if (t >= jend) {
+                        do j++; while (incl[j] <= t);   // (t < tm = incl[63]: ends inside the chunk)
+                        jend = incl[j]; qa = qadj[j]; ra = radj[j];
+                    }
+                    const uint32_t x = cp.anchor_pool[qa + t], y = cp.anchor_pool[ra + t];
+                    const int s = cell_score(cp.kind, tab, x, y);
+                    mat += x == y; mis += x != y; pos += s > 0; score += s;
+                }
+            }
+            cols += L;
+            wave_lds_fence();   // (the next chunk overwrites the table)
+        }
+        ba::AlignStats o{};
+        o.columns = wave_sum(cols); o.matches = wave_sum(mat); o.mismatches = wave_sum(mis); o.positives = wave_sum(pos);
+        o.ins = wave_sum(ins); o.del = wave_sum(del); o.gap_opens = wave_sum(opens);
+        o.longest_ins = wave_max(lins); o.longest_del = wave_max(ldel);
+        o.path_score = (int32_t)wave_sum((uint32_t)score);
+        if (!failed) {
+            o.q_start = cp.q_anchor[a0] - (dl != ba::CHAIN_NO_PIECE ? cp.ends.qidx[dl] : 0u);
+            o.r_start = cp.r_anchor[a0] - (dl != ba::CHAIN_NO_PIECE ? cp.ends.ridx[dl] : 0u);
+        }
+        if (lane == 0) out[c] = o;
+    }
+}
+
 extern "C" hipError_t ba_launch_stats(hipStream_t s, const ba::StatsParams* sp) {
     if (!sp->n) return hipSuccess;
     const uint32_t wgs = (sp->n + STATS_WAVES - 1) / STATS_WAVES;
@@ -159,5 +254,13 @@ extern "C" hipError_t ba_launch_stats(hipStream_t s, const ba::StatsParams* sp) 
 extern "C" hipError_t ba_launch_stats_extend(hipStream_t s, const ba::ExtendParams* ep, const ba::AlignStats* side, ba::AlignStats* out) {
     if (!ep->n) return hipSuccess;
     k_stats_extend<<<dim3((ep->n + 255) / 256), dim3(256), 0, s>>>(*ep, side, out);
+    return hipGetLastError();
+}
+// ends / gaps: the inner batches' records in their device order; null for a set without such pieces
+extern "C" hipError_t ba_launch_stats_chain(hipStream_t s, const ba::ChainParams* cp, const ba::AlignStats* ends, const ba::AlignStats* gaps,
+                                            ba::AlignStats* out) {
+    if (!cp->n) return hipSuccess;
+    const uint32_t wgs = (cp->n + STATS_WAVES - 1) / STATS_WAVES;
+    k_stats_chain<<<dim3(wgs < 4096u ? wgs : 4096u), dim3(64 * STATS_WAVES), 0, s>>>(*cp, ends, gaps, out);
     return hipGetLastError();
 }

@@ -55,6 +55,7 @@ if C.sizeof(AlignStatsC) != 48 or STATS_DTYPE.itemsize != 48:
 
 
 TEXT_CIGAR, TEXT_MD, TEXT_CS, TEXT_SOFT_CLIP = 0, 1, 2, 1 << 8   # ba_*_text: the format, and the CIGAR's soft-clip flag
+STATS_FAILED_BITS = 1 | 2 | 4 | 8 | 16 | 32 | 128   # status bits (overflow, lost, watchdog) after which a record is all zeros and a text empty
 
 
 class ExactC(C.Structure):
@@ -250,6 +251,9 @@ def lib() -> C.CDLL:
             getattr(L, f"{f}_stats").argtypes = [vp, vp]
             getattr(L, f"{f}_text").argtypes = [vp, C.c_uint32, vp, vp, C.c_uint64]
             getattr(L, f"{f}_destroy").argtypes = [vp]
+        L.ba_chain_batch_stats.argtypes = [vp, vp]
+        L.ba_chain_batch_text.argtypes = [vp, C.c_uint32, vp, vp, C.c_uint64]
+        L.ba_chain_batch_report_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         for f in ("ba_batch", "ba_sized_batch", "ba_multibatch"):
             getattr(L, f"{f}_exact").argtypes = [vp, u32, i32, vp, sz, vp]
             getattr(L, f"{f}_exact_cigars").argtypes = [vp, u32, i32, vp, sz, vp, vp, vp, C.c_uint64]
@@ -1008,7 +1012,8 @@ class ChainBatchAligner(_Batch):
     ExtendBatchAligner. mode must hold X_DROP; TRACE and CIGAR_EQ are optional. Arguments are checked before the device is touched.
 
     run() fills the ends, then the gaps, then splices, and returns both fills' time. results() has ExtendBatchAligner's keys; cigars() gives
-    chain c's runs. Statistics, strings and exact scores of chain batches are not offered ("Anchor chains")."""
+    chain c's runs; report() gives the chains' statistics and CIGAR / MD / cs strings (ChainReport). The exact scores of chain batches are
+    not offered (INTEGRATION.md, "Anchor chains")."""
 
     _C = "ba_chain_batch"
     RESULTS = ExtendBatchAligner.RESULTS
@@ -1051,9 +1056,75 @@ class ChainBatchAligner(_Batch):
 
     def _not_offered(self, *args, **kwargs):
         raise RuntimeError("chain batches offer run, results, cigars, reload and times only: statistics, strings, exact scores and the "
-                           "accuracy report of chain batches are out of scope (INTEGRATION.md, \"Anchor chains\")")
+                           "accuracy report of chain batches are out of scope (INTEGRATION.md, \"Anchor chains\"); the statistics and the "
+                           "strings of the chains are report()'s")
 
     stats = text = text_list = exact = exact_cigars = exact_paths = accuracy = _not_offered
+
+    def report(self) -> "ChainReport":
+        """TRACE batches after a run: the chains' statistics and strings (ba_chain_batch_stats, ba_chain_batch_text) -> ChainReport."""
+        return ChainReport(self)
+
+
+class ChainReport:
+    """What describes the alignments of a ChainBatchAligner ("Statistics and strings of a chain"): a view of the batch that
+    holds no device memory of its own; every call reads the batch as it is then (after a reload and a run: the new set). Chain c's record
+    and text are those of its spliced runs -- cigars() -- over the oriented query and the reference, ending at (q_end, r_end); reference
+    positions are in the frame the batch was created with (the window after chain_batch_args(margin=...): add last_window_shift)."""
+
+    def __init__(self, batch: ChainBatchAligner):
+        self._b = batch
+
+    @property
+    def n(self):
+        return self._b.n
+
+    def _call(self, name, *args):
+        self._b._call(name, *args)
+
+    def stats(self):
+        """-> the dict of BatchAligner.stats(), one entry per chain: q_start / r_start are results()'s, path_score == score."""
+        return _Batch.stats(self)
+
+    def text(self, what=TEXT_CIGAR, soft_clip=False):
+        """-> (buf, offsets) as BatchAligner.text(); soft_clip clips over the oriented query's full length."""
+        return _Batch.text(self, what, soft_clip)
+
+    def text_list(self, what=TEXT_CIGAR, soft_clip=False):
+        return _text_list(*self.text(what, soft_clip))
+
+    def ms(self):
+        """(stats_ms, text_ms): HIP-event times of the kernels of the last stats() / text() call."""
+        s, t = C.c_float(), C.c_float()
+        self._call("report_ms", C.byref(s), C.byref(t))
+        return s.value, t.value
+
+
+def paf_columns(results, stats, q_len, strand=None, r_shift=None) -> dict:
+    """The numeric PAF columns of a chain batch's alignments, in NumPy (no device): results = ChainBatchAligner.results(), stats =
+    report().stats(), q_len = the reads' lengths, strand = the batch's strand array (None: all plus), r_shift = what to add to reference
+    positions (AnchorChainer.last_window_shift after chain_batch_args(margin=...); None: nothing). -> dict of arrays, one entry per chain:
+    q_start / q_end in the read's own frame (on the minus strand the oriented frame mirrored: q_len - q_end, q_len - q_start), strand (b"+" /
+    b"-"), t_start / t_end in the reference's frame, n_match (matches), aln_len (columns), nm (edit distance), as_ (score). A chain whose
+    status has a failure bit (an all-zero record, empty text) gets zeros (and its strand)."""
+    n = len(results["score"])
+    q_len = np.asarray(q_len, dtype=np.int64)
+    minus = np.zeros(n, bool) if strand is None else np.asarray(strand).astype(bool)
+    shift = np.zeros(n, np.int64) if r_shift is None else np.asarray(r_shift, dtype=np.int64)
+    if not (len(q_len) == len(minus) == len(shift) == len(stats["columns"]) == n):
+        raise ValueError("results, stats, q_len, strand and r_shift must have one entry per chain")
+    qs, qe = np.asarray(stats["q_start"], dtype=np.int64), np.asarray(results["q_end"], dtype=np.int64)
+    ok = (np.asarray(results["status"]) & STATS_FAILED_BITS) == 0
+    z = np.zeros(n, np.int64)
+    return dict(q_start=np.where(ok, np.where(minus, q_len - qe, qs), z), q_end=np.where(ok, np.where(minus, q_len - qs, qe), z),
+                strand=np.where(minus, b"-", b"+").astype("S1"),
+                t_start=np.where(ok, np.asarray(stats["r_start"], dtype=np.int64) + shift, z),
+                t_end=np.where(ok, np.asarray(results["r_end"], dtype=np.int64) + shift, z),
+                n_match=np.where(ok, np.asarray(stats["matches"], dtype=np.int64), z),
+                aln_len=np.where(ok, np.asarray(stats["columns"], dtype=np.int64), z),
+                nm=np.where(ok, np.asarray(stats["mismatches"], dtype=np.int64) + np.asarray(stats["ins"], dtype=np.int64) +
+                            np.asarray(stats["del"], dtype=np.int64), z),
+                as_=np.where(ok, np.asarray(results["score"], dtype=np.int64), z))
 
 
 class AnchorChainer:

@@ -370,6 +370,8 @@ int ba_chain_batch_results(BaChainBatch* batch, int32_t* score, uint32_t* q_star
 int ba_chain_batch_cigars(BaChainBatch* batch, uint32_t* runs, uint64_t capacity);
 /* Device times in ms: the last run's two fills and its splice; the image packers of the last create / reload. Any pointer may be NULL. */
 int ba_chain_batch_times(BaChainBatch* batch, float* ends_ms, float* gaps_ms, float* pack_ms, float* splice_ms);
+/* (The statistics and the CIGAR / MD / cs strings of the chains: ba_chain_batch_stats, ba_chain_batch_text and ba_chain_batch_report_ms,
+ * declared with the other ba_*_stats and ba_*_text calls below.) */
 void ba_chain_batch_destroy(BaChainBatch* batch);
 
 /* ---- colinear anchor chaining on the device: from the raw hits of a problem (one read against one reference on one strand: a future row of a
@@ -582,6 +584,20 @@ int ba_multibatch_stats(BaMultiBatch* batch, struct BaAlignStats* out);
  * columns + the right side's record (counts add, the longest gaps are the larger; exact, since the joins only merge match-type runs);
  * q_start / r_start are the extension's. A seed whose status has a failure bit gets a record of zeros. */
 int ba_extend_batch_stats(BaExtendBatch* batch, struct BaAlignStats* out);
+/* One record per chain (n_chains records, the caller's order): the record of the chain's spliced runs -- those of ba_chain_batch_cigars --
+ * over the oriented query (its reverse complement where strand[c] = 1) and the reference, ending at the chain's (q_end, r_end). Computed as
+ * a sum over the chain's pieces: both ends' and every aligned gap's record, every anchor's ungapped columns, every gap with one empty slice
+ * as one I or D run (counts add, the longest gaps are the larger). Exact: a gap run of one piece never merges with a gap run of another,
+ * since an anchor lies between them. Hence q_start / r_start equal those of ba_chain_batch_results, path_score == score for every chain
+ * with status 0, and matches + mismatches + ins + del == columns. A chain whose status has a failure bit gets a record of zeros.
+ * Reference positions are in the frame of the r_off / r_len the batch was created with: the candidate window when the chains came through
+ * ba_chain_windows (Python: chain_batch_args(margin=...)), whose `lo` (last_window_shift) brings them back to the reference's frame.
+ * Refused as ba_extend_batch_stats is: a null batch, a null argument, a batch created without BA_TRACE, a batch that has not finished a
+ * run (ba_chain_batch_run) since it was created or reloaded. */
+int ba_chain_batch_stats(BaChainBatch* batch, struct BaAlignStats* out);
+/* HIP-event times (ms) of the kernels the last ba_chain_batch_stats (the pieces' statistics and the combine) and the last
+ * ba_chain_batch_text call on this batch ran; either pointer may be NULL. */
+int ba_chain_batch_report_ms(BaChainBatch* batch, float* stats_ms, float* text_ms);
 /* HIP-event time (ms) of the last ba_batch_stats kernel on this batch */
 int ba_batch_stats_ms(BaBatch* batch, float* ms);
 
@@ -835,6 +851,11 @@ int ba_batch_text(BaBatch* batch, uint32_t what, uint64_t* offsets, char* text, 
 int ba_sized_batch_text(BaSizedBatch* batch, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity);
 int ba_multibatch_text(BaMultiBatch* batch, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity);
 int ba_extend_batch_text(BaExtendBatch* batch, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity);
+/* Chain c's text: its spliced runs (ba_chain_batch_cigars) from (q_start, r_start) over the oriented query and the reference, as for an
+ * extension batch; BA_TEXT_SOFT_CLIP clips over the oriented query's full length. n_chains + 1 offsets, the two-call pattern above. A chain
+ * whose status has a failure bit gets empty text. Reference letters and positions are those of the r_off / r_len the batch was created with
+ * (the candidate window after ba_chain_windows). Refused as ba_extend_batch_text is. */
+int ba_chain_batch_text(BaChainBatch* batch, uint32_t what, uint64_t* offsets, char* text, uint64_t capacity);
 /* HIP-event time (ms) of the text kernels the last ba_batch_text call on this batch ran (the sizes, the rendering, or both) */
 int ba_batch_text_ms(BaBatch* batch, float* ms);
 
