@@ -13,6 +13,7 @@
 #include <cstring>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -3471,6 +3472,241 @@ BaChaining* ba_chaining_create_seeded(const BaChainingParams* params, BaSeeding*
                                     hipMemcpyDeviceToDevice)) return nullptr;
     return e.release();
 }
+
+// ------------------------------------------------------------------ read-level selection (ba_select_*)
+// From candidates in any order to the marks of a mapper's records (ba_select.hip; the rule: INTEGRATION.md, "Selecting a read's
+// alignments"). The host checks the arguments and orders the reads by their number of candidates; the grouping, the marking and the emit
+// are the device's. A selection is small work over many candidates, so what a call costs besides its kernels is kept to a few driver
+// calls: every array of a selector lies in ONE device allocation, the host's inputs go up in one copy and the outputs come back in one.
+static_assert(sizeof(BaSelectParams) == 24, "struct BaSelectParams is six 4-byte fields");
+// Byte offsets in that allocation for a capacity of n candidates and r reads, every array 16-byte aligned: the inputs that always come from
+// the host (0 .. in_b), the scores and spans (in_b .. in_end: from the host, or device to device from a chain batch), the scratch, and the
+// outputs (out .. out_end). kept has room for every candidate, so no output grows between the passes.
+extern "C++" {   // (member templates)
+struct SelectLayout {
+    size_t read, q_len, support, order, strand, exclude, in_b, score, q_start, q_end, in_end;
+    size_t status, a, b, counts, counter, first, keys;   // counts: per read the count, then (r entries on) the scatter's cursor
+    size_t out, kept_first, parent, rank, sub_score, n_kept, kept, cls, mapq, out_end;
+    explicit SelectLayout(size_t n = 0, size_t r = 0) {
+        size_t at = 0;
+        auto take = [&](size_t bytes) { const size_t o = at; at = (at + bytes + 15) & ~(size_t)15; return o; };
+        read = take(n * 4); q_len = take(n * 4); support = take(n * 4); order = take(r * 4); strand = take(n); exclude = take(n);
+        in_b = score = take(n * 4); q_start = take(n * 4); q_end = take(n * 4);
+        in_end = status = take(n * 4); a = take(n * 4); b = take(n * 4); counts = take(2 * r * 4); counter = take(4); first = take((r + 1) * 8); keys = take(n * 8);
+        out = kept_first = take((r + 1) * 8); parent = take(n * 4); rank = take(n * 4); sub_score = take(n * 4); n_kept = take(r * 4); kept = take(n * 4);
+        cls = take(n); mapq = take(n);
+        out_end = at;
+    }
+};
+// Creating a stream takes milliseconds and a selection a fraction of one, so a selector that is destroyed leaves its stream -- idle: every
+// call waits for what it launched -- to the next one on the same device. At most SELECT_STREAMS of them are kept.
+constexpr size_t SELECT_STREAMS = 4;
+static std::mutex g_select_mutex;
+static std::vector<std::pair<int, hipStream_t>> g_select_streams;
+struct BaSelect : StreamOwner {
+    int open_select(size_t n_events) {   // StreamOwner::open, with a stream that a destroyed selector left if there is one
+        {
+            std::lock_guard<std::mutex> lock(g_select_mutex);
+            for (size_t i = 0; i < g_select_streams.size(); i++)
+                if (g_select_streams[i].first == device) { stream = g_select_streams[i].second; g_select_streams.erase(g_select_streams.begin() + i); break; }
+        }
+        if (!stream) return open(n_events);
+        for (size_t i = 0; i < n_events; i++) if (hipEventCreate(&ev[i]) != hipSuccess) return fail("hipEventCreate failed");
+        return 0;
+    }
+    ~BaSelect() {
+        std::lock_guard<std::mutex> lock(g_select_mutex);
+        if (stream && g_select_streams.size() < SELECT_STREAMS) { g_select_streams.emplace_back(device, stream); stream = nullptr; }
+    }
+    BaSelectParams P{};
+    uint32_t n = 0, n_reads = 0;
+    uint64_t cap_n = 0, cap_reads = 0, total_kept = 0;
+    bool has_strand = false, has_support = false, has_exclude = false, chained = false, ran = false;
+    SelectLayout L;
+    DevBuf arena;
+    std::vector<uint8_t> stage, mirror;   // the inputs as they go up (0 .. in_end), the outputs as they came back (out .. out_end)
+    float group_ms = 0, mark_ms = 0, emit_ms = 0;
+    template <class T> T* dev(size_t off) const { return (T*)(arena.as<uint8_t>() + off); }
+    template <class T> T* up(size_t off) { return (T*)(stage.data() + off); }
+    template <class T> const T* got(size_t off) const { return (const T*)(mirror.data() + (off - L.out)); }
+    ba::SelectParams params() const {
+        ba::SelectParams sp{};
+        sp.n = n; sp.n_reads = n_reads; sp.mask_permille = P.mask_permille; sp.sec_permille = P.sec_permille; sp.max_secondary = P.max_secondary;
+        sp.mapq_max = P.mapq_max; sp.full_support = P.full_support; sp.min_score = P.min_score; sp.failed = ba::STATS_FAILED;
+        sp.read = dev<uint32_t>(L.read); sp.score = dev<int32_t>(L.score); sp.q_start = dev<uint32_t>(L.q_start); sp.q_end = dev<uint32_t>(L.q_end);
+        sp.q_len = dev<uint32_t>(L.q_len); sp.strand = has_strand ? dev<uint8_t>(L.strand) : nullptr; sp.support = has_support ? dev<uint32_t>(L.support) : nullptr;
+        sp.exclude = has_exclude ? dev<uint8_t>(L.exclude) : nullptr; sp.status = chained ? dev<uint32_t>(L.status) : nullptr;
+        sp.order = dev<uint32_t>(L.order); sp.counter = dev<uint32_t>(L.counter);
+        sp.a = dev<uint32_t>(L.a); sp.b = dev<uint32_t>(L.b); sp.count = dev<uint32_t>(L.counts); sp.cursor = dev<uint32_t>(L.counts) + cap_reads;
+        sp.first = dev<uint64_t>(L.first); sp.keys = dev<uint64_t>(L.keys);
+        sp.cls = dev<uint8_t>(L.cls); sp.mapq = dev<uint8_t>(L.mapq); sp.parent = dev<uint32_t>(L.parent); sp.rank = dev<uint32_t>(L.rank);
+        sp.sub_score = dev<int32_t>(L.sub_score); sp.n_kept = dev<uint32_t>(L.n_kept); sp.kept_first = dev<uint64_t>(L.kept_first); sp.kept = dev<uint32_t>(L.kept);
+        return sp;
+    }
+};
+template <class T> static void select_get(const BaSelect* e, size_t off, T* dst, size_t count) {   // from the host's image of the outputs
+    if (dst && count) memcpy(dst, e->got<T>(off), count * sizeof(T));
+}
+}  // extern "C++"
+static int select_check_params(const BaSelectParams& P) {
+    if (P.mask_permille < 1 || P.mask_permille > 1000) return fail("select: mask_permille must be between 1 and 1000 (it is %u)", P.mask_permille);
+    if (P.sec_permille > 1000) return fail("select: sec_permille must be between 0 and 1000 (it is %u)", P.sec_permille);
+    if (P.mapq_max > 255) return fail("select: mapq_max must be between 0 and 255 (it is %u)", P.mapq_max);
+    if (P.full_support < 1 || P.full_support > 65535) return fail("select: full_support must be between 1 and 65535 (it is %u)", P.full_support);
+    if (P.min_score < 1) return fail("select: min_score must be at least 1 (it is %d)", P.min_score);
+    return 0;
+}
+// Check a set of candidates (q_start, q_end and q_len null: a chain batch's, which are its own results) -> the reads ordered by their number
+// of candidates, the one with the most first.
+static int select_plan(const uint32_t* read, const uint32_t* q_start, const uint32_t* q_end, const uint32_t* q_len, const uint8_t* strand, size_t n,
+                       size_t n_reads, std::vector<uint32_t>& order) {
+    if (n == 0 || n > (1u << 28)) return fail("a selection must hold between 1 and 2^28 candidates");
+    if (n_reads == 0 || n_reads > (1u << 28)) return fail("a selection must hold between 1 and 2^28 reads");
+    std::vector<uint32_t> per(n_reads, 0);
+    for (size_t c = 0; c < n; c++) {
+        if (read[c] >= n_reads) return fail("candidate %zu: read %u is not below n_reads (%zu)", c, read[c], n_reads);
+        if (q_start && q_start[c] > q_end[c]) return fail("candidate %zu: q_start %u lies behind q_end %u", c, q_start[c], q_end[c]);
+        if (q_start && q_end[c] > q_len[c]) return fail("candidate %zu: q_end %u lies behind the end of the read (q_len %u)", c, q_end[c], q_len[c]);
+        if (strand && strand[c] > 1) return fail("candidate %zu: strand must be 0 or 1", c);
+        if (++per[read[c]] > ba::SELECT_MAX_PER_READ)
+            return fail("read %u holds more than %u candidates (candidate %zu is one too many)", read[c], ba::SELECT_MAX_PER_READ, c);
+    }
+    order.resize(n_reads);
+    for (size_t r = 0; r < n_reads; r++) order[r] = (uint32_t)r;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return per[x] > per[y]; });
+    return 0;
+}
+static int select_alloc(BaSelect* e, size_t n, size_t n_reads) {
+    e->cap_n = n; e->cap_reads = n_reads;
+    e->L = SelectLayout(n, n_reads);
+    e->stage.assign(e->L.in_end, 0); e->mirror.assign(e->L.out_end - e->L.out, 0);
+    return e->arena.alloc(e->L.out_end);
+}
+// the inputs that always come from the host, into the staging image (strand, support and exclude may be null)
+static void select_stage(BaSelect* e, const uint32_t* read, const uint32_t* q_len, const uint8_t* strand, const uint32_t* support, const uint8_t* exclude,
+                         size_t n, const std::vector<uint32_t>& order) {
+    memcpy(e->up<uint32_t>(e->L.read), read, n * 4); memcpy(e->up<uint32_t>(e->L.q_len), q_len, n * 4);
+    memcpy(e->up<uint32_t>(e->L.order), order.data(), order.size() * 4);
+    if (strand) memcpy(e->up<uint8_t>(e->L.strand), strand, n);
+    if (support) memcpy(e->up<uint32_t>(e->L.support), support, n * 4);
+    if (exclude) memcpy(e->up<uint8_t>(e->L.exclude), exclude, n);
+    e->has_strand = strand != nullptr; e->has_support = support != nullptr; e->has_exclude = exclude != nullptr;
+}
+static int select_load(BaSelect* e, const uint32_t* read, const int32_t* score, const uint32_t* q_start, const uint32_t* q_end, const uint32_t* q_len,
+                       const uint8_t* strand, const uint32_t* support, const uint8_t* exclude, size_t n, size_t n_reads, const std::vector<uint32_t>& order,
+                       bool create) {
+    if (create) { if (select_alloc(e, n, n_reads)) return 1; }
+    else if (over_count("candidates", n, e->cap_n) || over_count("reads", n_reads, e->cap_reads)) return 1;
+    e->n = 0; e->ran = false;   // (a failure from here on leaves no candidates loaded)
+    select_stage(e, read, q_len, strand, support, exclude, n, order);
+    memcpy(e->up<int32_t>(e->L.score), score, n * 4); memcpy(e->up<uint32_t>(e->L.q_start), q_start, n * 4); memcpy(e->up<uint32_t>(e->L.q_end), q_end, n * 4);
+    HIP_TRY(hipMemcpy(e->arena.p, e->stage.data(), e->L.in_end, hipMemcpyHostToDevice));
+    e->n = (uint32_t)n; e->n_reads = (uint32_t)n_reads;
+    return 0;
+}
+BaSelect* ba_select_create(const BaSelectParams* params, const uint32_t* read, const int32_t* score, const uint32_t* q_start, const uint32_t* q_end,
+                           const uint32_t* q_len, const uint8_t* strand, const uint32_t* support, const uint8_t* exclude, uintptr_t n, uintptr_t n_reads) {
+    std::vector<uint32_t> order;   // every argument is checked before the device is touched
+    if (!params || !read || !score || !q_start || !q_end || !q_len) { fail("null argument"); return nullptr; }
+    if (select_check_params(*params) || select_plan(read, q_start, q_end, q_len, strand, n, n_reads, order)) return nullptr;
+    if (ensure_device()) return nullptr;
+    std::unique_ptr<BaSelect> e(new BaSelect);
+    e->device = g_device; e->P = *params;
+    if (e->open_select(4) || select_load(e.get(), read, score, q_start, q_end, q_len, strand, support, exclude, n, n_reads, order, true)) return nullptr;
+    return e.release();
+}
+// The hand-off: a selector over the results of a chain batch that has run, where they lie. Nothing of the batch's results passes through the
+// host; q_len and strand are the host copies the batch keeps for its strings.
+BaSelect* ba_select_create_chained(const BaSelectParams* params, BaChainBatch* b, const uint32_t* read_of_chain, const uint32_t* support, uintptr_t n_reads) {
+    std::vector<uint32_t> order;
+    if (!params) { fail("null argument"); return nullptr; }
+    if (!b) { fail("null batch"); return nullptr; }
+    if (!read_of_chain) { fail("null argument"); return nullptr; }
+    if (select_check_params(*params)) return nullptr;
+    if (!b->ran) { fail("select: the batch has not finished a run (ba_chain_batch_run)"); return nullptr; }
+    const size_t n = b->n;
+    if (select_plan(read_of_chain, nullptr, nullptr, nullptr, nullptr, n, n_reads, order)) return nullptr;
+    if (hipSetDevice(b->device) != hipSuccess) { fail("hipSetDevice failed"); return nullptr; }
+    std::unique_ptr<BaSelect> e(new BaSelect);
+    e->device = b->device; e->P = *params; e->chained = true;
+    if (e->open_select(4) || select_alloc(e.get(), n, n_reads)) return nullptr;
+    // on the selector's own stream, which its kernels follow, and waited for: the batch may be reloaded or destroyed as soon as this call is over
+    const std::pair<size_t, const DevBuf*> copies[] = {{e->L.score, &b->score}, {e->L.q_start, &b->q_start}, {e->L.q_end, &b->q_end}, {e->L.status, &b->status}};
+    for (const auto& cp : copies)
+        if (hipMemcpyAsync(e->dev<uint8_t>(cp.first), cp.second->p, n * 4, hipMemcpyDeviceToDevice, e->stream) != hipSuccess) { fail("hipMemcpyAsync failed"); return nullptr; }
+    select_stage(e.get(), read_of_chain, b->h_t_ql.data(), b->h_t_strand.data(), support, nullptr, n, order);
+    if (hipMemcpyAsync(e->arena.p, e->stage.data(), e->L.in_b, hipMemcpyHostToDevice, e->stream) != hipSuccess) { fail("hipMemcpyAsync failed"); return nullptr; }
+    if (hipStreamSynchronize(e->stream) != hipSuccess) { fail("hipStreamSynchronize failed"); return nullptr; }
+    e->n = (uint32_t)n; e->n_reads = (uint32_t)n_reads;
+    return e.release();
+}
+int ba_select_reload(BaSelect* e, const uint32_t* read, const int32_t* score, const uint32_t* q_start, const uint32_t* q_end, const uint32_t* q_len,
+                     const uint8_t* strand, const uint32_t* support, const uint8_t* exclude, uintptr_t n, uintptr_t n_reads) {
+    if (!e) return fail("null batch");
+    if (e->chained) return fail("reload: the selector reads a chain batch's results (ba_select_create_chained makes another one from a batch that has run)");
+    if (!read || !score || !q_start || !q_end || !q_len) return fail("null argument");
+    std::vector<uint32_t> order;
+    if (select_plan(read, q_start, q_end, q_len, strand, n, n_reads, order)) return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    return select_load(e, read, score, q_start, q_end, q_len, strand, support, exclude, n, n_reads, order, false);
+}
+int ba_select_run(BaSelect* e, float* kernels_ms) {
+    if (!e) return fail("null batch");
+    if (!e->n) return fail("no candidates loaded (the last reload failed)");
+    HIP_TRY(hipSetDevice(e->device));
+    e->ran = false; e->group_ms = e->mark_ms = e->emit_ms = 0; e->total_kept = 0;
+    const ba::SelectParams sp = e->params();
+    HIP_TRY(hipMemsetAsync(sp.count, 0, 2 * (size_t)e->cap_reads * 4, e->stream));
+    HIP_TRY(hipMemsetAsync(sp.counter, 0, 4, e->stream));
+    HIP_TRY(hipEventRecord(e->ev[0], e->stream));
+    HIP_TRY(ba_launch_select_group(e->stream, &sp, 0));
+    HIP_TRY(ba_launch_offsets(e->stream, sp.count, e->dev<uint64_t>(e->L.first), sp.n_reads));
+    HIP_TRY(ba_launch_select_group(e->stream, &sp, 1));
+    HIP_TRY(hipEventRecord(e->ev[1], e->stream));
+    HIP_TRY(ba_launch_select_mark(e->stream, &sp));
+    HIP_TRY(ba_launch_offsets(e->stream, sp.n_kept, e->dev<uint64_t>(e->L.kept_first), sp.n_reads));
+    HIP_TRY(hipEventRecord(e->ev[2], e->stream));
+    HIP_TRY(ba_launch_select_emit(e->stream, &sp));   // (kept has room for every candidate: the host need not read the total in between)
+    HIP_TRY(hipEventRecord(e->ev[3], e->stream));
+    // every output in one copy, on the stream behind the kernels; the getters read the host's image
+    HIP_TRY(hipMemcpyAsync(e->mirror.data(), e->dev<uint8_t>(e->L.out), e->L.out_end - e->L.out, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (e->elapsed(0, 1, &e->group_ms) || e->elapsed(1, 2, &e->mark_ms) || e->elapsed(2, 3, &e->emit_ms)) return 1;
+    const uint64_t kept = e->got<uint64_t>(e->L.kept_first)[e->n_reads];
+    if (kept > e->n) return fail("select: the device kept %llu candidates, more than the set holds", (unsigned long long)kept);
+    e->total_kept = kept;
+    e->ran = true;
+    if (kernels_ms) *kernels_ms = e->group_ms + e->mark_ms + e->emit_ms;
+    return 0;
+}
+int ba_select_counts(BaSelect* e, uint64_t* n_kept, uint32_t* kept_per_read) {
+    if (!e) return fail("null batch");
+    if (!e->ran) return fail("ba_select_run has not been called");
+    if (n_kept) *n_kept = e->total_kept;
+    select_get(e, e->L.n_kept, kept_per_read, e->n_reads);
+    return 0;
+}
+int ba_select_results(BaSelect* e, uint8_t* cls, uint8_t* mapq, uint32_t* parent, uint32_t* rank, int32_t* sub_score) {
+    if (!e) return fail("null batch");
+    if (!e->ran) return fail("ba_select_run has not been called");
+    select_get(e, e->L.cls, cls, e->n); select_get(e, e->L.mapq, mapq, e->n); select_get(e, e->L.parent, parent, e->n);
+    select_get(e, e->L.rank, rank, e->n); select_get(e, e->L.sub_score, sub_score, e->n);
+    return 0;
+}
+int ba_select_kept(BaSelect* e, uint64_t* kept_first, uint32_t* kept) {
+    if (!e) return fail("null batch");
+    if (!e->ran) return fail("ba_select_run has not been called");
+    select_get(e, e->L.kept_first, kept_first, (size_t)e->n_reads + 1); select_get(e, e->L.kept, kept, e->total_kept);
+    return 0;
+}
+int ba_select_times(BaSelect* e, float* group_ms, float* mark_ms, float* emit_ms) {
+    if (!e) return fail("null batch");
+    if (group_ms) *group_ms = e->group_ms;
+    if (mark_ms) *mark_ms = e->mark_ms;
+    if (emit_ms) *emit_ms = e->emit_ms;
+    return 0;
+}
+void ba_select_destroy(BaSelect* e) { delete e; }
 
 // ------------------------------------------------------------------ the reference index (ba_ref_index_*, ba_seeding_*_indexed)
 // One reference's sketch, built once, and seeders whose problems are reads against all of it (ba_index.hip; the rule: INTEGRATION.md,

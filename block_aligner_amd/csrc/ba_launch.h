@@ -10,6 +10,7 @@
 #include "ba_index.h"
 #include "ba_params.h"
 #include "ba_seeding.h"
+#include "ba_select.h"
 #include "ba_stats.h"
 #include "ba_text.h"
 
@@ -88,6 +89,10 @@ hipError_t ba_launch_index_table(hipStream_t s, const ba::IndexParams* ip);
 hipError_t ba_launch_index_lookup(hipStream_t s, const ba::IndexLookupParams* lp, int emit);
 hipError_t ba_launch_index_hit_sort(hipStream_t s, const ba::IndexLookupParams* lp);
 hipError_t ba_launch_index_sort(hipStream_t s, const uint64_t* in, uint64_t* out, uint32_t n, uint32_t bits, void* temp, size_t* temp_bytes);
+// ba_select.hip (scatter 0: the count pass, 1: the scatter pass)
+hipError_t ba_launch_select_group(hipStream_t s, const ba::SelectParams* sp, int scatter);
+hipError_t ba_launch_select_mark(hipStream_t s, const ba::SelectParams* sp);
+hipError_t ba_launch_select_emit(hipStream_t s, const ba::SelectParams* sp);
 // ba_stats.hip
 hipError_t ba_launch_stats(hipStream_t s, const ba::StatsParams* sp);
 hipError_t ba_launch_stats_extend(hipStream_t s, const ba::ExtendParams* ep, const ba::AlignStats* side, ba::AlignStats* out);

@@ -80,6 +80,16 @@ class SeedingParamsC(C.Structure):
     _fields_ = [("k", C.c_uint32), ("w", C.c_uint32), ("max_occ", C.c_uint32)]
 
 
+class SelectParamsC(C.Structure):
+    """struct BaSelectParams (include/block_aligner_hip.h): the parameters of the ba_select_* calls."""
+    _fields_ = [("mask_permille", C.c_uint32), ("sec_permille", C.c_uint32), ("max_secondary", C.c_uint32), ("mapq_max", C.c_uint32),
+                ("full_support", C.c_uint32), ("min_score", C.c_int32)]
+
+
+SEL_PRIMARY, SEL_SUPPLEMENTARY, SEL_SECONDARY, SEL_DROPPED, SEL_EXCLUDED = 0, 1, 2, 3, 4   # Selector.results()["cls"]
+SEL_NONE = 0xffffffff                                                                         # parent and rank of an excluded candidate
+
+
 class AccuracyC(C.Structure):
     """struct BaAccuracy: what ba_accuracy_summary reports."""
     _fields_ = [("n", C.c_uint64), ("compared", C.c_uint64), ("skipped", C.c_uint64), ("wrong", C.c_uint64), ("below", C.c_uint64),
@@ -225,6 +235,17 @@ def lib() -> C.CDLL:
         L.ba_chaining_destroy.argtypes = [vp]
         L.ba_chaining_create_seeded.restype = vp
         L.ba_chaining_create_seeded.argtypes = [C.POINTER(ChainingParamsC), vp]
+        L.ba_select_create.restype = vp
+        L.ba_select_create.argtypes = [C.POINTER(SelectParamsC)] + [vp] * 8 + [sz, sz]
+        L.ba_select_create_chained.restype = vp
+        L.ba_select_create_chained.argtypes = [C.POINTER(SelectParamsC), vp, vp, vp, sz]
+        L.ba_select_reload.argtypes = [vp] * 9 + [sz, sz]
+        L.ba_select_run.argtypes = [vp, C.POINTER(C.c_float)]
+        L.ba_select_counts.argtypes = [vp, C.POINTER(C.c_uint64), vp]
+        L.ba_select_results.argtypes = [vp] * 6
+        L.ba_select_kept.argtypes = [vp, vp, vp]
+        L.ba_select_times.argtypes = [vp, vp, vp, vp]
+        L.ba_select_destroy.argtypes = [vp]
         L.ba_seeding_create.restype = vp
         L.ba_seeding_create.argtypes = [C.POINTER(SeedingParamsC), vp, vp, vp, vp, vp, vp, sz]
         L.ba_seeding_reload.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz]
@@ -1125,6 +1146,159 @@ def paf_columns(results, stats, q_len, strand=None, r_shift=None) -> dict:
                 nm=np.where(ok, np.asarray(stats["mismatches"], dtype=np.int64) + np.asarray(stats["ins"], dtype=np.int64) +
                             np.asarray(stats["del"], dtype=np.int64), z),
                 as_=np.where(ok, np.asarray(results["score"], dtype=np.int64), z))
+
+
+def sam_flags(cls, strand=None) -> np.ndarray:
+    """The SAM flag bits a selection decides, per candidate: 16 on the minus strand, 256 for a secondary, 2048 for a supplementary
+    alignment (cls = Selector.results()["cls"]; strand None: all plus). Dropped and excluded candidates are not reported at all."""
+    cls = np.asarray(cls)
+    minus = np.zeros(len(cls), bool) if strand is None else np.asarray(strand).astype(bool)
+    if len(minus) != len(cls):
+        raise ValueError("cls and strand must have one entry per candidate")
+    return (16 * minus + 256 * (cls == SEL_SECONDARY) + 2048 * (cls == SEL_SUPPLEMENTARY)).astype(np.uint16)
+
+
+def paf_lines(q_names, q_len, t_name, t_len, paf, selection, cigars=None) -> list:
+    """Whole PAF lines of a selection, in Python (no device): q_names and q_len per read, t_name / t_len the one reference, paf = the dict of
+    paf_columns (per chain), selection = the dict of Selector.results() over the same chains, cigars = the chains' CIGAR strings
+    (ChainReport.text_list()) or None. -> one line per kept chain, reads in order and in rank order within a read: the twelve PAF columns
+    with the selector's mapq in the twelfth, then tp:A:P (primary, supplementary) or tp:A:S (secondary), NM:i, AS:i, s2:i (the best score
+    under a head; heads only) and cg:Z where cigars are given."""
+    kept, first = selection["kept"], selection["kept_first"]
+    if len(q_names) != len(first) - 1 or len(q_len) != len(first) - 1:
+        raise ValueError("q_names and q_len must have one entry per read")
+    name = lambda x: x.decode() if isinstance(x, (bytes, bytearray, np.bytes_)) else str(x)
+    lines = []
+    for r in range(len(first) - 1):
+        for c in kept[int(first[r]):int(first[r + 1])].tolist():
+            head = int(selection["cls"][c]) != SEL_SECONDARY
+            f = [name(q_names[r]), int(q_len[r]), int(paf["q_start"][c]), int(paf["q_end"][c]), name(paf["strand"][c]), name(t_name), int(t_len),
+                 int(paf["t_start"][c]), int(paf["t_end"][c]), int(paf["n_match"][c]), int(paf["aln_len"][c]), int(selection["mapq"][c]),
+                 "tp:A:P" if head else "tp:A:S", f"NM:i:{int(paf['nm'][c])}", f"AS:i:{int(paf['as_'][c])}"]
+            if head:
+                f.append(f"s2:i:{int(selection['sub_score'][c])}")
+            if cigars is not None:
+                f.append("cg:Z:" + name(cigars[c]))
+            lines.append("\t".join(str(x) for x in f))
+    return lines
+
+
+class Selector:
+    """Read-level selection on the device (ba_select_*; the rule: INTEGRATION.md, "Selecting a read's alignments"). Candidate c -- a chain
+    before alignment, an alignment after it -- belongs to read[c], scores score[c] and covers [q_start[c], q_end[c]) of the oriented read of
+    q_len[c] bases on strand[c] (None: all plus); support[c] (None: full) scales the mapping quality, exclude[c] takes a candidate out.
+    Candidates may come in any order; a read holds at most 1024. Arguments are checked before the device is touched.
+
+    run() marks every candidate and returns the kernels' time; results() gives cls (SEL_*), mapq, parent, rank and sub_score per candidate in
+    the caller's order, and kept_first / kept / kept_per_read: per read, the candidates to report, the primary first."""
+
+    @staticmethod
+    def _arrays(read, score, q_start, q_end, q_len, strand, support, exclude):
+        a = [np.ascontiguousarray(read, dtype=np.uint32), np.ascontiguousarray(score, dtype=np.int32)] + \
+            [np.ascontiguousarray(x, dtype=np.uint32) for x in (q_start, q_end, q_len)] + \
+            [None if strand is None else np.ascontiguousarray(strand, dtype=np.uint8), None if support is None else np.ascontiguousarray(support, dtype=np.uint32),
+             None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint8)]
+        if any(x is not None and len(x) != len(a[0]) for x in a):
+            raise ValueError("read, score, q_start, q_end, q_len, strand, support and exclude must have one entry per candidate")
+        return a
+
+    @staticmethod
+    def _reads(read, n_reads):
+        return int(n_reads) if n_reads is not None else (int(np.max(read)) + 1 if len(read) else 0)
+
+    def __init__(self, mask_permille: int, sec_permille: int, max_secondary: int, mapq_max: int, full_support: int, min_score: int, read, score, q_start,
+                 q_end, q_len, strand=None, support=None, exclude=None, n_reads=None):
+        a = self._arrays(read, score, q_start, q_end, q_len, strand, support, exclude)
+        self.n, self.n_reads = len(a[0]), self._reads(a[0], n_reads)
+        self.params = SelectParamsC(mask_permille, sec_permille, max_secondary, mapq_max, full_support, min_score)
+        self._res = None
+        self._h = lib().ba_select_create(C.byref(self.params), *_ptrs(a), self.n, self.n_reads)
+        if not self._h:
+            raise RuntimeError(last_error())
+
+    @classmethod
+    def from_chain_batch(cls, mask_permille: int, sec_permille: int, max_secondary: int, mapq_max: int, full_support: int, min_score: int,
+                         batch: "ChainBatchAligner", read_of_chain, support=None, n_reads=None):
+        """A selector over the alignments of a ChainBatchAligner that has run (ba_select_create_chained): candidate c is chain c, of read
+        read_of_chain[c]; scores, spans and statuses go from the batch's buffers to the selector's on the device, q_len and strand are the
+        batch's, and a chain with a failed status is excluded. The selector does not depend on the batch afterwards; reload() refuses it."""
+        read = np.ascontiguousarray(read_of_chain, dtype=np.uint32)
+        sup = None if support is None else np.ascontiguousarray(support, dtype=np.uint32)
+        if len(read) != batch.n or (sup is not None and len(sup) != batch.n):
+            raise ValueError("read_of_chain and support must have one entry per chain")
+        self = cls.__new__(cls)
+        self._h = None
+        self._res = None
+        self.n, self.n_reads = len(read), cls._reads(read, n_reads)
+        self.params = SelectParamsC(mask_permille, sec_permille, max_secondary, mapq_max, full_support, min_score)
+        h = lib().ba_select_create_chained(C.byref(self.params), getattr(batch, "_h", None), read.ctypes.data, None if sup is None else sup.ctypes.data,
+                                           self.n_reads)
+        if not h:
+            raise RuntimeError(last_error())
+        self._h = h
+        return self
+
+    @classmethod
+    def from_chains(cls, mask_permille: int, sec_permille: int, max_secondary: int, mapq_max: int, full_support: int, min_score: int,
+                    chainer: "AnchorChainer", read_of_problem, q_len, strand=None, n_reads=None):
+        """A selector over the chains of an AnchorChainer that has run, to prune them before they are aligned (host-side glue over
+        results()): score = chain_score, the span runs from the chain's first anchor to the end of its last, support = its anchors;
+        read_of_problem, q_len and strand are per problem and expanded by chain_problem. results()["kept"] are then the chains to align."""
+        res = chainer.results()
+        per = [np.asarray(read_of_problem), np.asarray(q_len)] + ([] if strand is None else [np.asarray(strand)])
+        if any(len(x) != chainer.n for x in per):
+            raise ValueError("read_of_problem, q_len and strand must have one entry per problem")
+        cp, first = res["chain_problem"], res["anchor_first"].astype(np.int64)
+        last = first[1:] - 1
+        return cls(mask_permille, sec_permille, max_secondary, mapq_max, full_support, min_score, per[0][cp], res["chain_score"],
+                   res["q_anchor"][first[:-1]], res["q_anchor"][last] + res["anchor_len"][last], per[1][cp], None if strand is None else per[2][cp],
+                   (first[1:] - first[:-1]).astype(np.uint32), None, cls._reads(per[0], n_reads))
+
+    def _call(self, name, *args):
+        if getattr(lib(), f"ba_select_{name}")(self._h, *args):
+            raise RuntimeError(last_error())
+
+    def reload(self, read, score, q_start, q_end, q_len, strand=None, support=None, exclude=None, n_reads=None) -> None:
+        """Replace the candidates and keep parameters and device buffers (ba_select_reload): no more candidates and no more reads than at first."""
+        a = self._arrays(read, score, q_start, q_end, q_len, strand, support, exclude)
+        nr = self._reads(a[0], n_reads)
+        self._res = None
+        self._call("reload", *_ptrs(a), len(a[0]), nr)
+        self.n, self.n_reads = len(a[0]), nr
+
+    def run(self) -> float:
+        ms = C.c_float()
+        self._res = None
+        self._call("run", C.byref(ms))
+        return ms.value
+
+    def results(self):
+        """-> dict: per candidate cls, mapq, parent, rank, sub_score; kept_first (one entry per read and one more), kept, kept_per_read."""
+        if self._res is None:
+            nk = C.c_uint64()
+            per = np.zeros(self.n_reads, np.uint32)
+            self._call("counts", C.byref(nk), per.ctypes.data)
+            out = dict(cls=np.zeros(self.n, np.uint8), mapq=np.zeros(self.n, np.uint8), parent=np.zeros(self.n, np.uint32), rank=np.zeros(self.n, np.uint32),
+                       sub_score=np.zeros(self.n, np.int32))
+            self._call("results", *_ptrs(out.values()))
+            out["kept_first"], out["kept"] = np.zeros(self.n_reads + 1, np.uint64), np.zeros(nk.value, np.uint32)
+            self._call("kept", out["kept_first"].ctypes.data, out["kept"].ctypes.data)
+            out["kept_per_read"] = per
+            self._res = out
+        return self._res
+
+    def times(self):
+        """Device milliseconds of the last run(): the grouping with its scan, the marking with its scan, the emit."""
+        g, m, e = C.c_float(), C.c_float(), C.c_float()
+        self._call("times", C.byref(g), C.byref(m), C.byref(e))
+        return dict(group_ms=g.value, mark_ms=m.value, emit_ms=e.value)
+
+    def close(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.ba_select_destroy(self._h)
+            self._h = None
+
+    __del__ = close
 
 
 class AnchorChainer:

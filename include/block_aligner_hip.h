@@ -500,6 +500,59 @@ int ba_chain_windows(const uint32_t* q_len, const uint64_t* r_off, const uint32_
                      const uint32_t* r_anchor, const uint32_t* anchor_len, uintptr_t n_chains, uint32_t margin, uint64_t* r_off_out,
                      uint32_t* r_len_out, uint32_t* r_anchor_out);
 
+/* ---- read-level selection on the device: from candidates in any order -- chains before alignment, alignments after it -- to a mapper's
+ * records: which of a read's candidates is primary, which are supplementary or secondary, which are dropped, and the mapping quality of the
+ * heads ("Selecting a read's alignments": the rule, normative; all integer arithmetic, products in 64 bits).
+ *
+ * Candidate c belongs to read[c] < n_reads; the candidates of a read need be neither contiguous nor ordered, and a read may hold at most 1024.
+ * It covers [q_start, q_end) of the oriented read, q_start <= q_end <= q_len (q_len: the read's length), on strand 0 or 1 (NULL: all 0); on
+ * strand 1 its span in the read's own frame is [q_len - q_end, q_len - q_start). support (NULL: full support everywhere): what the mapping
+ * quality is scaled by, such as a chain's anchors. exclude (NULL: none): non-zero takes the candidate out. A candidate that is excluded, scores
+ * below min_score or has an empty span gets BA_SEL_EXCLUDED and plays no part. The others are ranked per read by score descending, index
+ * ascending, and marked in that order: the first head (a primary or supplementary candidate so far, in rank order) that it overlaps by at
+ * least mask_permille / 1000 of the shorter span is its parent, and it is secondary if it scores at least sec_permille / 1000 of the parent
+ * and fewer than max_secondary secondaries of the read were kept, else dropped; without such a head it is a head itself, primary at rank 0,
+ * supplementary otherwise. A head's mapq = mapq_max * (score - sub_score) * min(support, full_support) / (score * full_support), rounded
+ * down, sub_score being the best score that hangs under it (0: none). Every argument is checked before the device is touched; a message
+ * names the candidate, and for the cap the read. */
+struct BaSelectParams {
+    uint32_t mask_permille;   /* 1 .. 1000: the overlap with a head, of the shorter span, from which a candidate hangs under it */
+    uint32_t sec_permille;    /* 0 .. 1000: a secondary scores at least this much of its parent */
+    uint32_t max_secondary;   /* secondaries kept per read; 0 keeps none */
+    uint32_t mapq_max;        /* 0 .. 255 */
+    uint32_t full_support;    /* 1 .. 65535: the support from which the mapping quality is not scaled down */
+    int32_t min_score;        /* >= 1: a candidate takes part from this score */
+};
+enum { BA_SEL_PRIMARY = 0, BA_SEL_SUPPLEMENTARY = 1, BA_SEL_SECONDARY = 2, BA_SEL_DROPPED = 3, BA_SEL_EXCLUDED = 4 };
+typedef struct BaSelect BaSelect;
+BaSelect* ba_select_create(const struct BaSelectParams* params, const uint32_t* read, const int32_t* score, const uint32_t* q_start,
+                           const uint32_t* q_end, const uint32_t* q_len, const uint8_t* strand, const uint32_t* support, const uint8_t* exclude,
+                           uintptr_t n, uintptr_t n_reads);
+/* A selector over the results of a chain batch that has run: candidate c is the batch's chain c, of read read_of_chain[c]. score, q_start,
+ * q_end and status are copied device to device from the batch's result buffers, q_len and strand are the batch's; a chain whose status has an
+ * overflow, lost or watchdog bit (the bits after which ba_chain_batch_stats zeroes its record) is excluded. The batch need not have BA_TRACE.
+ * Refused for a batch that has not finished a run since it was created or reloaded. The handle does not depend on the batch afterwards: the
+ * copy is complete when the call returns. ba_select_reload refuses it. */
+BaSelect* ba_select_create_chained(const struct BaSelectParams* params, BaChainBatch* ran, const uint32_t* read_of_chain, const uint32_t* support,
+                                   uintptr_t n_reads);
+/* Replace the candidates and keep parameters and device buffers: the new set must hold no more candidates and no more reads. */
+int ba_select_reload(BaSelect* batch, const uint32_t* read, const int32_t* score, const uint32_t* q_start, const uint32_t* q_end, const uint32_t* q_len,
+                     const uint8_t* strand, const uint32_t* support, const uint8_t* exclude, uintptr_t n, uintptr_t n_reads);
+/* The grouping, the marking and the emit. kernels_ms (optional): the sum of their HIP-event times. */
+int ba_select_run(BaSelect* batch, float* kernels_ms);
+/* After a run: the candidates kept (class <= BA_SEL_SECONDARY) in all, and per read (n_reads entries). Either pointer may be NULL. */
+int ba_select_counts(BaSelect* batch, uint64_t* n_kept, uint32_t* kept_per_read);
+/* After a run, per candidate in the caller's order; any pointer may be NULL. cls: BA_SEL_*; mapq: heads only, else 0; parent: the head the
+ * candidate hangs under (a head: itself); rank: its place among the read's eligible candidates; sub_score: heads only, else 0. An excluded
+ * candidate has parent = rank = 0xffffffff. */
+int ba_select_results(BaSelect* batch, uint8_t* cls, uint8_t* mapq, uint32_t* parent, uint32_t* rank, int32_t* sub_score);
+/* After a run: what to report. kept_first (n_reads + 1 entries): where a read's kept candidates start; kept (n_kept entries): the candidates,
+ * reads in order and in rank order within a read (the primary first). Either pointer may be NULL. */
+int ba_select_kept(BaSelect* batch, uint64_t* kept_first, uint32_t* kept);
+/* Device times of the last run in ms: the grouping's two passes with their scan, the marking with its scan, the emit. Any may be NULL. */
+int ba_select_times(BaSelect* batch, float* group_ms, float* mark_ms, float* emit_ms);
+void ba_select_destroy(BaSelect* batch);
+
 /* ---- every pair with its own block range. The reference's callers choose the range per pair -- percent_len(max(|q|, |r|), 0.01) ..=
  * percent_len(max(|q|, |r|), p) in /root/reference/examples/nanopore_bench_global.rs:144-171, Block::align(..., min..=max, x) in
  * src/scan_block.rs:847 --, while ba_batch_create takes one range for the whole batch. These calls bin the pairs by (min, max), align every bin as
