@@ -2683,6 +2683,7 @@ int ba_batch_cigars(BaBatch* b, uint32_t* runs, uint64_t capacity) {
 // D11_open, whole columns one after the other (form 0: 128 cells per column, four columns per wave; 1: 32 cells, sixteen per wave; 2 / 3 / 4: one
 // column of 128 / 64 / 32 cells per wave; 5 / 6 / 7: k_multi's slots in the order of its loop of steps, four columns of 128 / two of 256 / one of 512 cells per wave);
 // out: the columns' R11.
+// (Beside it: ba_dev_lane_prim, the single helpers those scans are built from, and ba_dev_sort_keys, the seeding units' sort and search.)
 int ba_dev_lane_scan(int form, const int16_t* x, uint32_t n_cells, int gap_extend, int16_t* out) {
     if (form < 0 || form > 7 || !x || !out) return fail("ba_dev_lane_scan: bad arguments");
     const uint32_t per_wave = (form <= 1 || form >= 5) ? 512u : (form == 2 ? 128u : (form == 3 ? 64u : 32u));
@@ -2694,6 +2695,41 @@ int ba_dev_lane_scan(int form, const int16_t* x, uint32_t n_cells, int gap_exten
     HIP_TRY(ba_launch_lane_kat(nullptr, form, dx.as<short>(), dout.as<short>(), gap_extend, n_cells / per_wave));
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, dout.p, (size_t)n_cells * 2, hipMemcpyDeviceToHost));
+    return 0;
+}
+// ... of the single device helpers (k_prim_kat, ba_kernels.hip: op -> helper in its switch). x, out: four words per lane, whole waves of 64 lanes;
+// a helper's operands are x[i] ^ (low word of k), k is also the op's wave-uniform operand (high word: multiplier, constant, parked value; all 64
+// bits: a lane mask).
+constexpr int BA_PRIM_OPS = 78;
+int ba_dev_lane_prim(int op, const int32_t* x, uint32_t n_lanes, uint64_t k, int32_t* out) {
+    if (op < 0 || op >= BA_PRIM_OPS || !x || !out) return fail("ba_dev_lane_prim: bad arguments");
+    if (n_lanes == 0 || n_lanes % 64u) return fail("ba_dev_lane_prim: %u lanes are not whole waves of 64", n_lanes);
+    const size_t bytes = (size_t)n_lanes * 16;
+    DevBuf dx, dout;
+    if (dx.alloc(bytes) || dout.alloc(bytes)) return 1;
+    HIP_TRY(hipMemcpy(dx.p, x, bytes, hipMemcpyHostToDevice));
+    HIP_TRY(ba_launch_prim_kat(nullptr, op, dx.as<int>(), dout.as<int>(), (unsigned long long)k, n_lanes / 64u));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+// ... and of ba::seed::sort_network<threads> and ba::seed::lower_bound (k_sort_kat): keys holds 2 n words. The first n are sorted in place in LDS by one
+// workgroup of 64 (k_select_mark's) or 1024 (k_seeding_sort's, k_index_hit_sort's) threads, n within what those kernels sort in LDS; word n + i
+// receives lower_bound of the caller's i-th key in the sorted array.
+int ba_dev_sort_keys(int threads, uint64_t* keys, uint32_t n) {
+    if ((threads != 64 && threads != 1024) || !keys) return fail("ba_dev_sort_keys: bad arguments");
+    const uint32_t cap = threads == 64 ? ba::SELECT_MAX_PER_READ : ba::SEEDING_SORT_LDS;
+    if (n > cap) return fail("ba_dev_sort_keys: %u keys, %d threads sort at most %u in LDS", n, threads, cap);
+    if (n == 0) return 0;
+    DevBuf dk, dlb;
+    if (dk.alloc((size_t)n * 8) || dlb.alloc((size_t)n * 4)) return 1;
+    HIP_TRY(hipMemcpy(dk.p, keys, (size_t)n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(ba_launch_sort_kat(nullptr, threads, dk.as<uint64_t>(), n, dlb.as<uint32_t>()));
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<uint32_t> lb(n);
+    HIP_TRY(hipMemcpy(keys, dk.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(lb.data(), dlb.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n; i++) keys[n + i] = lb[i];
     return 0;
 }
 // ... and the kernel catalogue (tests/test_kernel_catalogue.py): the forms -- 0: there is no such kernel -- that the library holds of a family

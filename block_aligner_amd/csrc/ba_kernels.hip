@@ -24,6 +24,9 @@
 #if !BA_BIG && BA_PMAX == 1 && !BA_SPECIAL
 #include "ba_quad.hpp"
 #endif
+#if BA_KIND == 0 && BA_PMAX == 1 && !BA_SPECIAL && !BA_BIG
+#include "ba_seed_device.hpp"   // (k_sort_kat: the sort and the search of the seeding units, for their known-answer test)
+#endif
 
 // The catalogue entries of this unit (ba_launch.h): the only place that names a kernel's template arguments and its workgroup size.
 // K(T, X) is a family's instantiation with / without traceback and X-drop.
@@ -178,6 +181,150 @@ __global__ void __launch_bounds__(64) k_lane_kat(int form, const short* __restri
 }
 extern "C" hipError_t ba_launch_lane_kat(hipStream_t s, int form, const short* x, short* out, int gap_extend, unsigned waves) {
     k_lane_kat<<<dim3(waves), dim3(64), 0, s>>>(form, x, out, gap_extend);
+    return hipGetLastError();
+}
+
+// Device-side known answers of the single helpers the fill kernels are built from (ba_device.hpp, ba_quad.hpp, ba_multi.hpp, ba_small.hpp, and
+// ffbl_u32 of ba_driver.hpp): the lane shifts and broadcasts, the adds and maxima with a fused DPP control, the packed 16-bit arithmetic with its
+// op_sel / clamp / SDWA modifiers, the v_perm shuffles, v_bfi, v_cndmask with a scalar mask and the v_writelane parking. One wave per workgroup, all
+// 64 lanes active. Lane l of wave w reads four words x[0 .. 3]; k is wave-uniform (a multiplier, a mask, a value to park -- per op). Every operand of
+// a helper is a[i] = x[i] ^ (low word of k), computed here: a cross-lane helper then reads a register that a VALU instruction has just written, as
+// it does inside the loops of steps, and the wait states between that write and the DPP / swizzle / permute read are the helper's own (the s_nop 1
+// inside the assembly strings, the compiler's padding around the builtins). The helpers are called as they stand; templates with the
+// instantiations the kernels use plus the edges. op -> helper: the case labels below; tests/lane_prims_ref.py holds the same table and a model of
+// every op written from the helper's comment. Four words out per lane; an op leaves the words it does not name at 0.
+// Reached only through the development library (ba_dev_lane_prim, ba_host.cpp).
+__global__ void __launch_bounds__(64) k_prim_kat(int op, const int4* __restrict__ x, int4* __restrict__ out, unsigned long long k) {
+    using namespace ba;
+    const int lane = lane_id();
+    const size_t at = (size_t)blockIdx.x * 64 + (size_t)lane;
+    const int4 xi = x[at];
+    const int kl = (int)(uint32_t)k, kh = (int)(uint32_t)(k >> 32);
+    int o0 = 0, o1 = 0, o2 = 0, o3 = 0;
+#define A0 (xi.x ^ kl)
+#define A1 (xi.y ^ kl)
+#define A2 (xi.z ^ kl)
+#define A3 (xi.w ^ kl)
+    switch (op) {
+    // ---- shifts
+    case 0: o0 = wave_shr1(A0, A1); break;                          // (src, fill)
+    case 1: o0 = wave_shr1_z(A0); break;
+    case 2: o0 = row_shr1_z(A0); break;
+    case 3: o0 = row_shl1_keep(A1, A0); break;                      // (last, src)
+    case 4: o0 = quad_shr1(A0); break;
+    case 5: o0 = slot_shr1_z<16>(A0, lane & 15); break;
+    case 6: o0 = slot_shr1_z<32>(A0, lane & 31); break;
+    case 7: o0 = slot_shr1_z<64>(A0, lane); break;
+    case 8: o0 = slot_shl1_keep<16>(A1, A0, lane & 15); break;      // (last, src, l)
+    case 9: o0 = slot_shl1_keep<32>(A1, A0, lane & 31); break;
+    case 10: o0 = slot_shl1_keep<64>(A1, A0, lane); break;
+    // ---- broadcasts
+    case 11: o0 = row_bcast<0>(A0); break;
+    case 12: o0 = row_bcast<15>(A0); break;
+    case 13: o0 = row_bcast<7>(A0); break;
+    case 14: o0 = slot_bcast<0>(A0); break;
+    case 15: o0 = slot_bcast<15>(A0); break;
+    case 16: o0 = slot_bcast<3>(A0); break;
+    case 17: o0 = quad_bcast<0>(A0); o1 = quad_bcast<1>(A1); o2 = quad_bcast<2>(A2); o3 = quad_bcast<3>(A3); break;
+    case 18: o0 = slot_first<16>(A0, lane); break;
+    case 19: o0 = slot_first<32>(A0, lane); break;
+    case 20: o0 = slot_first<64>(A0, lane); break;
+    case 21: o0 = slot_last<16>(A0, lane); break;
+    case 22: o0 = slot_last<32>(A0, lane); break;
+    case 23: o0 = slot_last<64>(A0, lane); break;
+    case 24: o0 = set_lane0(A0, kh); break;
+    case 25: { int v = A0; park<0>(v, kh); o0 = v; o1 = unpark<0>(v); break; }
+    case 26: { int v = A0; park<31>(v, kh); o0 = v; o1 = unpark<31>(v); break; }
+    case 27: { int v = A0; park<63>(v, kh); o0 = v; o1 = unpark<63>(v); break; }
+    // ---- adds, maxima and scans over lanes
+    case 28: o0 = add_shr1(A0, A1); break;
+    case 29: o0 = add_row_shr1(A0, A1); break;
+    case 30: o0 = wave_prefix_max(A0); break;
+    case 31: o0 = wave_prefix_max16(A0); break;
+    case 32: o0 = wave_prefix_max32(A0); break;
+    case 33: o0 = max_lanes<16>(A0); break;
+    case 34: o0 = max_lanes<32>(A0); break;
+    case 35: o0 = max_lanes<64>(A0); break;
+    case 36: o0 = wave_max(A0); break;
+    case 37: o0 = wave_min(A0); break;
+    case 38: first8_max2(A0, A1, o0, o1); break;
+    case 39: o0 = quad_prefix_max(A0); break;
+    case 40: o0 = quad_all_max(A0); break;
+    case 41: case 42: {   // src = (a, ~a), last = (a rotated by one register + 1, by two - 1), the lane mask = k; 41: the first four registers out, 42: the others
+        const int sd[4] = {A0, A1, A2, A3}, sr[4] = {~A0, ~A1, ~A2, ~A3};
+        const int ld[4] = {A1 + 1, A2 + 1, A3 + 1, A0 + 1}, lr[4] = {A2 - 1, A3 - 1, A0 - 1, A1 - 1};
+        int d[4], r[4];
+        quad_shl1_keep8(d, r, sd, sr, ld, lr, k);
+        if (op == 41) { o0 = d[0]; o1 = d[1]; o2 = d[2]; o3 = d[3]; } else { o0 = r[0]; o1 = r[1]; o2 = r[2]; o3 = r[3]; }
+        break;
+    }
+    // ---- packed and bit arithmetic inside the lane
+    case 43: o0 = adds(A0, A1); break;
+    case 44: o0 = subs(A0, A1); break;
+    case 45: o0 = vmax(A0, A1); break;
+    case 46: o0 = vmaxu(A0, A1); break;
+    case 47: o0 = neq01(A0, A1, 0x00010001); break;
+    case 48: o0 = eq01(A0, A1, 0x00010001); break;
+    case 49: o0 = sign_bits(A0); break;
+    case 50: o0 = (int)bfi((uint32_t)kh, (uint32_t)A0, (uint32_t)A1); break;
+    case 51: o0 = pk_mul(A0, kh); break;
+    case 52: o0 = pk_mad(A0, kh, A1); break;
+    case 53: o0 = pk_mad_k<2>(A0, A1); break;
+    case 54: o0 = pk_mad_k<4>(A0, A1); break;
+    case 55: o0 = pk_mad_k<8>(A0, A1); break;
+    case 56: o0 = pk_mad_k<0>(A0, A1); break;
+    case 57: o0 = pk_mad_k<1>(A0, A1); break;
+    case 58: o0 = pk_mad_k<64>(A0, A1); break;
+    case 59: o0 = adds_lo(A0, kh); break;
+    case 60: o0 = max_hi_lo(A0, A1); break;
+    case 61: o0 = splat_lo(A0); break;
+    case 62: o0 = splat_hi(A0); break;
+    case 63: o0 = scan8_splat_lo(A0); break;
+    case 64: o0 = scan8_splat_hi(A0); break;
+    case 65: o0 = sel_mask(k, A0, A1); break;
+    case 66: { int v[4] = {A0, A1, A2, A3}; cells_split(v); o0 = v[0]; o1 = v[1]; o2 = v[2]; o3 = v[3]; break; }
+    case 67: { int v[4] = {A0, A1, A2, A3}; cells_join(v); o0 = v[0]; o1 = v[1]; o2 = v[2]; o3 = v[3]; break; }
+    case 68: o0 = clamp16(A0); break;
+    case 69: o0 = sat16(A0); break;
+    case 70: o0 = (int)ffbl_u32((uint32_t)A0); break;
+    case 71: o0 = (int)nuc_col_offsets((uint32_t)A0); break;
+    case 72: o0 = (int)nuc_keys2((uint32_t)A0); break;
+    case 73: o0 = (int)add_word((uint32_t)A0, (uint32_t)A1, 0); o1 = (int)add_word((uint32_t)A0, (uint32_t)A1, 1); break;
+    case 74: o0 = (int)add_byte((uint32_t)A0, (uint32_t)A1, 0); o1 = (int)add_byte((uint32_t)A0, (uint32_t)A1, 1);
+             o2 = (int)add_byte((uint32_t)A0, (uint32_t)A1, 2); o3 = (int)add_byte((uint32_t)A0, (uint32_t)A1, 3); break;
+    case 75: o0 = pk(A0, A1); break;
+    case 76: o0 = splat(A0); break;
+    case 77: o0 = scan8_inreg(A0, kh); break;
+    default: break;
+    }
+#undef A0
+#undef A1
+#undef A2
+#undef A3
+    out[at] = int4{o0, o1, o2, o3};
+}
+extern "C" hipError_t ba_launch_prim_kat(hipStream_t s, int op, const int* x, int* out, unsigned long long k, unsigned waves) {
+    k_prim_kat<<<dim3(waves), dim3(64), 0, s>>>(op, (const int4*)x, (int4*)out, k);
+    return hipGetLastError();
+}
+
+// ... and of the normalized bitonic network and the binary search that seeding, the reference index and the selection share (ba_seed_device.hpp):
+// one workgroup of THREADS threads sorts keys[0 .. n) in LDS, n <= CAP, as k_seeding_sort / k_index_hit_sort (1024 threads, SEEDING_SORT_LDS keys)
+// and k_select_mark (64 threads, SELECT_MAX_PER_READ keys) do; lb[i] = lower_bound of the caller's i-th key in the sorted array.
+template <uint32_t THREADS, uint32_t CAP>
+__global__ void __launch_bounds__(THREADS) k_sort_kat(uint64_t* keys, uint32_t n, uint32_t* lb) {
+    __shared__ uint64_t sorted[CAP];
+    if (n > CAP) return;
+    for (uint32_t i = threadIdx.x; i < n; i += THREADS) sorted[i] = keys[i];
+    __syncthreads();
+    ba::seed::sort_network<THREADS>(sorted, n);
+    for (uint32_t i = threadIdx.x; i < n; i += THREADS) lb[i] = ba::seed::lower_bound(sorted, n, keys[i]);
+    __syncthreads();   // (every thread has read the caller's keys)
+    for (uint32_t i = threadIdx.x; i < n; i += THREADS) keys[i] = sorted[i];
+}
+extern "C" hipError_t ba_launch_sort_kat(hipStream_t s, int threads, uint64_t* keys, uint32_t n, uint32_t* lb) {
+    if (threads == 64) k_sort_kat<64, ba::SELECT_MAX_PER_READ><<<dim3(1), dim3(64), 0, s>>>(keys, n, lb);
+    else k_sort_kat<1024, ba::SEEDING_SORT_LDS><<<dim3(1), dim3(1024), 0, s>>>(keys, n, lb);
     return hipGetLastError();
 }
 

@@ -54,6 +54,8 @@ extern "C" {
 // ba_kernels.hip
 hipError_t ba_launch_traceback(hipStream_t s, const ba::BatchParams* bp);
 hipError_t ba_launch_lane_kat(hipStream_t s, int form, const short* x, short* out, int gap_extend, unsigned waves);
+hipError_t ba_launch_prim_kat(hipStream_t s, int op, const int* x, int* out, unsigned long long k, unsigned waves);
+hipError_t ba_launch_sort_kat(hipStream_t s, int threads, uint64_t* keys, uint32_t n, uint32_t* lb);
 hipError_t ba_launch_walk(hipStream_t s, const ba::BatchParams* bp, uint32_t grid);
 hipError_t ba_launch_walk_l2(hipStream_t s, const ba::BatchParams* bp, uint32_t grid);
 hipError_t ba_launch_walk_loc(hipStream_t s, const ba::BatchParams* bp, uint32_t grid);
