@@ -33,6 +33,9 @@ struct ChainingParams {
     // start (chain_off[n] + 1 entries); per kept anchor, in path order: the trimmed anchor and the input anchor it came from.
     uint32_t* chain_problem; uint32_t* chain_rank; int32_t* chain_score; uint64_t* out_first;
     uint32_t* out_q; uint32_t* out_r; uint32_t* out_len; uint32_t* out_src;
+    // a bounded chainer ("Several sequences"): where the n_seqs sequences start in the frame of r_anchor, and where the last one ends
+    // (n_seqs + 1 entries). Read by the bounded fill alone; 0 and null otherwise.
+    uint32_t n_seqs; const uint64_t* seq_start;
 };
 
 }  // namespace ba

@@ -16,6 +16,14 @@
 #include <hip/hip_runtime.h>
 
 #include "ba_launch.h"
+#include "ba_seed_device.hpp"   // (lower_bound)
+
+// One source, two units: BA_CHAINING_UNIT 0 (the default) holds the three kernels of a chainer, 1 the fill of a chainer bounded by a
+// sequence table (k_chaining_fill<true>, ba_launch_chaining_fill_bounded) and nothing else -- so the unit that every chainer without a
+// table runs is built from what it was built from before there were tables.
+#ifndef BA_CHAINING_UNIT
+#define BA_CHAINING_UNIT 0
+#endif
 
 namespace {
 
@@ -62,7 +70,13 @@ __device__ __forceinline__ uint32_t wave_incl_sum(uint32_t x, uint32_t lane) {
 
 }  // namespace
 
-__global__ void __launch_bounds__(256) k_chaining_fill(const ba::ChainingParams cp) {
+// BOUNDED: the anchors lie in the frame of several sequences laid end to end ("Several sequences" in INTEGRATION.md), and a chain stays
+// inside one: the lane that loads an anchor finds S, the start of the sequence that holds it, by a lower bound over seq_start, and a
+// predecessor must end behind S -- the anchors are sorted by their ends and none straddles a junction, so that is exactly a predecessor in
+// the anchor's own sequence. re_j > S is dr = re_i - re_j < re_i - S, a bound on dr beside max_dist: the lane turns S into the anchor's own
+// limit min(max_dist, re_i - S - 1), which goes round with the anchor, and the look-back compares dr with it where it compared with
+// max_dist -- no instruction more per predecessor. Without BOUNDED none of this is compiled.
+template <bool BOUNDED> __global__ void __launch_bounds__(256) k_chaining_fill(const ba::ChainingParams cp) {
     extern __shared__ uint32_t lds[];
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6, mask = cp.ring - 1u;
     uint32_t* rq = lds + w * 3u * cp.ring;
@@ -82,8 +96,14 @@ __global__ void __launch_bounds__(256) k_chaining_fill(const ba::ChainingParams 
         for (uint32_t base = 0; base < cnt; base += 64u) {
             const uint32_t il = base + lane;
             const bool in = il < cnt;
-            uint32_t L = 1, qe = 0, re = 0;
+            uint32_t L = 1, qe = 0, re = 0, lim = 0;   // lim (BOUNDED): the largest dr a predecessor of the anchor may have
             if (in) { L = cp.anchor_len[a0 + il]; qe = cp.q_anchor[a0 + il] + L; re = cp.r_anchor[a0 + il] + L; }
+            if (BOUNDED && in) {
+                // the last sequence that starts at or before the anchor; an empty one starts where the next does, so it is never the last
+                const uint32_t S = (uint32_t)cp.seq_start[ba::seed::lower_bound(cp.seq_start, cp.n_seqs + 1u, (uint64_t)(re - L) + 1u) - 1u];
+                const uint32_t room = re - S - 1u;   // (re > S: the anchor starts at or behind S and has a base)
+                lim = room < cp.max_dist ? room : cp.max_dist;
+            }
             // (the slots written held the anchors il - ring <= base + 63 - (H + 64) < base - H: behind every look-back of this chunk)
             rq[il & mask] = qe; rr[il & mask] = re;
             wave_sync();
@@ -93,6 +113,7 @@ __global__ void __launch_bounds__(256) k_chaining_fill(const ba::ChainingParams 
             for (uint32_t t = 0; t < steps; t++) {
                 const uint32_t i = base + t;
                 const uint32_t qi = bcast(qe, t), ri = bcast(re, t), Li = bcast(L, t);
+                const uint32_t max_dr = BOUNDED ? bcast(lim, t) : cp.max_dist;
                 uint64_t key = (uint64_t)((mw * Li) ^ BIAS) << 32 | NONE;
                 uint32_t g_key = Li;   // the gain that goes with the lane's key
                 const uint32_t look = i < cp.lookback ? i : cp.lookback;
@@ -103,7 +124,7 @@ __global__ void __launch_bounds__(256) k_chaining_fill(const ba::ChainingParams 
                     const uint32_t fj = (uint32_t)rf[s];
                     const uint32_t drift = dq > dr ? udq - udr : udr - udq, lo = dq < dr ? udq : udr;
                     const uint32_t g = Li < lo ? Li : lo;
-                    const bool ok = dq > 0 && dr > 0 && udq <= cp.max_dist && udr <= cp.max_dist && drift <= cp.bandwidth;
+                    const bool ok = dq > 0 && dr > 0 && udq <= cp.max_dist && udr <= max_dr && drift <= cp.bandwidth;
                     const uint32_t v = fj + mw * g - dc * drift - sc * (lo - g);   // (an admissible j: no step leaves int32, by the host's checks)
                     const uint64_t cand = (uint64_t)(v ^ BIAS) << 32 | j;
                     if (ok && cand > key) { key = cand; g_key = g; }
@@ -121,6 +142,8 @@ __global__ void __launch_bounds__(256) k_chaining_fill(const ba::ChainingParams 
         }
     }
 }
+
+#if BA_CHAINING_UNIT == 0
 
 constexpr uint32_t CHAINING_WAVES = 4;   // waves per workgroup of k_chaining_pick and k_chaining_gather: one problem per wave at a time
 
@@ -211,12 +234,18 @@ __global__ void __launch_bounds__(64 * CHAINING_WAVES) k_chaining_gather(const b
     }
 }
 
-extern "C" hipError_t ba_launch_chaining_fill(hipStream_t s, const ba::ChainingParams* cp) {
+#endif   // BA_CHAINING_UNIT == 0
+
+template <bool BOUNDED> static hipError_t launch_fill(hipStream_t s, const ba::ChainingParams* cp) {
     const uint32_t waves = cp->ring > 1024u ? 2u : 4u;   // at most 48 KB of LDS per workgroup
     const uint32_t wgs = (cp->n + waves - 1u) / waves;
-    k_chaining_fill<<<dim3(wgs < 2048u ? wgs : 2048u), dim3(64u * waves), waves * 3u * cp->ring * 4u, s>>>(*cp);
+    k_chaining_fill<BOUNDED><<<dim3(wgs < 2048u ? wgs : 2048u), dim3(64u * waves), waves * 3u * cp->ring * 4u, s>>>(*cp);
     return hipGetLastError();
 }
+#if BA_CHAINING_UNIT == 1
+extern "C" hipError_t ba_launch_chaining_fill_bounded(hipStream_t s, const ba::ChainingParams* cp) { return launch_fill<true>(s, cp); }
+#else
+extern "C" hipError_t ba_launch_chaining_fill(hipStream_t s, const ba::ChainingParams* cp) { return launch_fill<false>(s, cp); }
 extern "C" hipError_t ba_launch_chaining_pick(hipStream_t s, const ba::ChainingParams* cp) {
     const uint32_t wgs = (cp->n + CHAINING_WAVES - 1u) / CHAINING_WAVES;
     k_chaining_pick<<<dim3(wgs < 4096u ? wgs : 4096u), dim3(64 * CHAINING_WAVES), 0, s>>>(*cp);
@@ -227,3 +256,4 @@ extern "C" hipError_t ba_launch_chaining_gather(hipStream_t s, const ba::Chainin
     k_chaining_gather<<<dim3(wgs < 4096u ? wgs : 4096u), dim3(64 * CHAINING_WAVES), 0, s>>>(*cp);
     return hipGetLastError();
 }
+#endif

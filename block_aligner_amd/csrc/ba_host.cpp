@@ -3044,6 +3044,26 @@ void ba_chain_batch_destroy(BaChainBatch* e) { delete e; }
 // From a problem's raw hits to its best chains, in ba_chain_batch_create's layout (ba_chaining.hip; the rule: INTEGRATION.md, "Chaining
 // anchors"). The host checks the arguments, orders the problems longest first and sizes the buffers; the recurrence, the picking and the
 // gather are the device's.
+// A sequence table ("Several sequences"): the sequence that holds position pos is the last non-empty one that starts at or before it.
+struct SeqTable {
+    const uint64_t* start; size_t n, last;   // n + 1 starts; the last non-empty sequence (0 when all are empty)
+    SeqTable(const uint64_t* s, size_t n_seqs) : start(s), n(n_seqs), last(0) {
+        for (size_t i = n; i-- > 0;) if (start[i + 1] > start[i]) { last = i; break; }
+    }
+    uint64_t total() const { return start[n]; }
+    size_t of(uint64_t pos) const {   // (pos >= 0 = start[0]; an empty sequence starts where the next one does, so only trailing ones can come up)
+        const size_t s = (size_t)(std::upper_bound(start, start + n, pos) - start) - 1;
+        return s < last ? s : last;
+    }
+};
+// the table of a call that gives lengths: between 1 and 2^20 sequences, less than 2^31 - 16 bytes in all
+static int seq_table_from_len(const uint32_t* seq_len, size_t n_seqs, std::vector<uint64_t>& start) {
+    if (n_seqs == 0 || n_seqs > (1u << 20)) return fail("an index must hold between 1 and 2^20 sequences (it has %llu)", (unsigned long long)n_seqs);
+    start.assign(n_seqs + 1, 0);
+    for (size_t s = 0; s < n_seqs; s++) start[s + 1] = start[s] + seq_len[s];
+    if (start[n_seqs] >= ba::SEEDING_MAX_LEN) return fail("the sequences (%llu bytes in all) must be shorter than 2^31 - 16 bytes", (unsigned long long)start[n_seqs]);
+    return 0;
+}
 struct BaChaining : StreamOwner {
     BaChainingParams P{};
     uint32_t n = 0, ring = 0;
@@ -3052,6 +3072,8 @@ struct BaChaining : StreamOwner {
     DevBuf chain_problem, chain_rank, chain_score, out_first, out_q, out_r, out_len, out_src;
     float fill_ms = 0, pick_ms = 0, gather_ms = 0;
     bool ran = false;
+    std::vector<uint64_t> seq_start;   // a bounded chainer's sequence table (ba_chaining_create_bounded, or a seeder's index's); empty otherwise
+    DevBuf seq_start_dev;
     ba::ChainingParams params() const {
         ba::ChainingParams cp{};
         cp.n = n; cp.match_w = P.match_w; cp.drift_cost = P.drift_cost; cp.skip_cost = P.skip_cost; cp.lookback = P.lookback; cp.max_dist = P.max_dist;
@@ -3064,6 +3086,7 @@ struct BaChaining : StreamOwner {
         cp.chain_problem = chain_problem.as<uint32_t>(); cp.chain_rank = chain_rank.as<uint32_t>(); cp.chain_score = chain_score.as<int32_t>();
         cp.out_first = out_first.as<uint64_t>(); cp.out_q = out_q.as<uint32_t>(); cp.out_r = out_r.as<uint32_t>(); cp.out_len = out_len.as<uint32_t>();
         cp.out_src = out_src.as<uint32_t>();
+        if (!seq_start.empty()) { cp.n_seqs = (uint32_t)(seq_start.size() - 1); cp.seq_start = seq_start_dev.as<uint64_t>(); }
         return cp;
     }
 };
@@ -3080,8 +3103,9 @@ static int chaining_check_params(const BaChainingParams& P) {
     return 0;
 }
 // Check a set of problems; -> the problems ordered by their number of anchors, the longest first.
+// table: a bounded chainer's sequences -- every anchor ends at or before the end of the sequence that holds its start.
 static int chaining_plan(const BaChainingParams& P, const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor, const uint32_t* anchor_len,
-                         size_t n, std::vector<uint32_t>& order) {
+                         size_t n, std::vector<uint32_t>& order, const std::vector<uint64_t>* table = nullptr) {
     if (!anchor_first || !q_anchor || !r_anchor || !anchor_len) return fail("null argument");
     if (n == 0 || n > (1u << 28)) return fail("a chaining batch must hold between 1 and 2^28 problems");
     if (anchor_first[0] != 0) return fail("anchor_first must start at 0 (problem 0 starts at %llu)", (unsigned long long)anchor_first[0]);
@@ -3089,6 +3113,8 @@ static int chaining_plan(const BaChainingParams& P, const uint64_t* anchor_first
         if (anchor_first[p + 1] < anchor_first[p])
             return fail("problem %zu: anchor_first must not decrease (%llu after %llu)", p, (unsigned long long)anchor_first[p + 1], (unsigned long long)anchor_first[p]);
     if (anchor_first[n] > (1u << 28)) return fail("a chaining batch must hold at most 2^28 anchors");
+    static const uint64_t none[2] = {0, 0};
+    const SeqTable T(table ? table->data() : none, table ? table->size() - 1 : 1);
     for (size_t p = 0; p < n; p++) {
         uint64_t sum = 0, pq = 0, pr = 0;
         for (uint64_t a = anchor_first[p]; a < anchor_first[p + 1]; a++) {
@@ -3101,6 +3127,12 @@ static int chaining_plan(const BaChainingParams& P, const uint64_t* anchor_first
                 return fail("problem %zu, anchor %llu: the anchors must be sorted by (reference end, query end): (%llu, %llu) comes after (%llu, %llu)", p,
                             (unsigned long long)k, (unsigned long long)re, (unsigned long long)qe, (unsigned long long)pr, (unsigned long long)pq);
             pq = qe; pr = re; sum += L;
+            if (table) {
+                const uint64_t end = r_anchor[a] < T.total() ? T.start[T.of(r_anchor[a]) + 1] : T.total();
+                if (re > end)
+                    return fail("problem %zu, anchor %llu: the anchor covers reference %llu to %llu and leaves its sequence, which ends at %llu", p,
+                                (unsigned long long)k, (unsigned long long)r_anchor[a], (unsigned long long)re, (unsigned long long)end);
+            }
         }
         if (sum * (uint64_t)P.match_w >= (1ull << 31))
             return fail("problem %zu: match_w * the sum of anchor_len must stay below 2^31 (it is %llu)", p, (unsigned long long)(sum * (uint64_t)P.match_w));
@@ -3140,24 +3172,51 @@ static int chaining_load(BaChaining* e, const uint64_t* anchor_first, const uint
     e->n = (uint32_t)n; e->n_anchors = na;
     return 0;
 }
-BaChaining* ba_chaining_create(const BaChainingParams* params, const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor,
-                               const uint32_t* anchor_len, uintptr_t n_problems) {
+// the sequence table of a bounded chainer goes to the device once, at its creation
+static int chaining_bound(BaChaining* e, const std::vector<uint64_t>& table) {
+    e->seq_start = table;
+    return e->seq_start_dev.alloc(table.size() * 8) || h2d(e->seq_start_dev, table.data(), table.size());
+}
+static BaChaining* chaining_create(const BaChainingParams* params, const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor,
+                                   const uint32_t* anchor_len, size_t n_problems, const std::vector<uint64_t>* table) {
     std::vector<uint32_t> order;   // every argument is checked before the device is touched
-    if (!params) { fail("null argument"); return nullptr; }
-    if (chaining_check_params(*params) || chaining_plan(*params, anchor_first, q_anchor, r_anchor, anchor_len, n_problems, order)) return nullptr;
+    if (chaining_check_params(*params) || chaining_plan(*params, anchor_first, q_anchor, r_anchor, anchor_len, n_problems, order, table)) return nullptr;
     if (ensure_device()) return nullptr;
     std::unique_ptr<BaChaining> e(new BaChaining);
     e->device = g_device; e->P = *params;
     e->ring = 128;
     while (e->ring < params->lookback + 64u) e->ring <<= 1;
-    if (e->open(4) || chaining_load(e.get(), anchor_first, q_anchor, r_anchor, anchor_len, n_problems, order, true)) return nullptr;
+    if (e->open(4) || (table && chaining_bound(e.get(), *table)) ||
+        chaining_load(e.get(), anchor_first, q_anchor, r_anchor, anchor_len, n_problems, order, true)) return nullptr;
     return e.release();
+}
+BaChaining* ba_chaining_create(const BaChainingParams* params, const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor,
+                               const uint32_t* anchor_len, uintptr_t n_problems) {
+    if (!params) { fail("null argument"); return nullptr; }
+    return chaining_create(params, anchor_first, q_anchor, r_anchor, anchor_len, n_problems, nullptr);
+}
+BaChaining* ba_chaining_create_bounded(const BaChainingParams* params, const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor,
+                                       const uint32_t* anchor_len, uintptr_t n_problems, const uint64_t* seq_start, uintptr_t n_seqs) {
+    if (!params || !seq_start) { fail("null argument"); return nullptr; }
+    if (n_seqs == 0 || n_seqs > (1u << 20)) { fail("a sequence table must hold between 1 and 2^20 sequences (it has %llu)", (unsigned long long)n_seqs); return nullptr; }
+    if (seq_start[0] != 0) { fail("seq_start must start at 0 (sequence 0 starts at %llu)", (unsigned long long)seq_start[0]); return nullptr; }
+    for (size_t s = 0; s < n_seqs; s++)
+        if (seq_start[s + 1] < seq_start[s]) {
+            fail("sequence %zu: seq_start must not decrease (%llu after %llu)", s, (unsigned long long)seq_start[s + 1], (unsigned long long)seq_start[s]);
+            return nullptr;
+        }
+    if (seq_start[n_seqs] >= ba::SEEDING_MAX_LEN) {
+        fail("the sequences (%llu bytes in all) must be shorter than 2^31 - 16 bytes", (unsigned long long)seq_start[n_seqs]);
+        return nullptr;
+    }
+    const std::vector<uint64_t> table(seq_start, seq_start + n_seqs + 1);
+    return chaining_create(params, anchor_first, q_anchor, r_anchor, anchor_len, n_problems, &table);
 }
 int ba_chaining_reload(BaChaining* e, const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor, const uint32_t* anchor_len,
                        uintptr_t n_problems) {
     if (!e) return fail("null batch");
     std::vector<uint32_t> order;
-    if (chaining_plan(e->P, anchor_first, q_anchor, r_anchor, anchor_len, n_problems, order)) return 1;
+    if (chaining_plan(e->P, anchor_first, q_anchor, r_anchor, anchor_len, n_problems, order, e->seq_start.empty() ? nullptr : &e->seq_start)) return 1;
     HIP_TRY(hipSetDevice(e->device));
     return chaining_load(e, anchor_first, q_anchor, r_anchor, anchor_len, n_problems, order, false);
 }
@@ -3169,7 +3228,8 @@ int ba_chaining_run(BaChaining* e, float* kernel_ms) {
     ba::ChainingParams cp = e->params();
     HIP_TRY(hipMemsetAsync(e->counter.p, 0, 4, e->stream));
     HIP_TRY(hipEventRecord(e->ev[0], e->stream));
-    HIP_TRY(ba_launch_chaining_fill(e->stream, &cp));
+    if (cp.n_seqs) HIP_TRY(ba_launch_chaining_fill_bounded(e->stream, &cp));   // (a chainer with a sequence table)
+    else HIP_TRY(ba_launch_chaining_fill(e->stream, &cp));
     HIP_TRY(hipEventRecord(e->ev[1], e->stream));
     HIP_TRY(ba_launch_chaining_pick(e->stream, &cp));
     HIP_TRY(ba_launch_offsets(e->stream, cp.n_chains, e->chain_off.as<uint64_t>(), cp.n));
@@ -3247,6 +3307,10 @@ struct IndexData {   // a reference index on the device (ba_ref_index_*): shared
     uint32_t k = 0, w = 0, prefix_bits = 0, longest_run = 0;
     uint64_t ref_len = 0, n_entries = 0;
     DevBuf key, table;   // n_entries keys code << 32 | pos, ascending; (1 << prefix_bits) + 1 bounds
+    // the sequences, laid end to end in the frame of the positions: where each starts, and where the last one ends (one entry more than
+    // sequences). multi: made by ba_ref_index_create_multi, so chainers over its seeders' hits are bounded by this table.
+    std::vector<uint64_t> seq_start;
+    bool multi = false;
 };
 struct BaSeeding : StreamOwner {
     BaSeedingParams P{};
@@ -3504,8 +3568,10 @@ BaChaining* ba_chaining_create_seeded(const BaChainingParams* params, BaSeeding*
     e->device = s->device; e->P = *params;
     e->ring = 128;
     while (e->ring < params->lookback + 64u) e->ring <<= 1;
-    if (e->open(4) || chaining_load(e.get(), first.data(), s->q_hit.as<uint32_t>(), s->r_hit.as<uint32_t>(), s->hit_len.as<uint32_t>(), n, order, true,
-                                    hipMemcpyDeviceToDevice)) return nullptr;
+    // (a seeder over a multi-sequence index: its hits are in that index's frame and each lies inside one sequence, so the chainer is bounded)
+    if (e->open(4) || (s->index && s->index->multi && chaining_bound(e.get(), s->index->seq_start)) ||
+        chaining_load(e.get(), first.data(), s->q_hit.as<uint32_t>(), s->r_hit.as<uint32_t>(), s->hit_len.as<uint32_t>(), n, order, true,
+                      hipMemcpyDeviceToDevice)) return nullptr;
     return e.release();
 }
 
@@ -3751,20 +3817,29 @@ struct BaRefIndex {
     std::shared_ptr<IndexData> d;
     float sketch_ms = 0, sort_ms = 0, table_ms = 0;
 };
+// ref: the bytes of D.seq_start's sequences, laid end to end
 static int index_build(BaRefIndex* x, const uint8_t* ref) {
     IndexData& D = *x->d;
     const uint32_t len = (uint32_t)D.ref_len, k = D.k, w = D.w;
-    const uint32_t nk = len >= k ? len - k + 1u : 0u, nw = nk == 0u ? 0u : nk > w ? nk - w + 1u : 1u;
+    const size_t n_seqs = D.seq_start.size() - 1;
+    // the work items: a sequence's windows in spans of INDEX_SPAN, numbered from seq_span[s] (a sequence without a k-mer has no window)
+    std::vector<uint64_t> seq_span(n_seqs + 1, 0);
+    for (size_t s = 0; s < n_seqs; s++) {
+        const uint64_t sl = D.seq_start[s + 1] - D.seq_start[s], nk = sl >= k ? sl - k + 1u : 0u, nw = nk == 0u ? 0u : nk > w ? nk - w + 1u : 1u;
+        seq_span[s + 1] = seq_span[s] + (nw + ba::INDEX_SPAN - 1u) / ba::INDEX_SPAN;
+    }
     StreamOwner T;   // the stream and the six events of this build (made below with the build's own error texts, destroyed with T)
-    DevBuf raw, counter, span_cnt, span_first, unsorted, temp, longest;
+    DevBuf raw, counter, span_cnt, span_first, unsorted, temp, longest, d_seq_start, d_seq_span;
     ba::IndexParams ip{};
-    ip.k = k; ip.w = w; ip.len = len; ip.n_windows = nw; ip.n_spans = (nw + ba::INDEX_SPAN - 1u) / ba::INDEX_SPAN; ip.prefix_bits = D.prefix_bits;
+    ip.k = k; ip.w = w; ip.len = len; ip.n_seqs = (uint32_t)n_seqs; ip.n_spans = (uint32_t)seq_span[n_seqs]; ip.prefix_bits = D.prefix_bits;
     HIP_TRY(hipStreamCreateWithFlags(&T.stream, hipStreamNonBlocking));
     for (int i = 0; i < 6; i++) HIP_TRY(hipEventCreate(&T.ev[i]));
     if (raw.alloc(len) || counter.alloc(4) || span_cnt.alloc((size_t)ip.n_spans * 4) || span_first.alloc(((size_t)ip.n_spans + 1) * 8) || longest.alloc(4) ||
-        D.table.alloc(((size_t)(1u << ip.prefix_bits) + 1) * 4)) return 1;
+        D.table.alloc(((size_t)(1u << ip.prefix_bits) + 1) * 4) || d_seq_start.alloc((n_seqs + 1) * 8) || d_seq_span.alloc((n_seqs + 1) * 8)) return 1;
     if (len && h2d(raw, ref, len)) return 1;
+    if (h2d(d_seq_start, D.seq_start.data(), n_seqs + 1) || h2d(d_seq_span, seq_span.data(), n_seqs + 1)) return 1;
     ip.ref = raw.as<uint8_t>(); ip.counter = counter.as<uint32_t>(); ip.span_cnt = span_cnt.as<uint32_t>(); ip.span_first = span_first.as<uint64_t>();
+    ip.seq_start = d_seq_start.as<uint64_t>(); ip.seq_span = d_seq_span.as<uint64_t>();
     ip.table = D.table.as<uint32_t>(); ip.longest_run = longest.as<uint32_t>();
     // the sketch: count, scan, emit
     HIP_TRY(hipMemsetAsync(counter.p, 0, 4, T.stream));
@@ -3808,9 +3883,34 @@ BaRefIndex* ba_ref_index_create(uint32_t k, uint32_t w, const uint8_t* ref, uint
     std::unique_ptr<BaRefIndex> x(new BaRefIndex);
     x->d = std::make_shared<IndexData>();
     x->d->device = g_device; x->d->k = k; x->d->w = w; x->d->ref_len = ref_len;
+    x->d->seq_start = {0, ref_len};
     x->d->prefix_bits = 2u * k < ba::INDEX_MAX_PREFIX_BITS ? 2u * k : ba::INDEX_MAX_PREFIX_BITS;
     if (index_build(x.get(), ref)) return nullptr;
     return x.release();
+}
+// Several sequences in one index ("Several sequences"): pool[seq_off[s] .. + seq_len[s]), laid end to end without a spacer.
+BaRefIndex* ba_ref_index_create_multi(uint32_t k, uint32_t w, const uint8_t* pool, const uint64_t* seq_off, const uint32_t* seq_len, uintptr_t n_seqs) {
+    if (seeding_check_params(BaSeedingParams{k, w, 1})) return nullptr;   // every argument is checked before the device is touched
+    if (!pool || !seq_off || !seq_len) { fail("null argument"); return nullptr; }
+    std::vector<uint64_t> start;
+    if (seq_table_from_len(seq_len, n_seqs, start)) return nullptr;
+    std::vector<uint8_t> bytes(start[n_seqs]);   // (one upload, whatever the number of sequences and wherever they lie in the pool)
+    for (size_t s = 0; s < n_seqs; s++)
+        if (seq_len[s]) memcpy(bytes.data() + start[s], pool + seq_off[s], seq_len[s]);
+    if (ensure_device()) return nullptr;
+    std::unique_ptr<BaRefIndex> x(new BaRefIndex);
+    x->d = std::make_shared<IndexData>();
+    x->d->device = g_device; x->d->k = k; x->d->w = w; x->d->ref_len = start[n_seqs];
+    x->d->seq_start = std::move(start); x->d->multi = true;
+    x->d->prefix_bits = 2u * k < ba::INDEX_MAX_PREFIX_BITS ? 2u * k : ba::INDEX_MAX_PREFIX_BITS;
+    if (index_build(x.get(), bytes.data())) return nullptr;
+    return x.release();
+}
+int ba_ref_index_sequences(BaRefIndex* x, uint64_t* n_seqs, uint64_t* seq_start) {
+    if (!x) return fail("null index");
+    if (n_seqs) *n_seqs = x->d->seq_start.size() - 1;
+    if (seq_start) std::copy(x->d->seq_start.begin(), x->d->seq_start.end(), seq_start);
+    return 0;
 }
 int ba_ref_index_counts(BaRefIndex* x, uint64_t* n_entries, uint32_t* k, uint32_t* w, uint64_t* ref_len, uint32_t* longest_run) {
     if (!x) return fail("null index");
@@ -3882,6 +3982,52 @@ int ba_chain_windows(const uint32_t* q_len, const uint64_t* r_off, const uint32_
         r_off_out[c] = r_off[c] + lo;
         r_len_out[c] = (uint32_t)(hi - lo);
         for (uint64_t a = a0; a < a1; a++) r_anchor_out[a] = (uint32_t)(r_anchor[a] - lo);
+    }
+    return 0;
+}
+// The same for chains in the frame of a multi-sequence index ("Several sequences"): a window stays inside the sequence that holds the
+// chain's first anchor, and comes out as bytes of the caller's pool, where only seq_off says where a sequence lies (host only).
+int ba_chain_windows_seqs(const uint32_t* q_len, const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor, const uint32_t* anchor_len,
+                          uintptr_t n_chains, uint32_t margin, const uint64_t* seq_off, const uint32_t* seq_len, uintptr_t n_seqs, uint64_t* r_off_out,
+                          uint32_t* r_len_out, uint32_t* r_anchor_out, uint32_t* seq_of_chain, uint32_t* local_shift) {
+    if (!q_len || !anchor_first || !q_anchor || !r_anchor || !anchor_len || !seq_off || !seq_len || !r_off_out || !r_len_out || !r_anchor_out || !seq_of_chain ||
+        !local_shift) return fail("null argument");
+    std::vector<uint64_t> start;
+    if (seq_table_from_len(seq_len, n_seqs, start)) return 1;
+    const SeqTable T(start.data(), n_seqs);
+    for (size_t c = 0; c < n_chains; c++) {
+        const uint64_t a0 = anchor_first[c], a1 = anchor_first[c + 1];
+        if (a1 <= a0) return fail("chain %zu has no anchors", c);
+        const size_t s = T.of(r_anchor[a0]);
+        const uint64_t S = start[s], E = start[s + 1];
+        for (uint64_t a = a0; a < a1; a++)
+            if ((uint64_t)q_anchor[a] + anchor_len[a] > q_len[c] || (uint64_t)r_anchor[a] + anchor_len[a] > E)
+                return fail("chain %zu: anchor %llu ends outside its sequences", c, (unsigned long long)(a - a0));
+        const uint64_t qa0 = q_anchor[a0], ra0 = r_anchor[a0], qe = (uint64_t)q_anchor[a1 - 1] + anchor_len[a1 - 1], re = (uint64_t)r_anchor[a1 - 1] + anchor_len[a1 - 1];
+        const uint64_t lo = ra0 - std::min(ra0 - S, qa0 + margin), hi = re + std::min(E - re, (q_len[c] - qe) + margin);
+        r_off_out[c] = seq_off[s] + (lo - S);
+        r_len_out[c] = (uint32_t)(hi - lo);
+        seq_of_chain[c] = (uint32_t)s;
+        local_shift[c] = (uint32_t)(lo - S);
+        for (uint64_t a = a0; a < a1; a++) r_anchor_out[a] = (uint32_t)(r_anchor[a] - lo);
+    }
+    return 0;
+}
+// From the frame of a multi-sequence index to a sequence and positions in it, for closed intervals [r_start, r_end] (host only).
+int ba_ref_locate(const uint32_t* seq_len, uintptr_t n_seqs, const uint32_t* r_start, const uint32_t* r_end, uintptr_t n, uint32_t* seq, uint32_t* local_start,
+                  uint32_t* local_end, uint8_t* crosses) {
+    if (!seq_len || !r_start || !r_end || !seq || !local_start || !local_end || !crosses) return fail("null argument");
+    std::vector<uint64_t> start;
+    if (seq_table_from_len(seq_len, n_seqs, start)) return 1;
+    const SeqTable T(start.data(), n_seqs);
+    for (size_t i = 0; i < n; i++) {
+        if (r_end[i] < r_start[i] || r_end[i] > T.total())
+            return fail("interval %zu: %u to %u is not an interval of the index's %llu bytes", i, r_start[i], r_end[i], (unsigned long long)T.total());
+        const size_t s = T.of(r_start[i]);
+        seq[i] = (uint32_t)s;
+        local_start[i] = (uint32_t)(r_start[i] - start[s]);
+        local_end[i] = (uint32_t)(r_end[i] - start[s]);
+        crosses[i] = r_end[i] > start[s + 1];
     }
     return 0;
 }

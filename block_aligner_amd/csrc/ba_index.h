@@ -9,14 +9,16 @@ constexpr uint32_t INDEX_SPAN = 1024;          // windows of the reference that 
 constexpr uint32_t INDEX_MAX_PREFIX_BITS = 20; // the prefix table is over the top min(2k, 20) bits of a code
 constexpr uint32_t INDEX_NO_CAP = 0xffffffffu; // max_ref_occ: no cap
 
-// The build. The index is keys code << 32 | pos, ascending, and table[x] .. table[x + 1] bounds the keys whose code starts with the
+// The build, of one sequence or of several ("Several sequences": no k-mer and no window holds bytes of two). The index is keys code << 32 | pos, ascending, and table[x] .. table[x + 1] bounds the keys whose code starts with the
 // prefix_bits bits x (1 << prefix_bits entries and one more).
 struct IndexParams {
-    uint32_t k, w, len;              // the reference's bytes
-    uint32_t n_windows, n_spans;     // spans of INDEX_SPAN windows, the last one shorter
+    uint32_t k, w, len;              // the bytes of all sequences, laid end to end: the index's frame
+    uint32_t n_seqs, n_spans;        // spans of INDEX_SPAN windows of one sequence, a sequence's last one shorter
     uint32_t prefix_bits;
     uint32_t n_entries;              // selected k-mers (known after the count pass)
     const uint8_t* ref;              // the bytes, on the device for the build only
+    const uint64_t* seq_start;       // n_seqs + 1: where a sequence starts in the index's frame
+    const uint64_t* seq_span;        // n_seqs + 1: a sequence's first span (a sequence without a k-mer has none)
     uint32_t* counter;               // the sketch's work counter, zeroed before each launch
     uint32_t* span_cnt;              // per span: selected k-mers (the count pass)
     const uint64_t* span_first;      // n_spans + 1: the exclusive scan of span_cnt

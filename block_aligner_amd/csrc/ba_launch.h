@@ -77,8 +77,9 @@ hipError_t ba_launch_extend_gather(hipStream_t s, const ba::ExtendParams* ep);
 // ba_chain.hip
 hipError_t ba_launch_chain_results(hipStream_t s, const ba::ChainParams* cp);
 hipError_t ba_launch_chain_gather(hipStream_t s, const ba::ChainParams* cp);
-// ba_chaining.hip
+// ba_chaining.hip (the bounded fill: its unit BA_CHAINING_UNIT 1)
 hipError_t ba_launch_chaining_fill(hipStream_t s, const ba::ChainingParams* cp);
+hipError_t ba_launch_chaining_fill_bounded(hipStream_t s, const ba::ChainingParams* cp);
 hipError_t ba_launch_chaining_pick(hipStream_t s, const ba::ChainingParams* cp);
 hipError_t ba_launch_chaining_gather(hipStream_t s, const ba::ChainingParams* cp);
 // ba_seeding.hip (emit 0: the count pass, 1: the emit pass)

@@ -265,6 +265,13 @@ def lib() -> C.CDLL:
         L.ba_seeding_create_indexed.argtypes = [vp, u32, u32, vp, vp, vp, vp, sz]
         L.ba_seeding_reload_indexed.argtypes = [vp, vp, vp, vp, vp, sz]
         L.ba_chain_windows.argtypes = [vp] * 7 + [sz, u32, vp, vp, vp]
+        L.ba_ref_index_create_multi.restype = vp
+        L.ba_ref_index_create_multi.argtypes = [u32, u32, vp, vp, vp, sz]
+        L.ba_ref_index_sequences.argtypes = [vp, C.POINTER(C.c_uint64), vp]
+        L.ba_chaining_create_bounded.restype = vp
+        L.ba_chaining_create_bounded.argtypes = [C.POINTER(ChainingParamsC), vp, vp, vp, vp, sz, vp, sz]
+        L.ba_chain_windows_seqs.argtypes = [vp] * 5 + [sz, u32, vp, vp, sz] + [vp] * 5
+        L.ba_ref_locate.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp, vp]
         for f, fields in (("ba_batch", 6), ("ba_sized_batch", 6), ("ba_multibatch", 6), ("ba_extend_batch", 10)):   # the calls of _Batch
             getattr(L, f"{f}_run").argtypes = [vp, C.POINTER(C.c_float)]
             getattr(L, f"{f}_results").argtypes = [vp] * (1 + fields)
@@ -1158,21 +1165,28 @@ def sam_flags(cls, strand=None) -> np.ndarray:
     return (16 * minus + 256 * (cls == SEL_SECONDARY) + 2048 * (cls == SEL_SUPPLEMENTARY)).astype(np.uint16)
 
 
-def paf_lines(q_names, q_len, t_name, t_len, paf, selection, cigars=None) -> list:
+def paf_lines(q_names, q_len, t_name, t_len, paf, selection, cigars=None, target=None) -> list:
     """Whole PAF lines of a selection, in Python (no device): q_names and q_len per read, t_name / t_len the one reference, paf = the dict of
     paf_columns (per chain), selection = the dict of Selector.results() over the same chains, cigars = the chains' CIGAR strings
     (ChainReport.text_list()) or None. -> one line per kept chain, reads in order and in rank order within a read: the twelve PAF columns
     with the selector's mapq in the twelfth, then tp:A:P (primary, supplementary) or tp:A:S (secondary), NM:i, AS:i, s2:i (the best score
-    under a head; heads only) and cg:Z where cigars are given."""
+    under a head; heads only) and cg:Z where cigars are given. With target -- per chain the number of its reference sequence
+    (AnchorChainer.last_window_seq) -- t_name and t_len are sequences indexed by it."""
     kept, first = selection["kept"], selection["kept_first"]
     if len(q_names) != len(first) - 1 or len(q_len) != len(first) - 1:
         raise ValueError("q_names and q_len must have one entry per read")
+    if target is not None:
+        if len(target) != len(paf["q_start"]):
+            raise ValueError("target must have one entry per chain")
+        if len(t_name) != len(t_len) or (len(target) and int(np.max(target)) >= len(t_name)):
+            raise ValueError("t_name and t_len must have one entry per reference sequence")
     name = lambda x: x.decode() if isinstance(x, (bytes, bytearray, np.bytes_)) else str(x)
     lines = []
     for r in range(len(first) - 1):
         for c in kept[int(first[r]):int(first[r + 1])].tolist():
             head = int(selection["cls"][c]) != SEL_SECONDARY
-            f = [name(q_names[r]), int(q_len[r]), int(paf["q_start"][c]), int(paf["q_end"][c]), name(paf["strand"][c]), name(t_name), int(t_len),
+            tn, tl = (t_name, t_len) if target is None else (t_name[int(target[c])], t_len[int(target[c])])
+            f = [name(q_names[r]), int(q_len[r]), int(paf["q_start"][c]), int(paf["q_end"][c]), name(paf["strand"][c]), name(tn), int(tl),
                  int(paf["t_start"][c]), int(paf["t_end"][c]), int(paf["n_match"][c]), int(paf["aln_len"][c]), int(selection["mapq"][c]),
                  "tp:A:P" if head else "tp:A:S", f"NM:i:{int(paf['nm'][c])}", f"AS:i:{int(paf['as_'][c])}"]
             if head:
@@ -1320,13 +1334,21 @@ class AnchorChainer:
         return a
 
     def __init__(self, match_w: int, drift_cost: int, skip_cost: int, lookback: int, max_dist: int, bandwidth: int, max_chains: int, min_score: int,
-                 min_anchors: int, anchor_first, q_anchor, r_anchor, anchor_len):
+                 min_anchors: int, anchor_first, q_anchor, r_anchor, anchor_len, seq_start=None):
+        """seq_start (one entry per sequence and one more, from 0): the anchors lie in the frame of several reference sequences laid end
+        to end, and every chain stays inside one (ba_chaining_create_bounded; INTEGRATION.md, "Several sequences")."""
         a = self._arrays(anchor_first, q_anchor, r_anchor, anchor_len)
         self.n = len(a[0]) - 1
         self.n_anchors = len(a[1])
         self.params = ChainingParamsC(match_w, drift_cost, skip_cost, lookback, max_dist, bandwidth, max_chains, min_score, min_anchors)
         self._res = None
-        self._h = lib().ba_chaining_create(C.byref(self.params), *_ptrs(a), self.n)
+        self.seq_start = None if seq_start is None else np.ascontiguousarray(seq_start, dtype=np.uint64)
+        if self.seq_start is None:
+            self._h = lib().ba_chaining_create(C.byref(self.params), *_ptrs(a), self.n)
+        else:
+            if len(self.seq_start) < 1:
+                raise ValueError("seq_start must have one entry per sequence and one more")
+            self._h = lib().ba_chaining_create_bounded(C.byref(self.params), *_ptrs(a), self.n, self.seq_start.ctypes.data, len(self.seq_start) - 1)
         if not self._h:
             raise RuntimeError(last_error())
 
@@ -1334,10 +1356,12 @@ class AnchorChainer:
     def from_seeder(cls, match_w: int, drift_cost: int, skip_cost: int, lookback: int, max_dist: int, bandwidth: int, max_chains: int, min_score: int,
                     min_anchors: int, seeder: "Seeder"):
         """A chainer over the hits of a Seeder that has run (ba_chaining_create_seeded): the hits go from the seeder's buffers to the chainer's
-        on the device, without a round trip through the host. The chainer is like any other afterwards and does not depend on the seeder."""
+        on the device, without a round trip through the host. The chainer is like any other afterwards and does not depend on the seeder.
+        Over a seeder of a multi-sequence index (RefIndex.from_sequences) the chainer is bounded by the index's sequences: seq_start."""
         self = cls.__new__(cls)
         self._h = None
         self._res = None
+        self.seq_start = getattr(seeder, "seq_start", None)
         self.params = ChainingParamsC(match_w, drift_cost, skip_cost, lookback, max_dist, bandwidth, max_chains, min_score, min_anchors)
         h = lib().ba_chaining_create_seeded(C.byref(self.params), seeder._h)
         if not h:
@@ -1392,12 +1416,25 @@ class AnchorChainer:
         self._call("times", C.byref(f), C.byref(p), C.byref(g))
         return dict(fill_ms=f.value, pick_ms=p.value, gather_ms=g.value)
 
-    def chain_batch_args(self, pool, q_off, q_len, r_off, r_len, strand=None, margin=None):
+    def chain_batch_args(self, pool, q_off, q_len, r_off, r_len, strand=None, margin=None, seq_off=None, seq_len=None):
         """The positional arguments of ChainBatchAligner after `mode` for the chains found: the per-problem arrays q_off, q_len, r_off, r_len
         and strand expanded by chain_problem, and the chains' anchors. With a margin every chain's reference is cut to its candidate window
         (chain_windows): reference positions of the batch's results are then relative to the window, and last_window_shift holds what to add
-        to them, per chain."""
+        to them, per chain. With seq_off and seq_len -- the sequences of a multi-sequence index, in whose frame the anchors are -- r_off and
+        r_len are None and a margin is required: the windows are chain_windows_seqs', last_window_shift leads to positions in the chain's
+        own sequence, and last_window_seq says which one that is."""
         res = self.results()
+        if seq_off is not None or seq_len is not None:
+            if seq_off is None or seq_len is None or r_off is not None or r_len is not None or margin is None:
+                raise ValueError("with seq_off and seq_len, r_off and r_len must be None and a margin is required")
+            per = [np.asarray(x) for x in (q_off, q_len)] + ([] if strand is None else [np.asarray(strand)])
+            if any(len(x) != self.n for x in per):
+                raise ValueError("q_off, q_len and strand must have one entry per problem")
+            cp = res["chain_problem"]
+            r_off_w, r_len_w, r_anchor_w, self.last_window_seq, self.last_window_shift = chain_windows_seqs(
+                per[1][cp], res["anchor_first"], res["q_anchor"], res["r_anchor"], res["anchor_len"], margin, seq_off, seq_len)
+            return (pool, per[0][cp], per[1][cp], r_off_w, r_len_w, res["anchor_first"], res["q_anchor"], r_anchor_w, res["anchor_len"],
+                    None if strand is None else per[2][cp])
         per = [np.asarray(x) for x in (q_off, q_len, r_off, r_len)] + ([] if strand is None else [np.asarray(strand)])
         if any(len(x) != self.n for x in per):
             raise ValueError("q_off, q_len, r_off, r_len and strand must have one entry per problem")
@@ -1434,6 +1471,42 @@ def chain_windows(q_len, r_off, r_len, anchor_first, q_anchor, r_anchor, anchor_
     return r_off_w, r_len_w, r_anchor_w, r_off_w - a[1]
 
 
+def chain_windows_seqs(q_len, anchor_first, q_anchor, r_anchor, anchor_len, margin: int, seq_off, seq_len):
+    """Candidate windows of chains whose anchors are in the frame of a multi-sequence index (ba_chain_windows_seqs; INTEGRATION.md, "Several
+    sequences"): a window stays inside the sequence that holds the chain's first anchor -> (r_off, r_len, r_anchor, seq, shift):
+    ChainBatchAligner's arguments (r_off in the pool, through seq_off), per chain its sequence, and what to add to the reference positions
+    of the batch's results to get positions in that sequence. Host only."""
+    a = [np.ascontiguousarray(x, dtype=t) for x, t in zip((q_len, anchor_first, q_anchor, r_anchor, anchor_len), (np.uint32, np.uint64, np.uint32, np.uint32, np.uint32))]
+    so, sl = np.ascontiguousarray(seq_off, dtype=np.uint64), np.ascontiguousarray(seq_len, dtype=np.uint32)
+    n = len(a[0])
+    if len(a[1]) != n + 1:
+        raise ValueError("q_len must have one entry per chain, anchor_first one more")
+    if any(len(x) != len(a[2]) for x in a[3:]) or len(a[2]) != int(a[1][-1]):
+        raise ValueError("q_anchor, r_anchor and anchor_len must have one entry per anchor (anchor_first[-1] of them)")
+    if len(so) != len(sl):
+        raise ValueError("seq_off and seq_len must have one entry per sequence")
+    r_off_w, r_len_w, r_anchor_w = np.zeros(n, np.uint64), np.zeros(n, np.uint32), np.zeros(len(a[2]), np.uint32)
+    seq, shift = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    if lib().ba_chain_windows_seqs(*_ptrs(a), n, margin, *_ptrs([so, sl]), len(sl), *_ptrs([r_off_w, r_len_w, r_anchor_w, seq, shift])):
+        raise RuntimeError(last_error())
+    return r_off_w, r_len_w, r_anchor_w, seq, shift
+
+
+def locate(seq_len, r_start, r_end) -> dict:
+    """From the frame of a multi-sequence index to its sequences (ba_ref_locate; INTEGRATION.md, "Several sequences"): for the closed
+    intervals [r_start, r_end] -> dict: seq (the last non-empty sequence that starts at or before r_start), local_start, local_end
+    (positions in it) and crosses (the interval reaches into the next sequence). Host only."""
+    sl = np.ascontiguousarray(seq_len, dtype=np.uint32)
+    a, b = np.ascontiguousarray(r_start, dtype=np.uint32), np.ascontiguousarray(r_end, dtype=np.uint32)
+    if len(a) != len(b):
+        raise ValueError("r_start and r_end must have one entry per interval")
+    n = len(a)
+    out = dict(seq=np.zeros(n, np.uint32), local_start=np.zeros(n, np.uint32), local_end=np.zeros(n, np.uint32), crosses=np.zeros(n, np.uint8))
+    if lib().ba_ref_locate(*_ptrs([sl]), len(sl), *_ptrs([a, b]), n, *_ptrs(out.values())):
+        raise RuntimeError(last_error())
+    return out
+
+
 class RefIndex:
     """The sketch of one reference, built once on the device (ba_ref_index_*; INTEGRATION.md, "Reference index"): the (w, k)-minimizers of
     `ref` on strand 0 under the rule of "Seeding", sorted by (code, position), with a prefix table. Seeder.indexed(index, ...) seeds reads
@@ -1444,9 +1517,53 @@ class RefIndex:
         n = len(r)
         if n == 0:   # (an empty array has no address)
             r = np.zeros(1, np.uint8)
+        self._multi = False
         self._h = lib().ba_ref_index_create(k, w, r.ctypes.data, n)
         if not self._h:
             raise RuntimeError(last_error())
+
+    @classmethod
+    def from_sequences(cls, k: int, w: int, pool, seq_off=None, seq_len=None):
+        """The index of several reference sequences (ba_ref_index_create_multi; INTEGRATION.md, "Several sequences"): sequence s is
+        pool[seq_off[s]:+seq_len[s]], or pool is a list of bytes, which is packed here. The sequences lie end to end in the index's
+        frame, sequences() says where; no k-mer and no window holds bytes of two. Seeders made from it give hits in that frame, and
+        AnchorChainer.from_seeder on them keeps every chain inside one sequence."""
+        if seq_off is None and seq_len is None:
+            seqs = [bytes(s) for s in pool]
+            seq_len = np.array([len(s) for s in seqs], np.uint32)
+            seq_off = np.cumsum(seq_len, dtype=np.uint64) - seq_len
+            pool = np.frombuffer(b"".join(seqs), np.uint8)
+        elif seq_off is None or seq_len is None:
+            raise ValueError("seq_off and seq_len go together")
+        p = np.ascontiguousarray(np.frombuffer(pool, np.uint8) if isinstance(pool, (bytes, bytearray)) else pool, dtype=np.uint8)
+        so, sl = np.ascontiguousarray(seq_off, dtype=np.uint64), np.ascontiguousarray(seq_len, dtype=np.uint32)
+        if len(so) != len(sl):
+            raise ValueError("seq_off and seq_len must have one entry per sequence")
+        if len(sl) and int((so + sl)[sl > 0].max(initial=0)) > len(p):
+            raise ValueError("a sequence ends beyond the pool")
+        if len(p) == 0:   # (an empty array has no address)
+            p = np.zeros(1, np.uint8)
+        self = cls.__new__(cls)
+        self._h = None
+        self._multi = True
+        h = lib().ba_ref_index_create_multi(k, w, p.ctypes.data, so.ctypes.data, sl.ctypes.data, len(sl))
+        if not h:
+            raise RuntimeError(last_error())
+        self._h = h
+        self.seq_off, self.seq_len = so, sl
+        return self
+
+    def sequences(self) -> np.ndarray:
+        """seq_start: where the index's sequences start in its frame, and where the last one ends (one entry more than sequences)."""
+        n = C.c_uint64()
+        self._call("sequences", C.byref(n), None)
+        start = np.zeros(n.value + 1, np.uint64)
+        self._call("sequences", C.byref(n), start.ctypes.data)
+        return start
+
+    def locate(self, r_start, r_end) -> dict:
+        """locate() with this index's sequences."""
+        return locate(np.diff(self.sequences()), r_start, r_end)
 
     def _call(self, name, *args):
         if getattr(lib(), f"ba_ref_index_{name}")(self._h, *args):
@@ -1532,6 +1649,7 @@ class Seeder:
         c = index.counts()
         self.params = SeedingParamsC(c["k"], c["w"], max_occ)
         self.max_ref_occ = max_ref_occ
+        self.seq_start = index.sequences() if getattr(index, "_multi", False) else None   # (what a chainer over the hits is bounded by)
         return self
 
     def reload_indexed(self, pool, q_off, q_len, strand=None) -> None:

@@ -469,7 +469,7 @@ BaChaining* ba_chaining_create_seeded(const struct BaChainingParams* params, BaS
  * index"). The index holds the (w, k)-minimizer sketch of ref[0 .. ref_len) on strand 0 under the rule of "Seeding", as keys
  * code << 32 | pos in ascending order with a prefix table over the top min(2k, 20) bits of the code; the bytes are not kept. k is 4 .. 16, w
  * is 1 .. 64, ref is not NULL and ref_len is below 2^31 - 16: checked before the device is touched. A reference shorter than k has no entries.
- * Several reference sequences: concatenate them with N spacers. */
+ * Several reference sequences: ba_ref_index_create_multi, below. */
 typedef struct BaRefIndex BaRefIndex;
 BaRefIndex* ba_ref_index_create(uint32_t k, uint32_t w, const uint8_t* ref, uint64_t ref_len);
 /* Any pointer may be NULL. longest_run: the largest number of entries that share one code (what max_ref_occ is compared with). */
@@ -499,6 +499,41 @@ int ba_seeding_reload_indexed(BaSeeding* batch, const uint8_t* pool, const uint6
 int ba_chain_windows(const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len, const uint64_t* anchor_first, const uint32_t* q_anchor,
                      const uint32_t* r_anchor, const uint32_t* anchor_len, uintptr_t n_chains, uint32_t margin, uint64_t* r_off_out,
                      uint32_t* r_len_out, uint32_t* r_anchor_out);
+
+/* ---- several reference sequences in one index ("Several sequences": the rule, normative). The sequences
+ * seq[s] = pool[seq_off[s] .. + seq_len[s]) are laid end to end without a spacer: seq_start[0] = 0, seq_start[s + 1] = seq_start[s] +
+ * seq_len[s]. Every reference position downstream -- index entries, r_hit, chain anchors -- is in that frame until it is located. The
+ * entries are the union of the entries of every sequence alone, shifted by its start: no k-mer and no window holds bytes of two sequences;
+ * longest_run, the prefix table and max_ref_occ count over all of them together. n_seqs is 1 .. 2^20, empty sequences are legal, and
+ * seq_start[n_seqs] stays below 2^31 - 16; every argument is checked before the device is touched. One sequence gives the index of
+ * ba_ref_index_create bit for bit. The pool need not hold the sequences contiguously or in order. A seeder made from such an index
+ * (ba_seeding_create_indexed, unchanged) carries the sequence table, and ba_chaining_create_seeded on it makes a bounded chainer. */
+BaRefIndex* ba_ref_index_create_multi(uint32_t k, uint32_t w, const uint8_t* pool, const uint64_t* seq_off, const uint32_t* seq_len, uintptr_t n_seqs);
+/* Any index's sequences: their number and where they start in the index's frame (n_seqs + 1 entries, the last one the end; or NULL). An
+ * index made by ba_ref_index_create has one, from 0 to ref_len. */
+int ba_ref_index_sequences(BaRefIndex* index, uint64_t* n_seqs, uint64_t* seq_start);
+/* ba_chaining_create for anchors in the frame of a sequence table (n_seqs + 1 ascending entries from 0, n_seqs 1 .. 2^20, the last below
+ * 2^31 - 16): the fill admits a predecessor j of anchor i only if it ends behind the start of the sequence that holds i -- the last
+ * non-empty sequence that starts at or before i's reference position --, so every chain lies in one sequence. Besides ba_chaining_create's
+ * checks, every anchor must end at or before the end of the sequence that holds its start; the message names the problem and the anchor.
+ * ba_chaining_reload keeps the table and the check. With one sequence the chains are ba_chaining_create's. */
+BaChaining* ba_chaining_create_bounded(const struct BaChainingParams* params, const uint64_t* anchor_first, const uint32_t* q_anchor,
+                                       const uint32_t* r_anchor, const uint32_t* anchor_len, uintptr_t n_problems, const uint64_t* seq_start,
+                                       uintptr_t n_seqs);
+/* Candidate windows of chains in an index's frame (host only). Chain c lies in sequence s, the one that holds its first anchor, from
+ * S = seq_start[s] to E = seq_start[s + 1]; in 64-bit arithmetic lo = ra0 - min(ra0 - S, qa0 + margin), hi = re + min(E - re, (q_len - qe) +
+ * margin); r_off_out = seq_off[s] + (lo - S), r_len_out = hi - lo, r_anchor_out = r_anchor - lo, seq_of_chain = s and local_shift = lo - S:
+ * what to add to the chain batch's reference positions to get positions in sequence s. A chain without anchors, or with an anchor that
+ * ends beyond E or beyond q_len, is refused with its number. Only seq_off says where a sequence lies in the pool. */
+int ba_chain_windows_seqs(const uint32_t* q_len, const uint64_t* anchor_first, const uint32_t* q_anchor, const uint32_t* r_anchor,
+                          const uint32_t* anchor_len, uintptr_t n_chains, uint32_t margin, const uint64_t* seq_off, const uint32_t* seq_len,
+                          uintptr_t n_seqs, uint64_t* r_off_out, uint32_t* r_len_out, uint32_t* r_anchor_out, uint32_t* seq_of_chain,
+                          uint32_t* local_shift);
+/* From the index's frame to a sequence (host only). For the closed interval [r_start, r_end], seq is the last non-empty sequence that
+ * starts at or before r_start, local_start / local_end are the ends less seq_start[seq], and crosses says r_end > seq_start[seq + 1]: the
+ * interval reaches into the next sequence. A position above seq_start[n_seqs], or r_end < r_start, is refused with the interval's number. */
+int ba_ref_locate(const uint32_t* seq_len, uintptr_t n_seqs, const uint32_t* r_start, const uint32_t* r_end, uintptr_t n, uint32_t* seq,
+                  uint32_t* local_start, uint32_t* local_end, uint8_t* crosses);
 
 /* ---- read-level selection on the device: from candidates in any order -- chains before alignment, alignments after it -- to a mapper's
  * records: which of a read's candidates is primary, which are supplementary or secondary, which are dropped, and the mapping quality of the
