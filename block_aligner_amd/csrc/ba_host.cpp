@@ -3311,6 +3311,7 @@ struct IndexData {   // a reference index on the device (ba_ref_index_*): shared
     // sequences). multi: made by ba_ref_index_create_multi, so chainers over its seeders' hits are bounded by this table.
     std::vector<uint64_t> seq_start;
     bool multi = false;
+    bool canonical = false;   // made by ba_ref_index_create_canonical ("Both strands at once"): the keys are code << 32 | strand << 31 | pos
 };
 struct BaSeeding : StreamOwner {
     BaSeedingParams P{};
@@ -3321,13 +3322,25 @@ struct BaSeeding : StreamOwner {
     std::shared_ptr<const IndexData> index;   // an indexed seeder (ba_seeding_create_indexed): every problem's reference is the index's
     uint32_t max_ref_occ = 0;
     DevBuf hit_key;                           // ... its hits as sort keys, as large as the hit arrays
+    // a both-strand seeder (ba_seeding_create_indexed_both): n_reads reads, each sketched once, and n = 2 n_reads problems. The per-sequence
+    // arrays, seed_cnt and seed_first are the reads' (n_reads), hit_cnt and hit_first the problems'; match_order lists the problems for the
+    // sort of the hits, both of a read together, and cap_n counts reads.
+    bool both = false;
+    uint32_t n_reads = 0;
     float sketch_ms = 0, sort_ms = 0, match_ms = 0;
     bool ran = false;
+    ba::IndexBothParams both_params() const {
+        ba::IndexBothParams bp{};
+        bp.lp = lookup_params();
+        bp.lp.n = n_reads; bp.lp.order = sort_order.as<uint32_t>();   // (the lookup goes read by read)
+        bp.q_len = seq_len.as<uint32_t>();
+        return bp;
+    }
     ba::IndexLookupParams lookup_params() const {
         ba::IndexLookupParams lp{};
         lp.n = n; lp.k = P.k; lp.max_occ = P.max_occ; lp.max_ref_occ = max_ref_occ;
         lp.prefix_bits = index->prefix_bits; lp.n_entries = (uint32_t)index->n_entries;
-        lp.order = sort_order.as<uint32_t>(); lp.seed_first = seed_first.as<uint64_t>(); lp.q_key = q_key.as<uint64_t>();
+        lp.order = both ? match_order.as<uint32_t>() : sort_order.as<uint32_t>(); lp.seed_first = seed_first.as<uint64_t>(); lp.q_key = q_key.as<uint64_t>();
         lp.key = index->key.as<uint64_t>(); lp.table = index->table.as<uint32_t>();
         lp.hit_cnt = hit_cnt.as<uint32_t>(); lp.hit_first = hit_first.as<uint64_t>(); lp.hit_key = hit_key.as<uint64_t>();
         lp.q_hit = q_hit.as<uint32_t>(); lp.r_hit = r_hit.as<uint32_t>(); lp.hit_len = hit_len.as<uint32_t>();
@@ -3335,9 +3348,9 @@ struct BaSeeding : StreamOwner {
     }
     ba::SeedingParams params() const {
         ba::SeedingParams sp{};
-        sp.n = n; sp.k = P.k; sp.w = P.w; sp.max_occ = P.max_occ;
+        sp.n = both ? n_reads : n; sp.k = P.k; sp.w = P.w; sp.max_occ = P.max_occ;
         sp.pool = raw.as<uint8_t>(); sp.seq_off = seq_off.as<uint64_t>(); sp.seq_len = seq_len.as<uint32_t>(); sp.seq_rc = seq_rc.as<uint8_t>();
-        sp.seq_order = seq_order.as<uint32_t>(); sp.sort_order = sort_order.as<uint32_t>(); sp.match_order = match_order.as<uint32_t>();
+        sp.seq_order = both ? sort_order.as<uint32_t>() : seq_order.as<uint32_t>(); sp.sort_order = sort_order.as<uint32_t>(); sp.match_order = match_order.as<uint32_t>();
         sp.counter = counter.as<uint32_t>(); sp.seed_cnt = seed_cnt.as<uint32_t>(); sp.seed_first = seed_first.as<uint64_t>();
         sp.seed_pos = seed_pos.as<uint32_t>(); sp.seed_code = seed_code.as<uint32_t>(); sp.q_key = q_key.as<uint64_t>();
         sp.hit_cnt = hit_cnt.as<uint32_t>(); sp.hit_first = hit_first.as<uint64_t>();
@@ -3417,16 +3430,19 @@ BaSeeding* ba_seeding_create(const BaSeedingParams* params, const uint8_t* pool,
 int ba_seeding_reload(BaSeeding* e, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len,
                       const uint8_t* strand, uintptr_t n_problems) {
     if (!e) return fail("null batch");
+    if (e->both) return fail("ba_seeding_reload: the seeder takes its reads on both strands at once; call ba_seeding_reload_indexed_both");
     if (e->index) return fail("ba_seeding_reload: the seeder was created over a reference index; call ba_seeding_reload_indexed");
     SeedingSet S;
     if (seeding_plan(pool, q_off, q_len, r_off, r_len, strand, n_problems, S)) return 1;
     HIP_TRY(hipSetDevice(e->device));
     return seeding_load(e, S, n_problems, false);
 }
+static int seeding_run_both(BaSeeding* e, float* kernel_ms);
 int ba_seeding_run(BaSeeding* e, float* kernel_ms) {
     if (!e) return fail("null batch");
     if (!e->n) return fail("no problems loaded (the last reload failed)");
     HIP_TRY(hipSetDevice(e->device));
+    if (e->both) return seeding_run_both(e, kernel_ms);
     e->ran = false; e->sketch_ms = e->sort_ms = e->match_ms = 0; e->n_q_seeds = e->n_seeds = e->n_hits = 0;
     const uint32_t n = e->n;
     ba::SeedingParams sp = e->params();
@@ -3524,8 +3540,12 @@ int ba_seeding_sketch(BaSeeding* e, uint64_t* q_seed_first, uint32_t* q_seed_pos
     if (!e) return fail("null batch");
     if (!e->ran) return fail("ba_seeding_run has not been called");
     HIP_TRY(hipSetDevice(e->device));
-    const size_t n = e->n, nq = e->n_q_seeds, nr = e->n_seeds - e->n_q_seeds;
+    const size_t n = e->both ? e->n_reads : e->n, nq = e->n_q_seeds, nr = e->n_seeds - e->n_q_seeds;
     if (d2h(e->seed_first, q_seed_first, n + 1) || d2h(e->seed_pos, q_seed_pos, nq) || d2h(e->seed_code, q_seed_code, nq)) return 1;
+    if (e->both) {   // per read, and no reference entries: seed_first holds the reads' offsets only
+        if (r_seed_first) std::fill(r_seed_first, r_seed_first + n + 1, 0ull);
+        return 0;
+    }
     if (r_seed_first) {   // (the references' entries lie behind the queries')
         HIP_TRY(hipMemcpy(r_seed_first, e->seed_first.as<uint64_t>() + n, (n + 1) * 8, hipMemcpyDeviceToHost));
         for (size_t p = 0; p <= n; p++) r_seed_first[p] -= nq;
@@ -3539,6 +3559,12 @@ int ba_seeding_times(BaSeeding* e, float* sketch_ms, float* sort_ms, float* matc
     if (sketch_ms) *sketch_ms = e->sketch_ms;
     if (sort_ms) *sort_ms = e->sort_ms;
     if (match_ms) *match_ms = e->match_ms;
+    return 0;
+}
+int ba_seeding_problems(BaSeeding* e, uint64_t* n_problems, uint64_t* n_reads) {
+    if (!e) return fail("null batch");
+    if (n_problems) *n_problems = e->n;
+    if (n_reads) *n_reads = e->both ? e->n_reads : e->n;
     return 0;
 }
 void ba_seeding_destroy(BaSeeding* e) { delete e; }
@@ -3844,7 +3870,7 @@ static int index_build(BaRefIndex* x, const uint8_t* ref) {
     // the sketch: count, scan, emit
     HIP_TRY(hipMemsetAsync(counter.p, 0, 4, T.stream));
     HIP_TRY(hipEventRecord(T.ev[0], T.stream));
-    HIP_TRY(ba_launch_index_sketch(T.stream, &ip, 0));
+    HIP_TRY(D.canonical ? ba_launch_both_index_sketch(T.stream, &ip, 0) : ba_launch_index_sketch(T.stream, &ip, 0));
     HIP_TRY(ba_launch_offsets(T.stream, ip.span_cnt, span_first.as<uint64_t>(), ip.n_spans));
     HIP_TRY(hipEventRecord(T.ev[1], T.stream));
     HIP_TRY(hipStreamSynchronize(T.stream));
@@ -3854,7 +3880,7 @@ static int index_build(BaRefIndex* x, const uint8_t* ref) {
     ip.n_entries = (uint32_t)total; ip.unsorted = unsorted.as<uint64_t>(); ip.key = D.key.as<uint64_t>();
     HIP_TRY(hipMemsetAsync(counter.p, 0, 4, T.stream));
     HIP_TRY(hipEventRecord(T.ev[2], T.stream));
-    HIP_TRY(ba_launch_index_sketch(T.stream, &ip, 1));
+    HIP_TRY(D.canonical ? ba_launch_both_index_sketch(T.stream, &ip, 1) : ba_launch_index_sketch(T.stream, &ip, 1));
     HIP_TRY(hipEventRecord(T.ev[3], T.stream));
     // the sort of the keys (a code has 2k bits above the position's 32), the table
     if (total) {
@@ -3889,7 +3915,7 @@ BaRefIndex* ba_ref_index_create(uint32_t k, uint32_t w, const uint8_t* ref, uint
     return x.release();
 }
 // Several sequences in one index ("Several sequences"): pool[seq_off[s] .. + seq_len[s]), laid end to end without a spacer.
-BaRefIndex* ba_ref_index_create_multi(uint32_t k, uint32_t w, const uint8_t* pool, const uint64_t* seq_off, const uint32_t* seq_len, uintptr_t n_seqs) {
+static BaRefIndex* index_create_seqs(uint32_t k, uint32_t w, const uint8_t* pool, const uint64_t* seq_off, const uint32_t* seq_len, uintptr_t n_seqs, bool canonical) {
     if (seeding_check_params(BaSeedingParams{k, w, 1})) return nullptr;   // every argument is checked before the device is touched
     if (!pool || !seq_off || !seq_len) { fail("null argument"); return nullptr; }
     std::vector<uint64_t> start;
@@ -3901,10 +3927,22 @@ BaRefIndex* ba_ref_index_create_multi(uint32_t k, uint32_t w, const uint8_t* poo
     std::unique_ptr<BaRefIndex> x(new BaRefIndex);
     x->d = std::make_shared<IndexData>();
     x->d->device = g_device; x->d->k = k; x->d->w = w; x->d->ref_len = start[n_seqs];
-    x->d->seq_start = std::move(start); x->d->multi = true;
+    x->d->seq_start = std::move(start); x->d->multi = true; x->d->canonical = canonical;
     x->d->prefix_bits = 2u * k < ba::INDEX_MAX_PREFIX_BITS ? 2u * k : ba::INDEX_MAX_PREFIX_BITS;
     if (index_build(x.get(), bytes.data())) return nullptr;
     return x.release();
+}
+BaRefIndex* ba_ref_index_create_multi(uint32_t k, uint32_t w, const uint8_t* pool, const uint64_t* seq_off, const uint32_t* seq_len, uintptr_t n_seqs) {
+    return index_create_seqs(k, w, pool, seq_off, seq_len, n_seqs, false);
+}
+// The same over canonical k-mers ("Both strands at once"): what ba_seeding_create_indexed_both seeds against.
+BaRefIndex* ba_ref_index_create_canonical(uint32_t k, uint32_t w, const uint8_t* pool, const uint64_t* seq_off, const uint32_t* seq_len, uintptr_t n_seqs) {
+    return index_create_seqs(k, w, pool, seq_off, seq_len, n_seqs, true);
+}
+int ba_ref_index_is_canonical(BaRefIndex* x, int* flag) {
+    if (!x) return fail("null index");
+    if (flag) *flag = x->d->canonical ? 1 : 0;
+    return 0;
 }
 int ba_ref_index_sequences(BaRefIndex* x, uint64_t* n_seqs, uint64_t* seq_start) {
     if (!x) return fail("null index");
@@ -3949,6 +3987,7 @@ BaSeeding* ba_seeding_create_indexed(BaRefIndex* x, uint32_t max_occ, uint32_t m
     if (max_ref_occ < 1) { fail("seeding: max_ref_occ must be at least 1"); return nullptr; }
     if (seeding_plan(pool, q_off, q_len, nullptr, nullptr, strand, n_problems, S, true)) return nullptr;   // (empty references: the sketch skips them)
     if (!x) { fail("null index"); return nullptr; }
+    if (x->d->canonical) { fail("ba_seeding_create_indexed: the index is canonical and holds both strands; call ba_seeding_create_indexed_both"); return nullptr; }
     if (hipSetDevice(x->d->device) != hipSuccess) { fail("hipSetDevice failed"); return nullptr; }   // the seeder lives on the index's device
     std::unique_ptr<BaSeeding> e(new BaSeeding);
     e->device = x->d->device; e->P = BaSeedingParams{x->d->k, x->d->w, max_occ};
@@ -3958,11 +3997,135 @@ BaSeeding* ba_seeding_create_indexed(BaRefIndex* x, uint32_t max_occ, uint32_t m
 }
 int ba_seeding_reload_indexed(BaSeeding* e, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint8_t* strand, uintptr_t n_problems) {
     if (!e) return fail("null batch");
+    if (e->both) return fail("ba_seeding_reload_indexed: the seeder takes its reads on both strands at once; call ba_seeding_reload_indexed_both");
     if (!e->index) return fail("ba_seeding_reload_indexed: the seeder was created without a reference index; call ba_seeding_reload");
     SeedingSet S;
     if (seeding_plan(pool, q_off, q_len, nullptr, nullptr, strand, n_problems, S, true)) return 1;
     HIP_TRY(hipSetDevice(e->device));
     return seeding_load(e, S, n_problems, false);
+}
+
+// ------------------------------------------------------------------ both strands at once (ba_seeding_*_indexed_both)
+// n reads against a canonical index, each sketched once: read r on strand s is problem 2 r + s of a BaSeeding with 2 n problems
+// (ba_index_both.hip; the rule: INTEGRATION.md, "Both strands at once"). The sort of a read's keys and the sort of the hits are the
+// indexed seeder's kernels.
+static int seeding_plan_both(const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, size_t n_reads, SeedingSet& S) {
+    if (!pool || !q_off || !q_len) return fail("null argument");
+    if (n_reads == 0 || n_reads > (1u << 27)) return fail("a both-strand seeding batch must hold between 1 and 2^27 reads");
+    for (size_t r = 0; r < n_reads; r++)   // (seeding_plan checks the lengths again: this loop is here for the wording, reads and not problems)
+        if (q_len[r] >= ba::SEEDING_MAX_LEN) return fail("read %zu: the read (%u bytes) must be shorter than 2^31 - 16 bytes", r, q_len[r]);
+    if (seeding_plan(pool, q_off, q_len, nullptr, nullptr, nullptr, n_reads, S, true)) return 1;
+    S.match_order.resize(2 * n_reads);   // the problems for the sort of the hits: both of a read, the reads longest first
+    for (size_t t = 0; t < n_reads; t++) { S.match_order[2 * t] = 2 * S.sort_order[t]; S.match_order[2 * t + 1] = 2 * S.sort_order[t] + 1; }
+    return 0;
+}
+static int seeding_load_both(BaSeeding* e, const SeedingSet& S, size_t n, bool create) {
+    if (create) {
+        e->cap_n = n; e->cap_raw = S.bytes;
+        if (e->raw.alloc(S.bytes) || e->seq_off.alloc(n * 8) || e->seq_len.alloc(n * 4) || e->sort_order.alloc(n * 4) || e->match_order.alloc(2 * n * 4) ||
+            e->counter.alloc(4) || e->seed_cnt.alloc(n * 4) || e->seed_first.alloc((n + 1) * 8) || e->hit_cnt.alloc(2 * n * 4) ||
+            e->hit_first.alloc((2 * n + 1) * 8)) return 1;
+    } else {
+        if (n > e->cap_n) return fail("reload: %zu reads exceed the batch's capacity of %llu", n, (unsigned long long)e->cap_n);
+        if (S.bytes > e->cap_raw) return fail("reload: %llu sequence bytes exceed the batch's capacity of %llu", (unsigned long long)S.bytes, (unsigned long long)e->cap_raw);
+    }
+    e->n = 0; e->n_reads = 0; e->ran = false;   // (a failure from here on leaves no problems loaded)
+    if ((S.bytes && h2d(e->raw, S.lo, S.bytes)) || h2d(e->seq_off, S.off.data(), n) || h2d(e->seq_len, S.len.data(), n) ||
+        h2d(e->sort_order, S.sort_order.data(), n) || h2d(e->match_order, S.match_order.data(), 2 * n)) return 1;
+    e->n_reads = (uint32_t)n; e->n = (uint32_t)(2 * n);
+    return 0;
+}
+BaSeeding* ba_seeding_create_indexed_both(BaRefIndex* x, uint32_t max_occ, uint32_t max_ref_occ, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len,
+                                          uintptr_t n_reads) {
+    SeedingSet S;   // (the index is looked at last, as in ba_seeding_create_indexed)
+    if (max_occ < 1) { fail("seeding: max_occ must be at least 1"); return nullptr; }
+    if (max_ref_occ < 1) { fail("seeding: max_ref_occ must be at least 1"); return nullptr; }
+    if (seeding_plan_both(pool, q_off, q_len, n_reads, S)) return nullptr;
+    if (!x) { fail("null index"); return nullptr; }
+    if (!x->d->canonical) {
+        fail("ba_seeding_create_indexed_both: the index is not canonical (ba_ref_index_create_canonical makes one); call ba_seeding_create_indexed");
+        return nullptr;
+    }
+    if (hipSetDevice(x->d->device) != hipSuccess) { fail("hipSetDevice failed"); return nullptr; }   // the seeder lives on the index's device
+    std::unique_ptr<BaSeeding> e(new BaSeeding);
+    e->device = x->d->device; e->P = BaSeedingParams{x->d->k, x->d->w, max_occ};
+    e->index = x->d; e->max_ref_occ = max_ref_occ; e->both = true;
+    if (e->open(9) || seeding_load_both(e.get(), S, n_reads, true)) return nullptr;
+    return e.release();
+}
+int ba_seeding_reload_indexed_both(BaSeeding* e, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, uintptr_t n_reads) {
+    if (!e) return fail("null batch");
+    if (!e->both) return fail("ba_seeding_reload_indexed_both: the seeder takes one strand per problem; call %s", e->index ? "ba_seeding_reload_indexed" : "ba_seeding_reload");
+    SeedingSet S;
+    if (seeding_plan_both(pool, q_off, q_len, n_reads, S)) return 1;
+    HIP_TRY(hipSetDevice(e->device));
+    return seeding_load_both(e, S, n_reads, false);
+}
+// ba_seeding_run of a both-strand seeder: the reads' sketch (count, scan, emit), the sort of every read's keys, the lookup (count, scan
+// over the 2 n problems, emit) and the sort of every problem's hits. The times are reported as ba_seeding_run reports an indexed seeder's.
+static int seeding_run_both(BaSeeding* e, float* kernel_ms) {
+    e->ran = false; e->sketch_ms = e->sort_ms = e->match_ms = 0; e->n_q_seeds = e->n_seeds = e->n_hits = 0;
+    const uint32_t nr = e->n_reads, n = e->n;
+    ba::SeedingParams sp = e->params();
+    HIP_TRY(hipMemsetAsync(e->counter.p, 0, 4, e->stream));
+    HIP_TRY(hipEventRecord(e->ev[0], e->stream));
+    HIP_TRY(ba_launch_both_read_sketch(e->stream, &sp, 0));
+    HIP_TRY(ba_launch_offsets(e->stream, sp.seed_cnt, e->seed_first.as<uint64_t>(), nr));
+    HIP_TRY(hipEventRecord(e->ev[1], e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    uint64_t seeds = 0;
+    HIP_TRY(hipMemcpy(&seeds, e->seed_first.as<uint64_t>() + nr, 8, hipMemcpyDeviceToHost));
+    if (seeds > e->seeds_cap || !e->seed_pos.p) {   // (grow, never shrink)
+        if (e->seed_pos.alloc(seeds * 4) || e->seed_code.alloc(seeds * 4) || e->q_key.alloc(seeds * 8)) return 1;
+        e->seeds_cap = e->q_seeds_cap = seeds;
+    }
+    sp = e->params();
+    HIP_TRY(hipMemsetAsync(e->counter.p, 0, 4, e->stream));
+    HIP_TRY(hipEventRecord(e->ev[2], e->stream));
+    HIP_TRY(ba_launch_both_read_sketch(e->stream, &sp, 1));
+    HIP_TRY(hipEventRecord(e->ev[3], e->stream));
+    HIP_TRY(ba_launch_seeding_sort(e->stream, &sp));   // (sp.n: the reads; the order of the keys puts a code's strand-0 entries first)
+    HIP_TRY(hipEventRecord(e->ev[4], e->stream));
+    ba::IndexBothParams bp = e->both_params();
+    HIP_TRY(ba_launch_both_lookup(e->stream, &bp, 0));
+    HIP_TRY(ba_launch_offsets(e->stream, bp.lp.hit_cnt, e->hit_first.as<uint64_t>(), n));
+    HIP_TRY(hipEventRecord(e->ev[5], e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    uint64_t hits = 0;
+    HIP_TRY(hipMemcpy(&hits, e->hit_first.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost));
+    if (hits > ba::SEEDING_MAX_HITS) {   // no emit: name the first problem that does not fit what the ones before it left
+        std::vector<uint32_t> per(n);
+        HIP_TRY(hipMemcpy(per.data(), e->hit_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        uint64_t left = ba::SEEDING_MAX_HITS;
+        size_t p = 0;
+        while (p + 1 < n && per[p] <= left) left -= per[p++];
+        return fail("seeding: the set has more than 2^28 hits: read %zu on strand %zu alone has %s%u, with %llu left after the problems before it; lower "
+                    "max_occ (it is %u) or max_ref_occ (it is %u), or seed fewer reads at once", p / 2, p % 2, per[p] == 0xffffffffu ? "at least " : "", per[p],
+                    (unsigned long long)left, e->P.max_occ, e->max_ref_occ);
+    }
+    if (hits > e->hits_cap || !e->q_hit.p) {
+        if (e->q_hit.alloc(hits * 4) || e->r_hit.alloc(hits * 4) || e->hit_len.alloc(hits * 4) || e->hit_key.alloc(hits * 8)) return 1;
+        e->hits_cap = hits;
+    }
+    bp = e->both_params();
+    HIP_TRY(hipEventRecord(e->ev[6], e->stream));
+    HIP_TRY(ba_launch_both_lookup(e->stream, &bp, 1));
+    HIP_TRY(hipEventRecord(e->ev[7], e->stream));
+    const ba::IndexLookupParams lp = e->lookup_params();   // (n: the 2 n problems; order: both problems of a read, the reads longest first)
+    HIP_TRY(ba_launch_index_hit_sort(e->stream, &lp));
+    HIP_TRY(hipEventRecord(e->ev[8], e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    float a = 0, b = 0;
+    if (e->elapsed(0, 1, &a) || e->elapsed(2, 3, &b)) return 1;
+    e->sketch_ms = a + b;
+    if (e->elapsed(3, 4, &a) || e->elapsed(7, 8, &b)) return 1;
+    e->sort_ms = a + b;
+    if (e->elapsed(4, 5, &a) || e->elapsed(6, 7, &b)) return 1;
+    e->match_ms = a + b;
+    e->n_q_seeds = e->n_seeds = seeds; e->n_hits = hits;
+    e->ran = true;
+    if (kernel_ms) *kernel_ms = e->sketch_ms + e->sort_ms + e->match_ms;
+    return 0;
 }
 
 // Candidate windows for chain batches: the reference stretch a chain can reach, so that a chain batch over a long reference packs no

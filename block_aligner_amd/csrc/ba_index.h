@@ -45,4 +45,17 @@ struct IndexLookupParams {
     uint32_t* q_hit; uint32_t* r_hit; uint32_t* hit_len;   // per hit, by problem and within it by (r_hit, q_hit)
 };
 
+// A canonical index ("Both strands at once"; ba_index_both.hip): IndexParams as they are, the keys code << 32 | strand << 31 | pos with
+// code the smaller of a k-mer's and its reverse complement's, strand: which one that was.
+constexpr uint64_t INDEX_STRAND_BIT = 1ull << 31;
+constexpr uint32_t INDEX_POS_MASK = 0x7fffffffu;
+
+// The lookup of n reads in a canonical index, each on both strands at once: read r on strand s is problem 2 r + s. lp.n, lp.order and
+// lp.seed_first are per read (n, n, n + 1), lp.q_key holds the strand bit as the index's keys do, and lp.hit_cnt and lp.hit_first are per
+// problem (2 n, 2 n + 1). The sort of the hits is k_index_hit_sort's, over the 2 n problems.
+struct IndexBothParams {
+    IndexLookupParams lp;
+    const uint32_t* q_len;           // per read: its bytes (a minus-strand hit's q_hit is q_len - k - pos)
+};
+
 }  // namespace ba

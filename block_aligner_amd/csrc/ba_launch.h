@@ -92,6 +92,10 @@ hipError_t ba_launch_index_table(hipStream_t s, const ba::IndexParams* ip);
 hipError_t ba_launch_index_lookup(hipStream_t s, const ba::IndexLookupParams* lp, int emit);
 hipError_t ba_launch_index_hit_sort(hipStream_t s, const ba::IndexLookupParams* lp);
 hipError_t ba_launch_index_sort(hipStream_t s, const uint64_t* in, uint64_t* out, uint32_t n, uint32_t bits, void* temp, size_t* temp_bytes);
+// ba_index_both.hip: a canonical index's sketch, and the sketch and the lookup of reads taken on both strands at once
+hipError_t ba_launch_both_index_sketch(hipStream_t s, const ba::IndexParams* ip, int emit);
+hipError_t ba_launch_both_read_sketch(hipStream_t s, const ba::SeedingParams* sp, int emit);
+hipError_t ba_launch_both_lookup(hipStream_t s, const ba::IndexBothParams* bp, int emit);
 // ba_select.hip (scatter 0: the count pass, 1: the scatter pass)
 hipError_t ba_launch_select_group(hipStream_t s, const ba::SelectParams* sp, int scatter);
 hipError_t ba_launch_select_mark(hipStream_t s, const ba::SelectParams* sp);

@@ -99,6 +99,53 @@ template <class Two> __device__ __forceinline__ uint64_t chunk_minimizer(SketchL
         }
     return m;
 }
+// The same for canonical k-mers ("Both strands at once"): a staged k-mer also has a strand bit. At k = 16 a code fills all
+// 32 bits, so the bit has a place of its own.
+struct CanonLds {   // one wave's
+    uint64_t key[CHUNK_KEYS];
+    uint32_t code[CHUNK_KEYS];
+    uint8_t two[CHUNK_BYTES];
+    uint8_t strand[CHUNK_KEYS];
+};
+// kmer_key for the canonical code min(f, g) of the k-mer's forward code f and its reverse complement's g; strand: g < f. A palindrome
+// (f == g) is invalid. The strand bit takes no part in the order key: of equal hashes the leftmost position wins, whatever the strands.
+__device__ __forceinline__ uint64_t kmer_key_canon(const CanonLds& L, uint32_t j, uint32_t pos, uint32_t k, uint32_t nk, uint32_t& code, uint32_t& strand) {
+    uint32_t bad = 0, f = 0;
+    for (uint32_t x = 0; x < k; x++) {
+        const uint32_t v = L.two[j + x];
+        bad |= v;
+        f = f << 2 | (v & 3u);
+    }
+    // g from f, once per k-mer: the complement is ~f; reversing all 32 bits brings the bases into reverse order at the top, each with its
+    // two bits swapped, which the masks undo; the shift drops what ~ made of the bits above f's 2k
+    uint32_t g = __brev(~f);
+    g = ((g >> 1) & 0x55555555u) | ((g & 0x55555555u) << 1);
+    g >>= 32u - 2u * k;
+    strand = g < f ? 1u : 0u;
+    code = strand ? g : f;
+    return pos < nk && !(bad & 4u) && f != g ? (uint64_t)hash32(code) << 32 | pos : NO_KEY;
+}
+// chunk_minimizer over canonical k-mers: L.code and L.strand hold what the selected position's entry is made of.
+template <class Two> __device__ __forceinline__ uint64_t chunk_minimizer_canon(CanonLds& L, Two two, uint32_t s0, uint32_t end, uint32_t k, uint32_t w,
+                                                                                uint32_t nk, uint32_t lane) {
+    const uint32_t need_keys = 63u + w, need_bytes = need_keys + k - 1u;
+    for (uint32_t b = lane; b < need_bytes; b += 64u) L.two[b] = (uint8_t)two(s0 + b);
+    wave_sync();
+    for (uint32_t j = lane; j < need_keys; j += 64u) {
+        uint32_t code, strand;
+        L.key[j] = kmer_key_canon(L, j, s0 + j, k, nk, code, strand);
+        L.code[j] = code;
+        L.strand[j] = (uint8_t)strand;
+    }
+    wave_sync();
+    uint64_t m = NO_KEY;
+    if (s0 + lane < end)
+        for (uint32_t x = 0; x < w; x++) {
+            const uint64_t c = L.key[lane + x];
+            m = c < m ? c : m;
+        }
+    return m;
+}
 // A window's minimizer is selected when it differs from the window's before it -- the minimizers of consecutive windows never go back --;
 // prev: the minimizer of the window before the chunk, and then of the chunk's last window.
 __device__ __forceinline__ bool chunk_select(uint64_t m, uint64_t& prev, uint32_t lane) {

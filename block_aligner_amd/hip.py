@@ -268,6 +268,13 @@ def lib() -> C.CDLL:
         L.ba_ref_index_create_multi.restype = vp
         L.ba_ref_index_create_multi.argtypes = [u32, u32, vp, vp, vp, sz]
         L.ba_ref_index_sequences.argtypes = [vp, C.POINTER(C.c_uint64), vp]
+        L.ba_ref_index_create_canonical.restype = vp
+        L.ba_ref_index_create_canonical.argtypes = [u32, u32, vp, vp, vp, sz]
+        L.ba_ref_index_is_canonical.argtypes = [vp, C.POINTER(C.c_int)]
+        L.ba_seeding_create_indexed_both.restype = vp
+        L.ba_seeding_create_indexed_both.argtypes = [vp, u32, u32, vp, vp, vp, sz]
+        L.ba_seeding_reload_indexed_both.argtypes = [vp, vp, vp, vp, sz]
+        L.ba_seeding_problems.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.ba_chaining_create_bounded.restype = vp
         L.ba_chaining_create_bounded.argtypes = [C.POINTER(ChainingParamsC), vp, vp, vp, vp, sz, vp, sz]
         L.ba_chain_windows_seqs.argtypes = [vp] * 5 + [sz, u32, vp, vp, sz] + [vp] * 5
@@ -1510,24 +1517,33 @@ def locate(seq_len, r_start, r_end) -> dict:
 class RefIndex:
     """The sketch of one reference, built once on the device (ba_ref_index_*; INTEGRATION.md, "Reference index"): the (w, k)-minimizers of
     `ref` on strand 0 under the rule of "Seeding", sorted by (code, position), with a prefix table. Seeder.indexed(index, ...) seeds reads
-    against all of it. Arguments are checked before the device is touched; the bytes are not kept."""
+    against all of it. Arguments are checked before the device is touched; the bytes are not kept.
 
-    def __init__(self, k: int, w: int, ref):
+    canonical=True makes the index of canonical k-mers (ba_ref_index_create_canonical; INTEGRATION.md, "Both strands at once"), which
+    Seeder.indexed_both seeds against, every read once for both strands: entries() then gives pos with the k-mer's strand in bit 31."""
+
+    def __init__(self, k: int, w: int, ref, canonical: bool = False):
         r = np.ascontiguousarray(np.frombuffer(ref, np.uint8) if isinstance(ref, (bytes, bytearray)) else ref, dtype=np.uint8)
         n = len(r)
         if n == 0:   # (an empty array has no address)
             r = np.zeros(1, np.uint8)
-        self._multi = False
-        self._h = lib().ba_ref_index_create(k, w, r.ctypes.data, n)
+        self.canonical = bool(canonical)
+        if canonical:   # one sequence of a sequence table: chainers over its seeders' hits are bounded by it
+            self._multi = True
+            self.seq_off, self.seq_len = np.zeros(1, np.uint64), np.array([n], np.uint32)
+            self._h = lib().ba_ref_index_create_canonical(k, w, r.ctypes.data, self.seq_off.ctypes.data, self.seq_len.ctypes.data, 1)
+        else:
+            self._multi = False
+            self._h = lib().ba_ref_index_create(k, w, r.ctypes.data, n)
         if not self._h:
             raise RuntimeError(last_error())
 
     @classmethod
-    def from_sequences(cls, k: int, w: int, pool, seq_off=None, seq_len=None):
+    def from_sequences(cls, k: int, w: int, pool, seq_off=None, seq_len=None, canonical: bool = False):
         """The index of several reference sequences (ba_ref_index_create_multi; INTEGRATION.md, "Several sequences"): sequence s is
         pool[seq_off[s]:+seq_len[s]], or pool is a list of bytes, which is packed here. The sequences lie end to end in the index's
         frame, sequences() says where; no k-mer and no window holds bytes of two. Seeders made from it give hits in that frame, and
-        AnchorChainer.from_seeder on them keeps every chain inside one sequence."""
+        AnchorChainer.from_seeder on them keeps every chain inside one sequence. canonical: as for RefIndex()."""
         if seq_off is None and seq_len is None:
             seqs = [bytes(s) for s in pool]
             seq_len = np.array([len(s) for s in seqs], np.uint32)
@@ -1546,7 +1562,9 @@ class RefIndex:
         self = cls.__new__(cls)
         self._h = None
         self._multi = True
-        h = lib().ba_ref_index_create_multi(k, w, p.ctypes.data, so.ctypes.data, sl.ctypes.data, len(sl))
+        self.canonical = bool(canonical)
+        create = lib().ba_ref_index_create_canonical if canonical else lib().ba_ref_index_create_multi
+        h = create(k, w, p.ctypes.data, so.ctypes.data, sl.ctypes.data, len(sl))
         if not h:
             raise RuntimeError(last_error())
         self._h = h
@@ -1576,7 +1594,7 @@ class RefIndex:
         return dict(n_entries=n.value, k=k.value, w=w.value, ref_len=ln.value, longest_run=run.value)
 
     def entries(self):
-        """-> (code, pos): the entries, ascending by (code, pos)."""
+        """-> (code, pos): the entries, ascending by (code, pos). Of a canonical index pos holds the k-mer's strand in bit 31."""
         n = self.counts()["n_entries"]
         code, pos = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
         self._call("entries", code.ctypes.data, pos.ctypes.data)
@@ -1605,7 +1623,7 @@ class Seeder:
 
     run() computes sketches and hits and returns the kernels' time; results() gives the hits of every problem, sorted by (r_hit, q_hit), as
     AnchorChainer takes them; AnchorChainer.from_seeder(..., seeder) chains them where they lie. Seeder.indexed(index, ...) is the same for
-    many reads against the one reference of a RefIndex."""
+    many reads against the one reference of a RefIndex, and Seeder.indexed_both(index, ...) takes every read once for both strands."""
 
     @staticmethod
     def _arrays(pool, q_off, q_len, r_off, r_len, strand):
@@ -1617,7 +1635,7 @@ class Seeder:
 
     def __init__(self, k: int, w: int, max_occ: int, pool, q_off, q_len, r_off, r_len, strand=None):
         a = self._arrays(pool, q_off, q_len, r_off, r_len, strand)
-        self.n = len(a[2])
+        self.n = self.n_reads = len(a[2])   # (n_reads: what ba_seeding_problems reports; it differs from n for indexed_both() only)
         self.params = SeedingParamsC(k, w, max_occ)
         self._counts = None
         self._h = lib().ba_seeding_create(C.byref(self.params), *_ptrs(a), self.n)
@@ -1641,7 +1659,7 @@ class Seeder:
         self = cls.__new__(cls)
         self._h = None
         self._counts = None
-        self.n = len(a[2])
+        self.n = self.n_reads = len(a[2])
         h = lib().ba_seeding_create_indexed(getattr(index, "_h", None), max_occ, max_ref_occ, *_ptrs(a), self.n)
         if not h:
             raise RuntimeError(last_error())
@@ -1652,12 +1670,47 @@ class Seeder:
         self.seq_start = index.sequences() if getattr(index, "_multi", False) else None   # (what a chainer over the hits is bounded by)
         return self
 
+    @classmethod
+    def indexed_both(cls, index: "RefIndex", max_occ: int, max_ref_occ: int, pool, q_off, q_len):
+        """A seeder that takes every read once and seeds it on both strands against a canonical RefIndex (ba_seeding_create_indexed_both;
+        INTEGRATION.md, "Both strands at once"): read r = pool[q_off[r]:+q_len[r]] on strand s is problem 2 r + s. n is the number of
+        problems, n_reads that of the reads, and read and strand are the per-problem arrays that chain_batch_args, Selector.from_chain_batch
+        and paf_columns take (q_off[seeder.read], q_len[seeder.read], seeder.strand). A code that more than max_occ of a read's entries or more
+        than max_ref_occ of the index's have, both strands together, gives no hits. sketch() is per read, with the strand in bit 31 of q_pos."""
+        a = cls._arrays_indexed(pool, q_off, q_len, None)[:3]
+        self = cls.__new__(cls)
+        self._h = None
+        self._counts = None
+        self.n_reads = len(a[2])
+        h = lib().ba_seeding_create_indexed_both(getattr(index, "_h", None), max_occ, max_ref_occ, *_ptrs(a), self.n_reads)
+        if not h:
+            raise RuntimeError(last_error())
+        self._h = h
+        c = index.counts()
+        self.params = SeedingParamsC(c["k"], c["w"], max_occ)
+        self.max_ref_occ = max_ref_occ
+        self.seq_start = index.sequences()   # (what a chainer over the hits is bounded by)
+        self._set_reads(self.n_reads)
+        return self
+
+    def _set_reads(self, n_reads: int) -> None:
+        self.n_reads, self.n = n_reads, 2 * n_reads
+        self.read = np.repeat(np.arange(n_reads, dtype=np.uint32), 2)
+        self.strand = np.tile(np.array([0, 1], np.uint8), n_reads)
+
+    def reload_indexed_both(self, pool, q_off, q_len) -> None:
+        """reload() for a seeder made by indexed_both() (ba_seeding_reload_indexed_both): no more reads and no more bytes than at first."""
+        a = self._arrays_indexed(pool, q_off, q_len, None)[:3]
+        self._counts = None
+        self._call("reload_indexed_both", *_ptrs(a), len(a[2]))
+        self._set_reads(len(a[2]))
+
     def reload_indexed(self, pool, q_off, q_len, strand=None) -> None:
         """reload() for a seeder made by indexed() (ba_seeding_reload_indexed)."""
         a = self._arrays_indexed(pool, q_off, q_len, strand)
         self._counts = None
         self._call("reload_indexed", *_ptrs(a), len(a[2]))
-        self.n = len(a[2])
+        self.n = self.n_reads = len(a[2])
 
     def _call(self, name, *args):
         if getattr(lib(), f"ba_seeding_{name}")(self._h, *args):
@@ -1668,7 +1721,7 @@ class Seeder:
         a = self._arrays(pool, q_off, q_len, r_off, r_len, strand)
         self._counts = None
         self._call("reload", *_ptrs(a), len(a[2]))
-        self.n = len(a[2])
+        self.n = self.n_reads = len(a[2])
 
     def run(self) -> float:
         ms = C.c_float()
@@ -1701,8 +1754,9 @@ class Seeder:
         """After run(): the raw sketches in position order -> dict: q_first, q_pos, q_code, r_first, r_pos, r_code (first: one entry per
         problem and one more)."""
         c = self.counts()
-        out = dict(q_first=np.zeros(self.n + 1, np.uint64), q_pos=np.zeros(c["n_q_seeds"], np.uint32), q_code=np.zeros(c["n_q_seeds"], np.uint32),
-                   r_first=np.zeros(self.n + 1, np.uint64), r_pos=np.zeros(c["n_r_seeds"], np.uint32), r_code=np.zeros(c["n_r_seeds"], np.uint32))
+        n = self.n_reads   # (a both-strand seeder's sketches are per read; for every other seeder a problem is a read)
+        out = dict(q_first=np.zeros(n + 1, np.uint64), q_pos=np.zeros(c["n_q_seeds"], np.uint32), q_code=np.zeros(c["n_q_seeds"], np.uint32),
+                   r_first=np.zeros(n + 1, np.uint64), r_pos=np.zeros(c["n_r_seeds"], np.uint32), r_code=np.zeros(c["n_r_seeds"], np.uint32))
         self._call("sketch", *_ptrs(out.values()))
         return out
 

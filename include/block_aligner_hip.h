@@ -535,6 +535,33 @@ int ba_chain_windows_seqs(const uint32_t* q_len, const uint64_t* anchor_first, c
 int ba_ref_locate(const uint32_t* seq_len, uintptr_t n_seqs, const uint32_t* r_start, const uint32_t* r_end, uintptr_t n, uint32_t* seq,
                   uint32_t* local_start, uint32_t* local_end, uint8_t* crosses);
 
+/* ---- both strands of a read at once: a canonical index ("Both strands at once": the rule, normative). The index of
+ * ba_ref_index_create_multi -- the same arguments, checks and messages, the same sequence table, no k-mer and no window across a junction --
+ * over canonical k-mers: a k-mer's code is the smaller of its own and its reverse complement's, its strand bit says whether that was the
+ * reverse complement's, and a k-mer equal to its reverse complement is never selected. A key is code << 32 | strand << 31 | pos, so
+ * ba_ref_index_entries on such an index returns pos with the strand in bit 31 (pos & 0x7fffffff is the position, pos >> 31 the strand),
+ * ascending by (code, strand, position); longest_run counts a code's entries of both strands together. counts, sequences, times, destroy
+ * and ba_ref_locate work unchanged. ba_seeding_create_indexed refuses such an index, and names ba_seeding_create_indexed_both. */
+BaRefIndex* ba_ref_index_create_canonical(uint32_t k, uint32_t w, const uint8_t* pool, const uint64_t* seq_off, const uint32_t* seq_len, uintptr_t n_seqs);
+/* flag (or NULL): 1 for an index made by ba_ref_index_create_canonical, 0 for any other. */
+int ba_ref_index_is_canonical(BaRefIndex* index, int* flag);
+/* A seeder over n_reads reads (1 .. 2^27), each taken once: read r = pool[q_off[r] .. + q_len[r]) on strand s is problem 2 r + s of a
+ * BaSeeding with 2 n_reads problems, and its hits are in the frame of ba_seeding_create_indexed's problem with that strand: r_hit in the
+ * index's frame, q_hit in the oriented read. A read entry whose code more than max_occ of the read's entries have, or more than max_ref_occ
+ * of the index's, gives no hits: both strands count together. The index must be canonical; a plain one is refused, and the message names
+ * ba_seeding_create_indexed. The other arguments are checked before the index is looked at and before the device is touched. run, counts
+ * (hits_per_problem: 2 n_reads entries), results (hit_first: 2 n_reads + 1), times, destroy and ba_chaining_create_seeded -- a chainer over
+ * the 2 n_reads problems, bounded by the index's sequences -- work on the handle. ba_seeding_sketch gives per-read arrays: q_seed_first has
+ * n_reads + 1 entries, q_seed_pos is in the read's own frame with the k-mer's strand in bit 31, q_seed_code is canonical, and there are no
+ * reference entries (r_seed_first: n_reads + 1 zeros). More than 2^28 hits over all problems are refused with the read and the strand.
+ * ba_seeding_reload and ba_seeding_reload_indexed refuse the handle, and ba_seeding_reload_indexed_both refuses any other seeder. */
+BaSeeding* ba_seeding_create_indexed_both(BaRefIndex* index, uint32_t max_occ, uint32_t max_ref_occ, const uint8_t* pool, const uint64_t* q_off,
+                                          const uint32_t* q_len, uintptr_t n_reads);
+int ba_seeding_reload_indexed_both(BaSeeding* batch, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, uintptr_t n_reads);
+/* Any seeder's number of problems and of reads (either pointer may be NULL): 2 n_reads and n_reads for a both-strand seeder, n_problems
+ * twice for any other. */
+int ba_seeding_problems(BaSeeding* batch, uint64_t* n_problems, uint64_t* n_reads);
+
 /* ---- read-level selection on the device: from candidates in any order -- chains before alignment, alignments after it -- to a mapper's
  * records: which of a read's candidates is primary, which are supplementary or secondary, which are dropped, and the mapping quality of the
  * heads ("Selecting a read's alignments": the rule, normative; all integer arithmetic, products in 64 bits).

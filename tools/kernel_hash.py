@@ -5,7 +5,7 @@ import hashlib
 import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FILES = ["ba_params.h", "ba_device.hpp", "ba_driver.hpp", "ba_quad.hpp", "ba_multi.hpp", "ba_small.hpp", "ba_kernels.hip", "ba_launch.h", "ba_extend.h", "ba_extend.hip", "ba_chain.h", "ba_chain.hip", "ba_chaining.h", "ba_chaining.hip", "ba_seeding.h", "ba_seeding.hip", "ba_seed_device.hpp", "ba_select.h", "ba_select.hip", "ba_index.h", "ba_index.hip", "ba_index_sort.hip", "ba_stats.h", "ba_stats.hip", "ba_text.h", "ba_text.hip", "ba_exact.h", "ba_exact.hip", "ba_host.cpp", "Makefile"]
+FILES = ["ba_params.h", "ba_device.hpp", "ba_driver.hpp", "ba_quad.hpp", "ba_multi.hpp", "ba_small.hpp", "ba_kernels.hip", "ba_launch.h", "ba_extend.h", "ba_extend.hip", "ba_chain.h", "ba_chain.hip", "ba_chaining.h", "ba_chaining.hip", "ba_seeding.h", "ba_seeding.hip", "ba_seed_device.hpp", "ba_select.h", "ba_select.hip", "ba_index.h", "ba_index.hip", "ba_index_both.hip", "ba_index_sort.hip", "ba_stats.h", "ba_stats.hip", "ba_text.h", "ba_text.hip", "ba_exact.h", "ba_exact.hip", "ba_host.cpp", "Makefile"]
 
 
 def kernel_hash() -> str:
