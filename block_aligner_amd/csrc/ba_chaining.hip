@@ -84,11 +84,7 @@ template <bool BOUNDED> __global__ void __launch_bounds__(256) k_chaining_fill(c
     int32_t* rf = (int32_t*)(rr + cp.ring);
     const uint32_t mw = (uint32_t)cp.match_w, dc = (uint32_t)cp.drift_cost, sc = (uint32_t)cp.skip_cost;
     for (;;) {
-        __builtin_amdgcn_wave_barrier();   // (a convergence point, as in ba_exact.hip's exact_records)
-        uint32_t k = 0;
-        if (lane == 0) k = atomicAdd(cp.counter, 1u);
-        __builtin_amdgcn_wave_barrier();
-        k = (uint32_t)__builtin_amdgcn_readfirstlane((int)k);
+        const uint32_t k = ba::seed::next_work(cp.counter, lane);
         if (k >= cp.n) break;
         const uint32_t p = cp.order[k];
         const uint64_t a0 = cp.anchor_first[p];

@@ -3296,10 +3296,18 @@ void ba_chaining_destroy(BaChaining* e) { delete e; }
 // ------------------------------------------------------------------ minimizer seeding (ba_seeding_*)
 // From the bytes of a problem to its raw hits, in the order ba_chaining_create demands (ba_seeding.hip; the rule: INTEGRATION.md,
 // "Seeding"). The host checks the arguments, orders sequences and problems longest first and sizes the buffers between the passes; the
-// sketch, the sort and the match are the device's.
+// sketch, the sort and the match are the device's. The three kinds of seeder -- problems with a reference each, problems against a
+// reference index, reads against a canonical index on both strands at once (the two sections on the index, below) -- are one BaSeeding,
+// loaded by seeding_load and run by ba_seeding_run: a kind is a set's counts, its kernels and the wording of two messages.
 struct SeedingSet {   // a checked set of problems: the extent of its sequences in the caller's pool, the per-sequence arrays, the orders
     const uint8_t* lo = nullptr; uint64_t bytes = 0;
-    std::vector<uint64_t> off; std::vector<uint32_t> len; std::vector<uint8_t> rc;   // 2n: the queries, then the references
+    // the sequences that are sketched (the queries, then the references; a both-strand set: the reads), the queries whose keys are sorted,
+    // the entries of match_order, the problems; what a reload that holds too many of them calls them
+    size_t n_seqs = 0, n_sort = 0, n_match = 0, n_problems = 0;
+    const char* nouns = "problems";
+    std::vector<uint64_t> off; std::vector<uint32_t> len; std::vector<uint8_t> rc;   // n_seqs each; rc: empty when no sequence has a strand
+    // seq_order: n_seqs, and empty when the sequences are the queries, which sort_order lists. match_order: the problems for the match, or
+    // against an index for the sort of the hits
     std::vector<uint32_t> seq_order, sort_order, match_order;
 };
 struct IndexData {   // a reference index on the device (ba_ref_index_*): shared by the index and the seeders made from it, freed with the last
@@ -3315,7 +3323,7 @@ struct IndexData {   // a reference index on the device (ba_ref_index_*): shared
 };
 struct BaSeeding : StreamOwner {
     BaSeedingParams P{};
-    uint32_t n = 0;
+    uint32_t n = 0, n_seqs = 0, n_reads = 0;   // the problems, the sequences that are sketched, the queries (the counts of the loaded SeedingSet)
     uint64_t cap_n = 0, cap_raw = 0, seeds_cap = 0, q_seeds_cap = 0, hits_cap = 0, n_q_seeds = 0, n_seeds = 0, n_hits = 0;
     DevBuf raw, seq_off, seq_len, seq_rc, seq_order, sort_order, match_order, counter, seed_cnt, seed_first, seed_pos, seed_code, q_key, hit_cnt, hit_first,
            q_hit, r_hit, hit_len;
@@ -3323,16 +3331,15 @@ struct BaSeeding : StreamOwner {
     uint32_t max_ref_occ = 0;
     DevBuf hit_key;                           // ... its hits as sort keys, as large as the hit arrays
     // a both-strand seeder (ba_seeding_create_indexed_both): n_reads reads, each sketched once, and n = 2 n_reads problems. The per-sequence
-    // arrays, seed_cnt and seed_first are the reads' (n_reads), hit_cnt and hit_first the problems'; match_order lists the problems for the
-    // sort of the hits, both of a read together, and cap_n counts reads.
+    // arrays, seed_cnt and seed_first are the reads' (n_reads), hit_cnt and hit_first the problems'; seq_order is a view of sort_order,
+    // match_order lists both problems of a read together, and cap_n counts reads.
     bool both = false;
-    uint32_t n_reads = 0;
     float sketch_ms = 0, sort_ms = 0, match_ms = 0;
     bool ran = false;
     ba::IndexBothParams both_params() const {
         ba::IndexBothParams bp{};
         bp.lp = lookup_params();
-        bp.lp.n = n_reads; bp.lp.order = sort_order.as<uint32_t>();   // (the lookup goes read by read)
+        bp.lp.n = n_reads; bp.lp.order = sort_order.as<uint32_t>();   // (the lookup goes read by read, the sort of the hits problem by problem)
         bp.q_len = seq_len.as<uint32_t>();
         return bp;
     }
@@ -3340,7 +3347,7 @@ struct BaSeeding : StreamOwner {
         ba::IndexLookupParams lp{};
         lp.n = n; lp.k = P.k; lp.max_occ = P.max_occ; lp.max_ref_occ = max_ref_occ;
         lp.prefix_bits = index->prefix_bits; lp.n_entries = (uint32_t)index->n_entries;
-        lp.order = both ? match_order.as<uint32_t>() : sort_order.as<uint32_t>(); lp.seed_first = seed_first.as<uint64_t>(); lp.q_key = q_key.as<uint64_t>();
+        lp.order = match_order.as<uint32_t>(); lp.seed_first = seed_first.as<uint64_t>(); lp.q_key = q_key.as<uint64_t>();
         lp.key = index->key.as<uint64_t>(); lp.table = index->table.as<uint32_t>();
         lp.hit_cnt = hit_cnt.as<uint32_t>(); lp.hit_first = hit_first.as<uint64_t>(); lp.hit_key = hit_key.as<uint64_t>();
         lp.q_hit = q_hit.as<uint32_t>(); lp.r_hit = r_hit.as<uint32_t>(); lp.hit_len = hit_len.as<uint32_t>();
@@ -3348,9 +3355,9 @@ struct BaSeeding : StreamOwner {
     }
     ba::SeedingParams params() const {
         ba::SeedingParams sp{};
-        sp.n = both ? n_reads : n; sp.k = P.k; sp.w = P.w; sp.max_occ = P.max_occ;
+        sp.n = n_reads; sp.k = P.k; sp.w = P.w; sp.max_occ = P.max_occ;
         sp.pool = raw.as<uint8_t>(); sp.seq_off = seq_off.as<uint64_t>(); sp.seq_len = seq_len.as<uint32_t>(); sp.seq_rc = seq_rc.as<uint8_t>();
-        sp.seq_order = both ? sort_order.as<uint32_t>() : seq_order.as<uint32_t>(); sp.sort_order = sort_order.as<uint32_t>(); sp.match_order = match_order.as<uint32_t>();
+        sp.seq_order = seq_order.as<uint32_t>(); sp.sort_order = sort_order.as<uint32_t>(); sp.match_order = match_order.as<uint32_t>();
         sp.counter = counter.as<uint32_t>(); sp.seed_cnt = seed_cnt.as<uint32_t>(); sp.seed_first = seed_first.as<uint64_t>();
         sp.seed_pos = seed_pos.as<uint32_t>(); sp.seed_code = seed_code.as<uint32_t>(); sp.q_key = q_key.as<uint64_t>();
         sp.hit_cnt = hit_cnt.as<uint32_t>(); sp.hit_first = hit_first.as<uint64_t>();
@@ -3371,6 +3378,7 @@ static int seeding_plan(const uint8_t* pool, const uint64_t* q_off, const uint32
     if (!pool || !q_off || !q_len || (!indexed && (!r_off || !r_len))) return fail("null argument");
     if (n == 0 || n > (1u << 28)) return fail("a seeding batch must hold between 1 and 2^28 problems");
     S = SeedingSet();
+    S.n_seqs = 2 * n; S.n_sort = S.n_match = S.n_problems = n;
     S.off.resize(2 * n); S.len.resize(2 * n); S.rc.assign(2 * n, 0);
     const uint8_t* hi = nullptr;
     for (size_t p = 0; p < n; p++) {
@@ -3396,24 +3404,29 @@ static int seeding_plan(const uint8_t* pool, const uint64_t* q_off, const uint32
     };
     by(S.len.data(), S.seq_order, 2 * n);
     by(q_len, S.sort_order, n);
-    by(S.len.data() + n, S.match_order, n);
+    if (indexed) S.match_order = S.sort_order;   // (the lookup and the sort of the hits: longest query first)
+    else by(S.len.data() + n, S.match_order, n);
     return 0;
 }
-static int seeding_load(BaSeeding* e, const SeedingSet& S, size_t n, bool create) {
+// Size the per-sequence and per-problem arrays for the set (create) or admit it to them (a reload), and upload it.
+static int seeding_load(BaSeeding* e, const SeedingSet& S, bool create) {
+    const size_t ns = S.n_seqs, nq = S.n_sort, nm = S.n_match, np = S.n_problems;
     if (create) {
-        e->cap_n = n; e->cap_raw = S.bytes;
-        if (e->raw.alloc(S.bytes) || e->seq_off.alloc(2 * n * 8) || e->seq_len.alloc(2 * n * 4) || e->seq_rc.alloc(2 * n) || e->seq_order.alloc(2 * n * 4) ||
-            e->sort_order.alloc(n * 4) || e->match_order.alloc(n * 4) || e->counter.alloc(4) || e->seed_cnt.alloc(2 * n * 4) ||
-            e->seed_first.alloc((2 * n + 1) * 8) || e->hit_cnt.alloc(n * 4) || e->hit_first.alloc((n + 1) * 8)) return 1;
+        e->cap_n = nq; e->cap_raw = S.bytes;
+        if (e->raw.alloc(S.bytes) || e->seq_off.alloc(ns * 8) || e->seq_len.alloc(ns * 4) || (!S.rc.empty() && e->seq_rc.alloc(ns)) ||
+            e->sort_order.alloc(nq * 4) || e->match_order.alloc(nm * 4) || e->counter.alloc(4) || e->seed_cnt.alloc(ns * 4) ||
+            e->seed_first.alloc((ns + 1) * 8) || e->hit_cnt.alloc(np * 4) || e->hit_first.alloc((np + 1) * 8)) return 1;
+        if (S.seq_order.empty()) e->seq_order.view(e->sort_order.p, nq * 4);
+        else if (e->seq_order.alloc(ns * 4)) return 1;
     } else {
-        if (n > e->cap_n) return fail("reload: %zu problems exceed the batch's capacity of %llu", n, (unsigned long long)e->cap_n);
+        if (nq > e->cap_n) return fail("reload: %zu %s exceed the batch's capacity of %llu", nq, S.nouns, (unsigned long long)e->cap_n);
         if (S.bytes > e->cap_raw) return fail("reload: %llu sequence bytes exceed the batch's capacity of %llu", (unsigned long long)S.bytes, (unsigned long long)e->cap_raw);
     }
-    e->n = 0; e->ran = false;   // (a failure from here on leaves no problems loaded)
-    if ((S.bytes && h2d(e->raw, S.lo, S.bytes)) || h2d(e->seq_off, S.off.data(), 2 * n) || h2d(e->seq_len, S.len.data(), 2 * n) ||
-        h2d(e->seq_rc, S.rc.data(), 2 * n) || h2d(e->seq_order, S.seq_order.data(), 2 * n) || h2d(e->sort_order, S.sort_order.data(), n) ||
-        h2d(e->match_order, S.match_order.data(), n)) return 1;
-    e->n = (uint32_t)n;
+    e->n = e->n_seqs = e->n_reads = 0; e->ran = false;   // (a failure from here on leaves no problems loaded)
+    if ((S.bytes && h2d(e->raw, S.lo, S.bytes)) || h2d(e->seq_off, S.off.data(), ns) || h2d(e->seq_len, S.len.data(), ns) ||
+        (!S.rc.empty() && h2d(e->seq_rc, S.rc.data(), ns)) || (!S.seq_order.empty() && h2d(e->seq_order, S.seq_order.data(), ns)) ||
+        h2d(e->sort_order, S.sort_order.data(), nq) || h2d(e->match_order, S.match_order.data(), nm)) return 1;
+    e->n = (uint32_t)np; e->n_seqs = (uint32_t)ns; e->n_reads = (uint32_t)nq;
     return 0;
 }
 BaSeeding* ba_seeding_create(const BaSeedingParams* params, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off,
@@ -3424,7 +3437,7 @@ BaSeeding* ba_seeding_create(const BaSeedingParams* params, const uint8_t* pool,
     if (ensure_device()) return nullptr;
     std::unique_ptr<BaSeeding> e(new BaSeeding);
     e->device = g_device; e->P = *params;
-    if (e->open(9) || seeding_load(e.get(), S, n_problems, true)) return nullptr;
+    if (e->open(9) || seeding_load(e.get(), S, true)) return nullptr;
     return e.release();
 }
 int ba_seeding_reload(BaSeeding* e, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len,
@@ -3435,27 +3448,53 @@ int ba_seeding_reload(BaSeeding* e, const uint8_t* pool, const uint64_t* q_off, 
     SeedingSet S;
     if (seeding_plan(pool, q_off, q_len, r_off, r_len, strand, n_problems, S)) return 1;
     HIP_TRY(hipSetDevice(e->device));
-    return seeding_load(e, S, n_problems, false);
+    return seeding_load(e, S, false);
 }
-static int seeding_run_both(BaSeeding* e, float* kernel_ms);
+// More than 2^28 hits after the count pass, so no emit: name the first problem that does not fit what the ones before it left.
+static int seeding_over_limit(const BaSeeding* e) {
+    const size_t n = e->n;
+    std::vector<uint32_t> per(n);
+    HIP_TRY(hipMemcpy(per.data(), e->hit_cnt.p, n * 4, hipMemcpyDeviceToHost));
+    uint64_t left = ba::SEEDING_MAX_HITS;
+    size_t p = 0;
+    while (p + 1 < n && per[p] <= left) left -= per[p++];
+    const char* at_least = per[p] == 0xffffffffu ? "at least " : "";
+    if (e->both)
+        return fail("seeding: the set has more than 2^28 hits: read %zu on strand %zu alone has %s%u, with %llu left after the problems before it; lower "
+                    "max_occ (it is %u) or max_ref_occ (it is %u), or seed fewer reads at once", p / 2, p % 2, at_least, per[p], (unsigned long long)left,
+                    e->P.max_occ, e->max_ref_occ);
+    return fail("seeding: the set has more than 2^28 hits: problem %zu alone has %s%u, with %llu left after the problems before it; lower max_occ "
+                "(it is %u) or seed fewer problems at once", p, at_least, per[p], (unsigned long long)left, e->P.max_occ);
+}
+// Every kind of seeder: the sketch (count, scan, emit), the sort of every query's keys, the match (count, scan over the problems, emit)
+// and, against an index, the sort of every problem's hits. What a kind chooses is taken from the seeder here at the top; the events, the
+// two sizings between the passes, the refusal and the times are written once.
 int ba_seeding_run(BaSeeding* e, float* kernel_ms) {
     if (!e) return fail("null batch");
     if (!e->n) return fail("no problems loaded (the last reload failed)");
     HIP_TRY(hipSetDevice(e->device));
-    if (e->both) return seeding_run_both(e, kernel_ms);
     e->ran = false; e->sketch_ms = e->sort_ms = e->match_ms = 0; e->n_q_seeds = e->n_seeds = e->n_hits = 0;
-    const uint32_t n = e->n;
+    const uint32_t n = e->n, n_seqs = e->n_seqs, n_reads = e->n_reads;
+    const bool indexed = (bool)e->index;   // the lookup in the index in place of the match; its emit pass writes sort keys
+    const auto sketch = e->both ? ba_launch_both_read_sketch : ba_launch_seeding_sketch;
     ba::SeedingParams sp = e->params();
+    const auto match = [&](int emit) {   // (the parameters are read at the call: the buffers they name grow between the passes)
+        if (!indexed) return ba_launch_seeding_match(e->stream, &sp, emit);
+        if (e->both) { const ba::IndexBothParams bp = e->both_params(); return ba_launch_both_lookup(e->stream, &bp, emit); }
+        const ba::IndexLookupParams lp = e->lookup_params();
+        return ba_launch_index_lookup(e->stream, &lp, emit);
+    };
     // the sketch: count, scan, emit
     HIP_TRY(hipMemsetAsync(e->counter.p, 0, 4, e->stream));
     HIP_TRY(hipEventRecord(e->ev[0], e->stream));
-    HIP_TRY(ba_launch_seeding_sketch(e->stream, &sp, 0));
-    HIP_TRY(ba_launch_offsets(e->stream, sp.seed_cnt, e->seed_first.as<uint64_t>(), 2 * n));
+    HIP_TRY(sketch(e->stream, &sp, 0));
+    HIP_TRY(ba_launch_offsets(e->stream, sp.seed_cnt, e->seed_first.as<uint64_t>(), n_seqs));
     HIP_TRY(hipEventRecord(e->ev[1], e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     uint64_t q_seeds = 0, seeds = 0;
-    HIP_TRY(hipMemcpy(&q_seeds, e->seed_first.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&seeds, e->seed_first.as<uint64_t>() + 2 * (size_t)n, 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&seeds, e->seed_first.as<uint64_t>() + n_seqs, 8, hipMemcpyDeviceToHost));
+    if (n_seqs == n_reads) q_seeds = seeds;   // (no sequence but the queries)
+    else HIP_TRY(hipMemcpy(&q_seeds, e->seed_first.as<uint64_t>() + n_reads, 8, hipMemcpyDeviceToHost));
     if (seeds > e->seeds_cap || !e->seed_pos.p) {   // (grow, never shrink)
         if (e->seed_pos.alloc(seeds * 4) || e->seed_code.alloc(seeds * 4)) return 1;
         e->seeds_cap = seeds;
@@ -3467,50 +3506,35 @@ int ba_seeding_run(BaSeeding* e, float* kernel_ms) {
     sp = e->params();
     HIP_TRY(hipMemsetAsync(e->counter.p, 0, 4, e->stream));
     HIP_TRY(hipEventRecord(e->ev[2], e->stream));
-    HIP_TRY(ba_launch_seeding_sketch(e->stream, &sp, 1));
+    HIP_TRY(sketch(e->stream, &sp, 1));
     HIP_TRY(hipEventRecord(e->ev[3], e->stream));
-    // the sort of the queries' keys; the match: count, scan
+    // the sort of the queries' keys (a both-strand read's: the order of the keys puts a code's strand-0 entries first); the match: count, scan
     HIP_TRY(ba_launch_seeding_sort(e->stream, &sp));
     HIP_TRY(hipEventRecord(e->ev[4], e->stream));
-    ba::IndexLookupParams lp{};   // an indexed seeder: the lookup in the index in place of the match
-    if (e->index) { lp = e->lookup_params(); HIP_TRY(ba_launch_index_lookup(e->stream, &lp, 0)); }
-    else HIP_TRY(ba_launch_seeding_match(e->stream, &sp, 0));
+    HIP_TRY(match(0));
     HIP_TRY(ba_launch_offsets(e->stream, sp.hit_cnt, e->hit_first.as<uint64_t>(), n));
     HIP_TRY(hipEventRecord(e->ev[5], e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     uint64_t hits = 0;
     HIP_TRY(hipMemcpy(&hits, e->hit_first.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost));
-    if (hits > ba::SEEDING_MAX_HITS) {   // no emit: name the first problem that does not fit what the ones before it left
-        std::vector<uint32_t> per(n);
-        HIP_TRY(hipMemcpy(per.data(), e->hit_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-        uint64_t left = ba::SEEDING_MAX_HITS;
-        size_t p = 0;
-        while (p + 1 < n && per[p] <= left) left -= per[p++];
-        return fail("seeding: the set has more than 2^28 hits: problem %zu alone has %s%u, with %llu left after the problems before it; lower max_occ "
-                    "(it is %u) or seed fewer problems at once", p, per[p] == 0xffffffffu ? "at least " : "", per[p], (unsigned long long)left, e->P.max_occ);
-    }
+    if (hits > ba::SEEDING_MAX_HITS) return seeding_over_limit(e);
     if (hits > e->hits_cap || !e->q_hit.p) {
-        if (e->q_hit.alloc(hits * 4) || e->r_hit.alloc(hits * 4) || e->hit_len.alloc(hits * 4) || (e->index && e->hit_key.alloc(hits * 8))) return 1;
+        if (e->q_hit.alloc(hits * 4) || e->r_hit.alloc(hits * 4) || e->hit_len.alloc(hits * 4) || (indexed && e->hit_key.alloc(hits * 8))) return 1;
         e->hits_cap = hits;
     }
     sp = e->params();
+    // the match: emit; the sort of every problem's keys unpacks them
     HIP_TRY(hipEventRecord(e->ev[6], e->stream));
-    if (e->index) {   // the emit pass writes sort keys; the sort of every problem's keys unpacks them
-        lp = e->lookup_params();
-        HIP_TRY(ba_launch_index_lookup(e->stream, &lp, 1));
-        HIP_TRY(hipEventRecord(e->ev[7], e->stream));
-        HIP_TRY(ba_launch_index_hit_sort(e->stream, &lp));
-    } else {
-        HIP_TRY(ba_launch_seeding_match(e->stream, &sp, 1));
-        HIP_TRY(hipEventRecord(e->ev[7], e->stream));
-    }
+    HIP_TRY(match(1));
+    HIP_TRY(hipEventRecord(e->ev[7], e->stream));
+    if (indexed) { const ba::IndexLookupParams lp = e->lookup_params(); HIP_TRY(ba_launch_index_hit_sort(e->stream, &lp)); }
     HIP_TRY(hipEventRecord(e->ev[8], e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     float a = 0, b = 0;
     if (e->elapsed(0, 1, &a) || e->elapsed(2, 3, &b)) return 1;
     e->sketch_ms = a + b;
-    if (e->elapsed(3, 4, &e->sort_ms)) return 1;
-    if (e->index) { if (e->elapsed(7, 8, &a)) return 1; e->sort_ms += a; }   // the sort of the hits
+    if (e->elapsed(3, 4, &a) || e->elapsed(7, 8, &b)) return 1;
+    e->sort_ms = indexed ? a + b : a;   // ... and the sort of the hits
     if (e->elapsed(4, 5, &a) || e->elapsed(6, 7, &b)) return 1;
     e->match_ms = a + b;
     e->n_q_seeds = q_seeds; e->n_seeds = seeds; e->n_hits = hits;
@@ -3540,7 +3564,7 @@ int ba_seeding_sketch(BaSeeding* e, uint64_t* q_seed_first, uint32_t* q_seed_pos
     if (!e) return fail("null batch");
     if (!e->ran) return fail("ba_seeding_run has not been called");
     HIP_TRY(hipSetDevice(e->device));
-    const size_t n = e->both ? e->n_reads : e->n, nq = e->n_q_seeds, nr = e->n_seeds - e->n_q_seeds;
+    const size_t n = e->n_reads, nq = e->n_q_seeds, nr = e->n_seeds - e->n_q_seeds;
     if (d2h(e->seed_first, q_seed_first, n + 1) || d2h(e->seed_pos, q_seed_pos, nq) || d2h(e->seed_code, q_seed_code, nq)) return 1;
     if (e->both) {   // per read, and no reference entries: seed_first holds the reads' offsets only
         if (r_seed_first) std::fill(r_seed_first, r_seed_first + n + 1, 0ull);
@@ -3564,7 +3588,7 @@ int ba_seeding_times(BaSeeding* e, float* sketch_ms, float* sort_ms, float* matc
 int ba_seeding_problems(BaSeeding* e, uint64_t* n_problems, uint64_t* n_reads) {
     if (!e) return fail("null batch");
     if (n_problems) *n_problems = e->n;
-    if (n_reads) *n_reads = e->both ? e->n_reads : e->n;
+    if (n_reads) *n_reads = e->n_reads;
     return 0;
 }
 void ba_seeding_destroy(BaSeeding* e) { delete e; }
@@ -3901,18 +3925,22 @@ static int index_build(BaRefIndex* x, const uint8_t* ref) {
     x->sketch_ms = a + b;
     return T.elapsed(3, 4, &x->sort_ms) || T.elapsed(4, 5, &x->table_ms);
 }
+// An index over the sequences that start (one entry more than sequences) lays end to end in ref.
+static BaRefIndex* index_create(uint32_t k, uint32_t w, const uint8_t* ref, std::vector<uint64_t> start, bool multi, bool canonical) {
+    if (ensure_device()) return nullptr;
+    std::unique_ptr<BaRefIndex> x(new BaRefIndex);
+    x->d = std::make_shared<IndexData>();
+    x->d->device = g_device; x->d->k = k; x->d->w = w; x->d->ref_len = start.back();
+    x->d->seq_start = std::move(start); x->d->multi = multi; x->d->canonical = canonical;
+    x->d->prefix_bits = 2u * k < ba::INDEX_MAX_PREFIX_BITS ? 2u * k : ba::INDEX_MAX_PREFIX_BITS;
+    if (index_build(x.get(), ref)) return nullptr;
+    return x.release();
+}
 BaRefIndex* ba_ref_index_create(uint32_t k, uint32_t w, const uint8_t* ref, uint64_t ref_len) {
     if (seeding_check_params(BaSeedingParams{k, w, 1})) return nullptr;   // every argument is checked before the device is touched
     if (!ref) { fail("null argument"); return nullptr; }
     if (ref_len >= ba::SEEDING_MAX_LEN) { fail("the reference (%llu bytes) must be shorter than 2^31 - 16 bytes", (unsigned long long)ref_len); return nullptr; }
-    if (ensure_device()) return nullptr;
-    std::unique_ptr<BaRefIndex> x(new BaRefIndex);
-    x->d = std::make_shared<IndexData>();
-    x->d->device = g_device; x->d->k = k; x->d->w = w; x->d->ref_len = ref_len;
-    x->d->seq_start = {0, ref_len};
-    x->d->prefix_bits = 2u * k < ba::INDEX_MAX_PREFIX_BITS ? 2u * k : ba::INDEX_MAX_PREFIX_BITS;
-    if (index_build(x.get(), ref)) return nullptr;
-    return x.release();
+    return index_create(k, w, ref, {0, ref_len}, false, false);   // (one sequence, read where it lies)
 }
 // Several sequences in one index ("Several sequences"): pool[seq_off[s] .. + seq_len[s]), laid end to end without a spacer.
 static BaRefIndex* index_create_seqs(uint32_t k, uint32_t w, const uint8_t* pool, const uint64_t* seq_off, const uint32_t* seq_len, uintptr_t n_seqs, bool canonical) {
@@ -3923,14 +3951,7 @@ static BaRefIndex* index_create_seqs(uint32_t k, uint32_t w, const uint8_t* pool
     std::vector<uint8_t> bytes(start[n_seqs]);   // (one upload, whatever the number of sequences and wherever they lie in the pool)
     for (size_t s = 0; s < n_seqs; s++)
         if (seq_len[s]) memcpy(bytes.data() + start[s], pool + seq_off[s], seq_len[s]);
-    if (ensure_device()) return nullptr;
-    std::unique_ptr<BaRefIndex> x(new BaRefIndex);
-    x->d = std::make_shared<IndexData>();
-    x->d->device = g_device; x->d->k = k; x->d->w = w; x->d->ref_len = start[n_seqs];
-    x->d->seq_start = std::move(start); x->d->multi = true; x->d->canonical = canonical;
-    x->d->prefix_bits = 2u * k < ba::INDEX_MAX_PREFIX_BITS ? 2u * k : ba::INDEX_MAX_PREFIX_BITS;
-    if (index_build(x.get(), bytes.data())) return nullptr;
-    return x.release();
+    return index_create(k, w, bytes.data(), std::move(start), true, canonical);
 }
 BaRefIndex* ba_ref_index_create_multi(uint32_t k, uint32_t w, const uint8_t* pool, const uint64_t* seq_off, const uint32_t* seq_len, uintptr_t n_seqs) {
     return index_create_seqs(k, w, pool, seq_off, seq_len, n_seqs, false);
@@ -3992,7 +4013,7 @@ BaSeeding* ba_seeding_create_indexed(BaRefIndex* x, uint32_t max_occ, uint32_t m
     std::unique_ptr<BaSeeding> e(new BaSeeding);
     e->device = x->d->device; e->P = BaSeedingParams{x->d->k, x->d->w, max_occ};
     e->index = x->d; e->max_ref_occ = max_ref_occ;
-    if (e->open(9) || seeding_load(e.get(), S, n_problems, true)) return nullptr;
+    if (e->open(9) || seeding_load(e.get(), S, true)) return nullptr;
     return e.release();
 }
 int ba_seeding_reload_indexed(BaSeeding* e, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, const uint8_t* strand, uintptr_t n_problems) {
@@ -4002,37 +4023,24 @@ int ba_seeding_reload_indexed(BaSeeding* e, const uint8_t* pool, const uint64_t*
     SeedingSet S;
     if (seeding_plan(pool, q_off, q_len, nullptr, nullptr, strand, n_problems, S, true)) return 1;
     HIP_TRY(hipSetDevice(e->device));
-    return seeding_load(e, S, n_problems, false);
+    return seeding_load(e, S, false);
 }
 
 // ------------------------------------------------------------------ both strands at once (ba_seeding_*_indexed_both)
 // n reads against a canonical index, each sketched once: read r on strand s is problem 2 r + s of a BaSeeding with 2 n problems
-// (ba_index_both.hip; the rule: INTEGRATION.md, "Both strands at once"). The sort of a read's keys and the sort of the hits are the
-// indexed seeder's kernels.
+// (ba_index_both.hip; the rule: INTEGRATION.md, "Both strands at once"). Such a seeder is a set with other counts (seeding_plan_both) and
+// two kernels of its own; seeding_load loads it and ba_seeding_run runs it, in the seeding section above.
 static int seeding_plan_both(const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, size_t n_reads, SeedingSet& S) {
     if (!pool || !q_off || !q_len) return fail("null argument");
     if (n_reads == 0 || n_reads > (1u << 27)) return fail("a both-strand seeding batch must hold between 1 and 2^27 reads");
     for (size_t r = 0; r < n_reads; r++)   // (seeding_plan checks the lengths again: this loop is here for the wording, reads and not problems)
         if (q_len[r] >= ba::SEEDING_MAX_LEN) return fail("read %zu: the read (%u bytes) must be shorter than 2^31 - 16 bytes", r, q_len[r]);
     if (seeding_plan(pool, q_off, q_len, nullptr, nullptr, nullptr, n_reads, S, true)) return 1;
+    // the reads are all that is sketched, in the order of the sort, and none has a strand; two problems each
+    S.n_seqs = n_reads; S.n_match = S.n_problems = 2 * n_reads; S.nouns = "reads";
+    S.off.resize(n_reads); S.len.resize(n_reads); S.rc.clear(); S.seq_order.clear();
     S.match_order.resize(2 * n_reads);   // the problems for the sort of the hits: both of a read, the reads longest first
     for (size_t t = 0; t < n_reads; t++) { S.match_order[2 * t] = 2 * S.sort_order[t]; S.match_order[2 * t + 1] = 2 * S.sort_order[t] + 1; }
-    return 0;
-}
-static int seeding_load_both(BaSeeding* e, const SeedingSet& S, size_t n, bool create) {
-    if (create) {
-        e->cap_n = n; e->cap_raw = S.bytes;
-        if (e->raw.alloc(S.bytes) || e->seq_off.alloc(n * 8) || e->seq_len.alloc(n * 4) || e->sort_order.alloc(n * 4) || e->match_order.alloc(2 * n * 4) ||
-            e->counter.alloc(4) || e->seed_cnt.alloc(n * 4) || e->seed_first.alloc((n + 1) * 8) || e->hit_cnt.alloc(2 * n * 4) ||
-            e->hit_first.alloc((2 * n + 1) * 8)) return 1;
-    } else {
-        if (n > e->cap_n) return fail("reload: %zu reads exceed the batch's capacity of %llu", n, (unsigned long long)e->cap_n);
-        if (S.bytes > e->cap_raw) return fail("reload: %llu sequence bytes exceed the batch's capacity of %llu", (unsigned long long)S.bytes, (unsigned long long)e->cap_raw);
-    }
-    e->n = 0; e->n_reads = 0; e->ran = false;   // (a failure from here on leaves no problems loaded)
-    if ((S.bytes && h2d(e->raw, S.lo, S.bytes)) || h2d(e->seq_off, S.off.data(), n) || h2d(e->seq_len, S.len.data(), n) ||
-        h2d(e->sort_order, S.sort_order.data(), n) || h2d(e->match_order, S.match_order.data(), 2 * n)) return 1;
-    e->n_reads = (uint32_t)n; e->n = (uint32_t)(2 * n);
     return 0;
 }
 BaSeeding* ba_seeding_create_indexed_both(BaRefIndex* x, uint32_t max_occ, uint32_t max_ref_occ, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len,
@@ -4050,7 +4058,7 @@ BaSeeding* ba_seeding_create_indexed_both(BaRefIndex* x, uint32_t max_occ, uint3
     std::unique_ptr<BaSeeding> e(new BaSeeding);
     e->device = x->d->device; e->P = BaSeedingParams{x->d->k, x->d->w, max_occ};
     e->index = x->d; e->max_ref_occ = max_ref_occ; e->both = true;
-    if (e->open(9) || seeding_load_both(e.get(), S, n_reads, true)) return nullptr;
+    if (e->open(9) || seeding_load(e.get(), S, true)) return nullptr;
     return e.release();
 }
 int ba_seeding_reload_indexed_both(BaSeeding* e, const uint8_t* pool, const uint64_t* q_off, const uint32_t* q_len, uintptr_t n_reads) {
@@ -4059,75 +4067,8 @@ int ba_seeding_reload_indexed_both(BaSeeding* e, const uint8_t* pool, const uint
     SeedingSet S;
     if (seeding_plan_both(pool, q_off, q_len, n_reads, S)) return 1;
     HIP_TRY(hipSetDevice(e->device));
-    return seeding_load_both(e, S, n_reads, false);
+    return seeding_load(e, S, false);
 }
-// ba_seeding_run of a both-strand seeder: the reads' sketch (count, scan, emit), the sort of every read's keys, the lookup (count, scan
-// over the 2 n problems, emit) and the sort of every problem's hits. The times are reported as ba_seeding_run reports an indexed seeder's.
-static int seeding_run_both(BaSeeding* e, float* kernel_ms) {
-    e->ran = false; e->sketch_ms = e->sort_ms = e->match_ms = 0; e->n_q_seeds = e->n_seeds = e->n_hits = 0;
-    const uint32_t nr = e->n_reads, n = e->n;
-    ba::SeedingParams sp = e->params();
-    HIP_TRY(hipMemsetAsync(e->counter.p, 0, 4, e->stream));
-    HIP_TRY(hipEventRecord(e->ev[0], e->stream));
-    HIP_TRY(ba_launch_both_read_sketch(e->stream, &sp, 0));
-    HIP_TRY(ba_launch_offsets(e->stream, sp.seed_cnt, e->seed_first.as<uint64_t>(), nr));
-    HIP_TRY(hipEventRecord(e->ev[1], e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    uint64_t seeds = 0;
-    HIP_TRY(hipMemcpy(&seeds, e->seed_first.as<uint64_t>() + nr, 8, hipMemcpyDeviceToHost));
-    if (seeds > e->seeds_cap || !e->seed_pos.p) {   // (grow, never shrink)
-        if (e->seed_pos.alloc(seeds * 4) || e->seed_code.alloc(seeds * 4) || e->q_key.alloc(seeds * 8)) return 1;
-        e->seeds_cap = e->q_seeds_cap = seeds;
-    }
-    sp = e->params();
-    HIP_TRY(hipMemsetAsync(e->counter.p, 0, 4, e->stream));
-    HIP_TRY(hipEventRecord(e->ev[2], e->stream));
-    HIP_TRY(ba_launch_both_read_sketch(e->stream, &sp, 1));
-    HIP_TRY(hipEventRecord(e->ev[3], e->stream));
-    HIP_TRY(ba_launch_seeding_sort(e->stream, &sp));   // (sp.n: the reads; the order of the keys puts a code's strand-0 entries first)
-    HIP_TRY(hipEventRecord(e->ev[4], e->stream));
-    ba::IndexBothParams bp = e->both_params();
-    HIP_TRY(ba_launch_both_lookup(e->stream, &bp, 0));
-    HIP_TRY(ba_launch_offsets(e->stream, bp.lp.hit_cnt, e->hit_first.as<uint64_t>(), n));
-    HIP_TRY(hipEventRecord(e->ev[5], e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    uint64_t hits = 0;
-    HIP_TRY(hipMemcpy(&hits, e->hit_first.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost));
-    if (hits > ba::SEEDING_MAX_HITS) {   // no emit: name the first problem that does not fit what the ones before it left
-        std::vector<uint32_t> per(n);
-        HIP_TRY(hipMemcpy(per.data(), e->hit_cnt.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-        uint64_t left = ba::SEEDING_MAX_HITS;
-        size_t p = 0;
-        while (p + 1 < n && per[p] <= left) left -= per[p++];
-        return fail("seeding: the set has more than 2^28 hits: read %zu on strand %zu alone has %s%u, with %llu left after the problems before it; lower "
-                    "max_occ (it is %u) or max_ref_occ (it is %u), or seed fewer reads at once", p / 2, p % 2, per[p] == 0xffffffffu ? "at least " : "", per[p],
-                    (unsigned long long)left, e->P.max_occ, e->max_ref_occ);
-    }
-    if (hits > e->hits_cap || !e->q_hit.p) {
-        if (e->q_hit.alloc(hits * 4) || e->r_hit.alloc(hits * 4) || e->hit_len.alloc(hits * 4) || e->hit_key.alloc(hits * 8)) return 1;
-        e->hits_cap = hits;
-    }
-    bp = e->both_params();
-    HIP_TRY(hipEventRecord(e->ev[6], e->stream));
-    HIP_TRY(ba_launch_both_lookup(e->stream, &bp, 1));
-    HIP_TRY(hipEventRecord(e->ev[7], e->stream));
-    const ba::IndexLookupParams lp = e->lookup_params();   // (n: the 2 n problems; order: both problems of a read, the reads longest first)
-    HIP_TRY(ba_launch_index_hit_sort(e->stream, &lp));
-    HIP_TRY(hipEventRecord(e->ev[8], e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    float a = 0, b = 0;
-    if (e->elapsed(0, 1, &a) || e->elapsed(2, 3, &b)) return 1;
-    e->sketch_ms = a + b;
-    if (e->elapsed(3, 4, &a) || e->elapsed(7, 8, &b)) return 1;
-    e->sort_ms = a + b;
-    if (e->elapsed(4, 5, &a) || e->elapsed(6, 7, &b)) return 1;
-    e->match_ms = a + b;
-    e->n_q_seeds = e->n_seeds = seeds; e->n_hits = hits;
-    e->ran = true;
-    if (kernel_ms) *kernel_ms = e->sketch_ms + e->sort_ms + e->match_ms;
-    return 0;
-}
-
 // Candidate windows for chain batches: the reference stretch a chain can reach, so that a chain batch over a long reference packs no
 // more than that (host only). All arithmetic is 64-bit.
 int ba_chain_windows(const uint32_t* q_len, const uint64_t* r_off, const uint32_t* r_len, const uint64_t* anchor_first, const uint32_t* q_anchor,

@@ -4,13 +4,11 @@
 // tests/index_ref.py bit for bit. The sort of the index's keys is a library call in a unit of its own (ba_index_sort.hip).
 //
 // k_index_sketch<EMIT>: k_seeding_sketch's count and emit passes for sequences that many waves share. A work item is a span of
-// INDEX_SPAN windows of one sequence, taken from a work counter; within it the wave goes chunk by chunk as k_seeding_sketch does. The one
-// new thing is the seam: a window's minimizer is selected when it differs from the window's before it, so a span that does not start its
-// sequence first computes the minimizer of the window before its first one from the w k-mers under that window -- all ones when none of
-// them is valid, which is also what a sequence's first window compares with. The entries are written as keys code << 32 | pos, in position
-// order. Several sequences ("Several sequences" in INTEGRATION.md) lie end to end in one frame; the host numbers every sequence's spans
-// from seq_span[s], the wave finds its span's sequence by a lower bound over those, and every byte outside that sequence reads as invalid:
-// one reference is the case n_seqs = 1, with the same arithmetic.
+// INDEX_SPAN windows of one sequence, taken from a work counter; within it the wave goes chunk by chunk as k_seeding_sketch does, after
+// the seam: the minimizer of the window before the span. The entries are written as keys code << 32 | pos, in position order. Several
+// sequences ("Several sequences" in INTEGRATION.md) lie end to end in one frame, and every byte outside a span's sequence reads as
+// invalid. The body is index_sketch<false, EMIT> of ba_seed_device.hpp, which says all this in full; the canonical index
+// (ba_index_both.hip) runs the same body over canonical k-mers.
 // k_index_table: one lower bound per prefix over the sorted keys, and the longest run of one code, by a search from every run's start.
 // k_index_lookup<EMIT>: one wave per problem, longest query first, 64 of the query's sorted keys per step, a count pass, a scan and an emit
 // pass. Every lane finds how often its code occurs in the query (k_seeding_match's two searches) and, through the prefix table, in the
@@ -27,52 +25,12 @@ using namespace ba::seed;
 namespace {
 
 constexpr uint32_t SKETCH_WAVES = 4, LOOKUP_WAVES = 4, SORT_THREADS = 1024, TABLE_THREADS = 256;
-static_assert(ba::INDEX_SPAN % 64u == 0u, "a span is whole chunks");
 
 }  // namespace
 
 template <bool EMIT> __global__ void __launch_bounds__(64 * SKETCH_WAVES) k_index_sketch(const ba::IndexParams ip) {
     __shared__ SketchLds lds[SKETCH_WAVES];
-    const uint32_t lane = threadIdx.x & 63u;
-    SketchLds& L = lds[threadIdx.x >> 6];
-    const uint32_t k = ip.k, w = ip.w;
-    for (;;) {
-        __builtin_amdgcn_wave_barrier();   // (a convergence point, as in k_seeding_sketch)
-        uint32_t t = 0;
-        if (lane == 0) t = atomicAdd(ip.counter, 1u);
-        __builtin_amdgcn_wave_barrier();
-        t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
-        if (t >= ip.n_spans) break;
-        // the span's sequence: the last one whose first span is t or before it (a sequence without a k-mer has no span, so it is never that)
-        const uint32_t sq = lower_bound(ip.seq_span, ip.n_seqs + 1u, (uint64_t)t + 1u) - 1u;
-        const uint32_t S = (uint32_t)ip.seq_start[sq], E = (uint32_t)ip.seq_start[sq + 1u];   // its bytes, in the index's frame (E - S >= k)
-        const uint32_t nk = E - k + 1u;   // one past its last k-mer; positions, k-mers and windows are numbered in the index's frame from here on
-        const uint32_t nw = nk - S > w ? nk - w + 1u : S + 1u;   // one past its last window
-        const auto two = [&](uint32_t i) { return i >= S && i < E ? two_bits(ip.ref[i], false) : 4u; };   // (no byte of a neighbour)
-        const uint32_t first = S + (t - (uint32_t)ip.seq_span[sq]) * ba::INDEX_SPAN, last = first + ba::INDEX_SPAN < nw ? first + ba::INDEX_SPAN : nw;
-        uint64_t prev = NO_KEY;   // the minimizer of the window before the chunk
-        if (first != S) {         // the seam: window first - 1 lies over the k-mers first - 1 .. first + w - 2 (the sequence has more than w here)
-            for (uint32_t b = lane; b < w + k - 1u; b += 64u) L.two[b] = (uint8_t)two(first - 1u + b);
-            wave_sync();
-            uint32_t code;
-            prev = wave_min64(lane < w ? kmer_key(L, lane, first - 1u + lane, k, nk, code) : NO_KEY);
-            wave_sync();   // the first chunk overwrites what this read
-        }
-        const uint64_t out0 = EMIT ? ip.span_first[t] : 0ull;
-        uint32_t count = 0;
-        for (uint32_t s0 = first; s0 < last; s0 += 64u) {
-            const uint64_t m = chunk_minimizer(L, two, s0, last, k, w, nk, lane);   // (a window past the span's last one is the next span's)
-            const bool take = chunk_select(m, prev, lane);
-            const uint64_t ballot = __ballot(take);
-            if (EMIT && take) {
-                const uint32_t pos = (uint32_t)m;
-                ip.unsorted[out0 + count + (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull))] = (uint64_t)L.code[pos - s0] << 32 | pos;
-            }
-            count += (uint32_t)__popcll(ballot);
-            wave_sync();   // the next chunk overwrites what this one read
-        }
-        if (!EMIT && lane == 0) ip.span_cnt[t] = count;
-    }
+    index_sketch<false, EMIT>(ip, lds[threadIdx.x >> 6]);
 }
 
 __global__ void __launch_bounds__(TABLE_THREADS) k_index_table(const ba::IndexParams ip) {

@@ -5,10 +5,11 @@
 // tests/index_both_ref.py bit for bit. The kernels of ba_index.hip and ba_seeding.hip that do not look at a key's low word -- the sort of a
 // read's keys, the library sort of the index, the prefix table and the sort of the hits -- are launched as they are.
 //
-// k_both_index_sketch<EMIT>: k_index_sketch's spans, seams and sequence bounds over canonical k-mers (chunk_minimizer_canon); an entry is
-// written as code << 32 | strand << 31 | pos.
-// k_both_read_sketch<EMIT>: k_seeding_sketch's persistent wave per read, over the n reads only and always forward: seed_pos holds the strand
-// in bit 31, and q_key is an index key in the read's own frame.
+// The two sketches are the plain ones' code (ba_seed_device.hpp) with CANON set: the same work counter, chunk loop and selection.
+// k_both_index_sketch<EMIT>: k_index_sketch's body, index_sketch, over canonical k-mers; an entry is written as
+// code << 32 | strand << 31 | pos.
+// k_both_read_sketch<EMIT>: k_seeding_sketch's persistent wave per read and its loop, sketch_windows, over the n reads only and always
+// forward: seed_pos holds the strand in bit 31, and q_key is an index key in the read's own frame.
 // k_both_lookup<EMIT>: k_index_lookup's wave per read and 64 sorted read entries per step. A lane finds its code's run among the read's keys
 // and, through the prefix table, in the index, both strands together for the caps; one more search splits the index's run into its strand-0
 // and strand-1 entries. An index entry on the lane's own strand is a hit of problem 2 r, one on the other strand a hit of problem 2 r + 1
@@ -23,52 +24,12 @@ using namespace ba::seed;
 namespace {
 
 constexpr uint32_t SKETCH_WAVES = 4, LOOKUP_WAVES = 4;
-static_assert(ba::INDEX_SPAN % 64u == 0u, "a span is whole chunks");
 
 }  // namespace
 
 template <bool EMIT> __global__ void __launch_bounds__(64 * SKETCH_WAVES) k_both_index_sketch(const ba::IndexParams ip) {
     __shared__ CanonLds lds[SKETCH_WAVES];
-    const uint32_t lane = threadIdx.x & 63u;
-    CanonLds& L = lds[threadIdx.x >> 6];
-    const uint32_t k = ip.k, w = ip.w;
-    for (;;) {
-        __builtin_amdgcn_wave_barrier();   // (a convergence point, as in k_index_sketch)
-        uint32_t t = 0;
-        if (lane == 0) t = atomicAdd(ip.counter, 1u);
-        __builtin_amdgcn_wave_barrier();
-        t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
-        if (t >= ip.n_spans) break;
-        const uint32_t sq = lower_bound(ip.seq_span, ip.n_seqs + 1u, (uint64_t)t + 1u) - 1u;   // the span's sequence, as in k_index_sketch
-        const uint32_t S = (uint32_t)ip.seq_start[sq], E = (uint32_t)ip.seq_start[sq + 1u];   // its bytes, in the index's frame (E - S >= k)
-        const uint32_t nk = E - k + 1u;                          // one past its last k-mer
-        const uint32_t nw = nk - S > w ? nk - w + 1u : S + 1u;   // one past its last window
-        const auto two = [&](uint32_t i) { return i >= S && i < E ? two_bits(ip.ref[i], false) : 4u; };   // (no byte of a neighbour)
-        const uint32_t first = S + (t - (uint32_t)ip.seq_span[sq]) * ba::INDEX_SPAN, last = first + ba::INDEX_SPAN < nw ? first + ba::INDEX_SPAN : nw;
-        uint64_t prev = NO_KEY;   // the minimizer of the window before the chunk
-        if (first != S) {         // the seam: window first - 1 lies over the k-mers first - 1 .. first + w - 2
-            for (uint32_t b = lane; b < w + k - 1u; b += 64u) L.two[b] = (uint8_t)two(first - 1u + b);
-            wave_sync();
-            uint32_t code, strand;
-            prev = wave_min64(lane < w ? kmer_key_canon(L, lane, first - 1u + lane, k, nk, code, strand) : NO_KEY);
-            wave_sync();   // the first chunk overwrites what this read
-        }
-        const uint64_t out0 = EMIT ? ip.span_first[t] : 0ull;
-        uint32_t count = 0;
-        for (uint32_t s0 = first; s0 < last; s0 += 64u) {
-            const uint64_t m = chunk_minimizer_canon(L, two, s0, last, k, w, nk, lane);
-            const bool take = chunk_select(m, prev, lane);
-            const uint64_t ballot = __ballot(take);
-            if (EMIT && take) {
-                const uint32_t pos = (uint32_t)m;
-                ip.unsorted[out0 + count + (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull))] =
-                    (uint64_t)L.code[pos - s0] << 32 | (uint64_t)L.strand[pos - s0] << 31 | pos;
-            }
-            count += (uint32_t)__popcll(ballot);
-            wave_sync();   // the next chunk overwrites what this one read
-        }
-        if (!EMIT && lane == 0) ip.span_cnt[t] = count;
-    }
+    index_sketch<true, EMIT>(ip, lds[threadIdx.x >> 6]);
 }
 
 // sp.n: the reads; sp.seq_off, sp.seq_len and sp.seq_order are theirs (n each), and no sequence is a reference's.
@@ -78,33 +39,19 @@ template <bool EMIT> __global__ void __launch_bounds__(64 * SKETCH_WAVES) k_both
     CanonLds& L = lds[threadIdx.x >> 6];
     const uint32_t k = sp.k, w = sp.w;
     for (;;) {
-        __builtin_amdgcn_wave_barrier();   // (a convergence point, as in k_seeding_sketch)
-        uint32_t t = 0;
-        if (lane == 0) t = atomicAdd(sp.counter, 1u);
-        __builtin_amdgcn_wave_barrier();
-        t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+        const uint32_t t = next_work(sp.counter, lane);
         if (t >= sp.n) break;
         const uint32_t s = sp.seq_order[t], len = sp.seq_len[s];
         const uint8_t* seq = sp.pool + sp.seq_off[s];
         const uint32_t nk = len >= k ? len - k + 1u : 0u;                  // k-mers
         const uint32_t nw = nk == 0u ? 0u : nk > w ? nk - w + 1u : 1u;     // windows
         const uint64_t out0 = EMIT ? sp.seed_first[s] : 0ull;
-        uint32_t count = 0;
-        uint64_t prev = NO_KEY;   // the minimizer of the window before the chunk
         const auto two = [&](uint32_t i) { return i < len ? two_bits(seq[i], false) : 4u; };   // (a read is never reversed for its sketch)
-        for (uint32_t s0 = 0; s0 < nw; s0 += 64u) {
-            const uint64_t m = chunk_minimizer_canon(L, two, s0, nw, k, w, nk, lane);
-            const bool take = chunk_select(m, prev, lane);
-            const uint64_t ballot = __ballot(take);
-            if (EMIT && take) {
-                const uint32_t pos = (uint32_t)m, code = L.code[pos - s0], low = (uint32_t)L.strand[pos - s0] << 31 | pos;
-                const uint64_t at = out0 + count + (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull));
-                sp.seed_pos[at] = low; sp.seed_code[at] = code;
-                sp.q_key[at] = (uint64_t)code << 32 | low;
-            }
-            count += (uint32_t)__popcll(ballot);
-            wave_sync();   // the next chunk overwrites what this one read
-        }
+        const uint32_t count = sketch_windows<true, EMIT>(L, two, 0u, nw, k, w, nk, NO_KEY, lane, [&](uint32_t i, uint32_t code, uint32_t low) {
+            const uint64_t at = out0 + i;
+            sp.seed_pos[at] = low; sp.seed_code[at] = code;
+            sp.q_key[at] = (uint64_t)code << 32 | low;
+        });
         if (!EMIT && lane == 0) sp.seed_cnt[s] = count;
     }
 }

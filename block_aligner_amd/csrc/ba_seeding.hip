@@ -3,12 +3,10 @@
 // everything is integer arithmetic, so the kernels equal the model of tests/seeding_ref.py bit for bit.
 //
 // k_seeding_sketch<EMIT>: the (w, k)-minimizer sketch of every sequence, as a count pass and an emit pass with a scan of the counts between
-// them. One wave per sequence at a time, persistent, the sequences longest first through a work counter. A chunk is 64 consecutive windows:
-// the wave stages the chunk's bytes and a halo of k + w - 2 more in LDS as two-bit codes (4: not ACGT; a minus-strand query is read from its
-// end and complemented), computes code and order key (h << 32 | pos, all ones for an invalid k-mer) of the 63 + w k-mers under those windows,
-// one or two per lane, and every lane takes the minimum of its window's w keys. A window's minimizer is selected when it differs from the
-// window's before it -- the minimizers of consecutive windows never go back --, and the selected ones are compacted by a ballot and a running
-// count. A query's entries are also written as sort keys, code << 32 | pos.
+// them. One wave per sequence at a time, persistent, the sequences longest first through a work counter. The kernel says how a byte is read
+// (4: not ACGT; a minus-strand query is read from its end and complemented) and where an entry goes; the loop over the sequence's windows,
+// 64 at a time, is sketch_windows of ba_seed_device.hpp, which the index's sketches run as well. A query's entries are also written as sort
+// keys, code << 32 | pos.
 // k_seeding_sort: one workgroup per problem sorts the query's keys with a normalized bitonic network: every compare-exchange is ascending,
 // so an entry past the end would never move, and a pair whose partner lies past the end is skipped: no padding. Up to 8192 entries in LDS,
 // more than that in the problem's own slice of global memory, the same network between workgroup barriers.
@@ -20,7 +18,7 @@
 #include "ba_launch.h"
 #include "ba_seed_device.hpp"
 
-using namespace ba::seed;   // the helpers shared with ba_index.hip
+using namespace ba::seed;   // the helpers shared with ba_index.hip and ba_index_both.hip
 
 namespace {
 
@@ -34,11 +32,7 @@ template <bool EMIT> __global__ void __launch_bounds__(64 * SKETCH_WAVES) k_seed
     SketchLds& L = lds[threadIdx.x >> 6];
     const uint32_t k = sp.k, w = sp.w, n_seq = 2u * sp.n;
     for (;;) {
-        __builtin_amdgcn_wave_barrier();   // (a convergence point, as in k_chaining_fill)
-        uint32_t t = 0;
-        if (lane == 0) t = atomicAdd(sp.counter, 1u);
-        __builtin_amdgcn_wave_barrier();
-        t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+        const uint32_t t = next_work(sp.counter, lane);
         if (t >= n_seq) break;
         const uint32_t s = sp.seq_order[t], len = sp.seq_len[s];
         const uint8_t* seq = sp.pool + sp.seq_off[s];
@@ -46,22 +40,12 @@ template <bool EMIT> __global__ void __launch_bounds__(64 * SKETCH_WAVES) k_seed
         const uint32_t nk = len >= k ? len - k + 1u : 0u;                  // k-mers
         const uint32_t nw = nk == 0u ? 0u : nk > w ? nk - w + 1u : 1u;     // windows
         const uint64_t out0 = EMIT ? sp.seed_first[s] : 0ull;
-        uint32_t count = 0;
-        uint64_t prev = NO_KEY;   // the minimizer of the window before the chunk
         const auto two = [&](uint32_t i) { return i < len ? two_bits(seq[rc ? len - 1u - i : i], rc) : 4u; };
-        for (uint32_t s0 = 0; s0 < nw; s0 += 64u) {
-            const uint64_t m = chunk_minimizer(L, two, s0, nw, k, w, nk, lane);   // (a window past the last one selects nothing)
-            const bool take = chunk_select(m, prev, lane);
-            const uint64_t ballot = __ballot(take);
-            if (EMIT && take) {
-                const uint32_t pos = (uint32_t)m, code = L.code[pos - s0];
-                const uint64_t at = out0 + count + (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull));
-                sp.seed_pos[at] = pos; sp.seed_code[at] = code;
-                if (s < sp.n) sp.q_key[at] = (uint64_t)code << 32 | pos;   // (the queries' entries come first: the same index)
-            }
-            count += (uint32_t)__popcll(ballot);
-            wave_sync();   // the next chunk overwrites what this one read
-        }
+        const uint32_t count = sketch_windows<false, EMIT>(L, two, 0u, nw, k, w, nk, NO_KEY, lane, [&](uint32_t i, uint32_t code, uint32_t pos) {
+            const uint64_t at = out0 + i;
+            sp.seed_pos[at] = pos; sp.seed_code[at] = code;
+            if (s < sp.n) sp.q_key[at] = (uint64_t)code << 32 | pos;   // (the queries' entries come first: the same index)
+        });
         if (!EMIT && lane == 0) sp.seed_cnt[s] = count;
     }
 }

@@ -4,9 +4,11 @@ the chain model over the oracle."""
 import numpy as np
 import pytest
 
-from tests import chain_ref, chaining_ref, seeding_ref as S
+from tests import chain_ref, chaining_ref, index_both_ref as B, index_ref as X, seeding_ref as S
 from tests.test_gpu_chain import DNA_GAPS, NUC, X_DROP, check as check_chain_batch
 from tests.test_gpu_chaining import compare as compare_chainer
+from tests.test_gpu_index import compare as compare_indexed
+from tests.test_gpu_index_both import compare as compare_both
 
 pytestmark = pytest.mark.gpu
 
@@ -160,6 +162,79 @@ def test_reload_with_a_smaller_set_and_back(hip):
     with pytest.raises(RuntimeError, match="reload: .* problems exceed the batch's capacity"):
         sd.reload(*get_set("tiny", S.tiny_set).args())
     sd.close()
+
+
+GROWTH_K, GROWTH_W, GROWTH_OCC = 11, 5, 16
+# Reads of one length have about as many minimizers wherever they come from, so the generator's seed is one of those -- about one in three --
+# whose reads from the reference have more than its unrelated ones, plain and canonical: 394 against 368, and 391 against 377. The test asserts it.
+GROWTH_SEED = 52
+
+
+def growth_reads(seed: int = GROWTH_SEED):
+    """-> a reference of 2000 bases, 4 unrelated reads of 300, and 4 reads of 300 cut from the reference with 5 % of their bases
+    substituted -- the same count and the same bytes --, the second and the fourth of them reverse-complemented."""
+    rng = np.random.default_rng(seed)
+    ref = S.dna(rng, 2000)
+    unrelated = [S.dna(rng, 300) for _ in range(4)]
+    cut = []
+    for i in range(4):
+        a = int(rng.integers(0, 2000 - 300 + 1))
+        q = bytearray(ref[a:a + 300])
+        for j in np.nonzero(rng.random(300) < 0.05)[0].tolist():
+            q[j] = b"ACGT"[(b"ACGT".index(q[j]) + 1 + int(rng.integers(3))) % 4]   # another base
+        cut.append(B.revcomp(bytes(q)) if i % 2 else bytes(q))
+    return ref, unrelated, cut
+
+
+def growth_kinds(hip):
+    """Per kind of seeder -> (make(reads) -> (seeder, what to close with it), reload(seeder, reads), check(seeder, reads)): the reads that
+    were reverse-complemented go on the minus strand where the kind takes a strand."""
+    ref = get_set("growth", growth_reads)[0]
+    strands = [0, 1, 0, 1]
+    P = S.Params(GROWTH_K, GROWTH_W, GROWTH_OCC)
+    XP = X.Params(GROWTH_K, GROWTH_W, GROWTH_OCC, X.NO_CAP)
+    plain = lambda reads: S.ProblemSet([(q, ref, s) for q, s in zip(reads, strands)])   # noqa: E731
+    listed = lambda reads: X.ReadSet(list(zip(reads, strands)))                          # noqa: E731
+
+    def indexed(reads):
+        ix = hip.RefIndex(GROWTH_K, GROWTH_W, ref)
+        return hip.Seeder.indexed(ix, XP.max_occ, XP.max_ref_occ, *listed(reads).args()), ix
+
+    def both(reads):
+        ix = hip.RefIndex(GROWTH_K, GROWTH_W, ref, canonical=True)
+        return hip.Seeder.indexed_both(ix, XP.max_occ, XP.max_ref_occ, *B.Reads(reads).args()), ix
+
+    return dict(plain=(lambda reads: (hip.Seeder(*P, *plain(reads).args()), None), lambda sd, reads: sd.reload(*plain(reads).args()),
+                       lambda sd, reads: compare(sd, P, plain(reads).expected(P))),
+                indexed=(indexed, lambda sd, reads: sd.reload_indexed(*listed(reads).args()),
+                         lambda sd, reads: compare_indexed(sd, GROWTH_K, listed(reads).expected(ref, XP))),
+                both=(both, lambda sd, reads: sd.reload_indexed_both(*B.Reads(reads).args()),
+                      lambda sd, reads: compare_both(sd, GROWTH_K, B.expected(reads, [ref], XP))))
+
+
+@pytest.mark.parametrize("kind", ["plain", "indexed", "both"])
+def test_growth_between_runs(hip, kind):
+    """One handle from few seeds and close to no hits to many: the second run's buffers grow after its count passes, and the parameters of
+    its emit passes are read again. Every entry of the sketch and every hit of both runs against the kind's model, bit for bit; the second
+    run's times add up to what run() returned."""
+    _, unrelated, cut = get_set("growth", growth_reads)
+    make, reload, check = growth_kinds(hip)[kind]
+    sd, ix = make(unrelated)
+    sd.run()
+    check(sd, unrelated)
+    c = sd.counts()
+    seeds, hits = c["n_q_seeds"] + c["n_r_seeds"], c["n_hits"]
+    reload(sd, cut)
+    ms = sd.run()
+    check(sd, cut)
+    c = sd.counts()
+    assert c["n_q_seeds"] + c["n_r_seeds"] > seeds and c["n_hits"] > hits, (seeds, hits, c)   # (or nothing grew)
+    t = sd.times()
+    assert all(t[x] > 0 for x in ("sketch_ms", "sort_ms", "match_ms")), t
+    assert ms == pytest.approx(t["sketch_ms"] + t["sort_ms"] + t["match_ms"], rel=1e-6), (ms, t)
+    sd.close()
+    if ix is not None:
+        ix.close()
 
 
 def test_over_the_limit(hip):

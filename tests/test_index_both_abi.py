@@ -169,10 +169,16 @@ def test_the_messages_of_mixed_use_name_the_other_call():
 
 
 def test_the_release_library_reads_no_environment_variable_in_the_new_calls():
+    """(The both-strand seeder is loaded and run by the seeding section's code, so both sections that hold a part of it are read whole.)"""
     host = open(os.path.join(ROOT, "block_aligner_amd", "csrc", "ba_host.cpp")).read()
+    for first, last in (("// ------------------------------------------------------------------ minimizer seeding (ba_seeding_*)",
+                         "// ------------------------------------------------------------------ read-level selection (ba_select_*)"),
+                        ("// ------------------------------------------------------------------ the reference index (ba_ref_index_*, ba_seeding_*_indexed)",
+                         "// Candidate windows for chain batches")):
+        a, b = host.index(first), host.index(last)
+        assert a < b and "getenv" not in host[a:b], first
     a = host.index("both strands at once (ba_seeding_*_indexed_both)")
-    b = host.index("// Candidate windows for chain batches")
-    assert a < b and "getenv" not in host[a:b]
+    assert host.index("the reference index (ba_ref_index_*, ba_seeding_*_indexed)") < a < host.index("// Candidate windows for chain batches")
 
 
 # ------------------------------------------------------------------ the kernels
@@ -207,13 +213,29 @@ def test_kernel_hash_makefile_and_launch_header_list_the_new_unit():
         assert f in launch
 
 
-def test_the_old_kernels_stay_as_they_are():
-    """The units that today's paths run hold none of the new code: no canonical helper is named in them, and SketchLds keeps its fields."""
+@pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
+def test_the_sketch_kernels_keep_their_resources(tmp_path):
+    """The plain and the canonical sketches are one loop (ba_seed_device.hpp). What the older paths' kernels must not pay for the newer
+    ones is stated as what the compiler reports for all eight: no scratch, 8 waves per SIMD, and the LDS of their own staging area -- 4
+    waves of 1728 bytes, and of 1856 with the canonical k-mers' strand bytes. The figures are those of the kernels before they shared."""
     csrc = os.path.join(ROOT, "block_aligner_amd", "csrc")
-    for f in ("ba_seeding.hip", "ba_index.hip"):
-        text = open(os.path.join(csrc, f)).read()
-        assert "canon" not in text.lower() and "CanonLds" not in text, f
-    dev = open(os.path.join(csrc, "ba_seed_device.hpp")).read()
-    m = re.search(r"struct SketchLds \{[^}]*\}", dev)
-    assert m and re.sub(r"\s+", " ", m.group(0)) == ("struct SketchLds { // one wave's uint64_t key[CHUNK_KEYS]; uint32_t code[CHUNK_KEYS]; "
-                                                      "uint8_t two[CHUNK_BYTES]; }")
+    units = ("ba_seeding", "ba_index", "ba_index_both")
+    runs = [subprocess.Popen(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Rpass-analysis=kernel-resource-usage",
+                              "-c", os.path.join(csrc, u + ".hip"), "-o", str(tmp_path / (u + ".o"))], stderr=subprocess.PIPE, text=True) for u in units]
+    figures = {}
+    for u, r in zip(units, runs):
+        err = r.communicate()[1]
+        assert r.returncode == 0, err
+        name = None
+        for line in err.splitlines():
+            m = re.search(r"Function Name: (\S+)", line)
+            if m:
+                name = m.group(1)
+                figures[name] = {}
+            m = re.search(r"(ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", line)
+            if m and name:
+                figures[name][m.group(1).split(" [")[0]] = int(m.group(2))
+    lds = {"k_seeding_sketch": 6912, "k_index_sketch": 6912, "k_both_index_sketch": 7424, "k_both_read_sketch": 7424}
+    for kernel, size in lds.items():
+        got = [v for f, v in figures.items() if re.search(rf"\d{kernel}ILb[01]E", f)]
+        assert got == [dict(ScratchSize=0, Occupancy=8, **{"LDS Size": size})] * 2, (kernel, got)   # the count pass and the emit pass
